@@ -15,6 +15,14 @@ of the ranks.  Rank 0 prints ONE JSON line.
 value = batch-256 grad steps per second summed over GPUs (= global samples/s / 256).  For N > 1 the
 line also carries a `strong` block: the same global batch of 256 split over the ranks (256/N samples
 per GPU), i.e. true optimiser steps per second.
+
+A plain run (`--steps K --warmup W`) does only what the headline needs: it builds the module, takes W warm-up
+steps, conditions the chip (`--condition-ms`), times exactly K steps and prints the line.  Everything else it
+can measure - the unconditioned region, the per-step distribution, the roofline probes of the encoder launch,
+the `strong` block, the other configurations and the segment probe (`configs`), the CPU baseline - runs only
+with `--full` (the `--no-*` switches then leave out single pieces of it).  `--dump-outputs DIR` writes what the
+last timed step computed (its logged scalars, sampled latent plan and the updated trainable parameters) as
+DIR/<name>.npy, so that two builds can be compared output for output: the inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -513,6 +521,32 @@ def condition_chip(mod, ms):
     return round((time.perf_counter() - t0) * 1e3, 1)
 
 
+DUMP_MAX_ELEMS = 1 << 22  # per array (16 MB in fp32); a larger output is dumped as a fixed, seeded sample of its elements
+
+
+def dump_outputs(mod, logs, out_dir):
+    """`--dump-outputs DIR`: what the last timed training_step computed, as DIR/<name>.npy - every logged scalar
+    (metric_<slot>.npy, float64), the sampled latent plan (latent_plan.npy, float32 [B, latent]) and the trainable
+    parameters it updated (param_<net>.npy, float32: the flat blocks of the actor, both critics and their targets, and
+    log_alpha / log_alpha_prime)."""
+    import numpy as np
+
+    e = mod.engine
+    arrays = {f"metric_{k}": np.array([v], dtype=np.float64) for k, v in logs.items()}
+    arrays["latent_plan"] = mod.plan
+    for name, blk in (("actor", e.actor), ("q1", e.q1), ("q2", e.q2), ("q1_target", e.tq1), ("q2_target", e.tq2),
+                      ("log_alpha", e.log_alpha), ("log_alpha_prime", e.log_alpha_prime)):
+        arrays[f"param_{name}"] = blk.param
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        if torch.is_tensor(x):
+            x = x.detach().float().cpu().numpy()
+        if x.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_ELEMS, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+
+
 def timed_steps(mod, batch, steps, barrier):
     """Contract region: exactly `steps` training steps between barrier + synchronize on both sides."""
     barrier()
@@ -744,11 +778,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (unconditioned region, per-step distribution, roofline "
+                         "probes, strong scaling, the `configs` block, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (logged scalars, latent plan, updated parameters) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-distribution", action="store_true", help="skip the per-step HIP-event statistics")
+    ap.add_argument("--no-distribution", action="store_true", help="with --full: skip the per-step HIP-event statistics")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the ~10 s `configs` block (C3 / C4 share / C5 / PlayLMP / hbm feeder after the headline region)")
+                    help="with --full: skip the `configs` block (C3 / C4 share / C5 / PlayLMP / hbm feeder / segment probe "
+                         "after the headline region)")
     ap.add_argument("--launch-check", action="store_true", help="rendezvous + one host all-reduce only (launcher test)")
     ap.add_argument("--ad-every", type=int, default=1,
                     help="evaluate the (logging-only, frozen) action-decoder loss every k-th step; 1 = every step "
@@ -768,6 +809,8 @@ def main():
                          "to back for this many ms (no training step, no parameter changes; 0 = none).  Behind the host-side "
                          "capture the chip clocks up over ~25 steps: without it a 20-step region reads 2-3 %% above the steady state")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.probe == "segments":
         return segment_probe(a.dtype)
@@ -860,7 +903,7 @@ def main():
             coll_form += " (in-graph capture was refused)"
     # (VERDICT r5 / advisor: the same K steps right behind the warm-up, WITHOUT conditioning, reported beside the headline)
     uncond_ms = None
-    if a.condition_ms > 0:
+    if a.full and a.condition_ms > 0:
         uncond_ms = round(max_over_ranks(timed_steps(mod, batch, a.steps, barrier)) / a.steps * 1e3, 4)
         heartbeat("timed unconditioned")
     cond_ms = condition_chip(mod, a.condition_ms)
@@ -876,13 +919,17 @@ def main():
     heartbeat("timed")
     logs = mod.engine.metrics()
     finite = all(v == v and abs(v) < 1e30 for v in logs.values())
-    dist_stats = None if a.no_distribution else step_time_distribution(mod, batch, ms_step)
-    # the roofline probe of the dominant kernel, taken here - straight behind the timed steps, the chip in the clock state
-    # the step runs in (behind the other blocks below, after a module teardown, the same launch read up to 8 % slower)
-    enc_probe = time_encoder_fwd(mod, B, H, W) if rank == 0 else None
-    # (training steps: on N ranks they hold the step's all-reduces, so every rank runs them; rank 0's reading is reported)
-    enc_in_step = time_encoder_in_step(mod, batch)
-    heartbeat("probes")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(mod, logs, a.dump_outputs)
+    dist_stats = step_time_distribution(mod, batch, ms_step) if a.full and not a.no_distribution else None
+    enc_probe = enc_in_step = None
+    if a.full:
+        # the roofline probe of the dominant kernel, taken here - straight behind the timed steps, the chip in the clock state
+        # the step runs in (behind the other blocks below, after a module teardown, the same launch read up to 8 % slower)
+        enc_probe = time_encoder_fwd(mod, B, H, W) if rank == 0 else None
+        # (training steps: on N ranks they hold the step's all-reduces, so every rank runs them; rank 0's reading is reported)
+        enc_in_step = time_encoder_in_step(mod, batch)
+        heartbeat("probes")
 
     def replicas_in_sync():
         e = mod.engine
@@ -899,7 +946,7 @@ def main():
             # a form whose all-reduces did not reduce is a failed attempt: the supervisor moves on to the next one
             sys.exit(f"[rank {rank}] replicas out of sync after the timed steps with {coll_form}")
         # strong scaling: the SAME global batch of 256, 256/N samples per GPU -> true optimiser steps per second
-        if B % world == 0:
+        if a.full and B % world == 0:
             sb = synth_batch(B // world, T, H, W, dev, DATA_SEED + 100 + rank)
             for _ in range(a.warmup):
                 mod.training_step(sb)
@@ -917,7 +964,7 @@ def main():
         for _ in range(3):
             mod.training_step(batch)
     configs = None
-    if world == 1 and not a.no_configs and a.frames == "f32" and not a.launch_check:
+    if world == 1 and a.full and not a.no_configs and a.frames == "f32" and not a.launch_check:
         # (after the contract's timed region; `value` is untouched)
         configs = {}
         if a.feeder == "none":
@@ -947,10 +994,27 @@ def main():
 
     out = None
     if rank == 0:
-        b2b_ms, n_img, fused = enc_probe
-        enc_ms = enc_in_step[0] if (fused and enc_in_step is not None) else b2b_ms
-        tflops = n_img * ENC_FLOP_PER_IMG_84 / (enc_ms * 1e-3) / 1e12
-        peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else PEAK_F32_TFLOPS
+        roofline = None
+        if a.full:
+            b2b_ms, n_img, fused = enc_probe
+            enc_ms = enc_in_step[0] if (fused and enc_in_step is not None) else b2b_ms
+            tflops = n_img * ENC_FLOP_PER_IMG_84 / (enc_ms * 1e-3) / 1e12
+            peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else PEAK_F32_TFLOPS
+            roofline = {"bound": "mfma", "achieved": round(tflops, 2), "peak": peak, "unit": "TFLOP/s",
+                        "frac": round(tflops / peak, 4), "traffic": measured_traffic(n_img, fused, a.dtype),
+                        "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE, profiles/)",
+                        "kernel": ("encoder_fused_kernel: the step's single LMPVisionEncoder forward launch "
+                                   "(all 27*B encoder images: frozen LMP B*T frames, actor/q1/q2 over "
+                                   "[obs;goal], actor(next), both targets)") if fused else
+                                  "LMPVisionEncoder forward, per-layer kernels (tacorl_encoder_fwd)",
+                        "images_per_launch": n_img, "avg_ms": round(enc_ms, 4),
+                        "how": ("HIP events around the launch inside 40 training steps (eager replays of the step), minus the "
+                                "bracket's launch gaps, measured on a 120 us one-thread spin kernel that records its own "
+                                "duration, bracketed right behind it"
+                                if (fused and enc_in_step is not None) else "HIP events over 100 back-to-back launches"),
+                        "event_bracket_ms": round(enc_in_step[1], 4) if enc_in_step else None,
+                        "event_overhead_ms": round(enc_in_step[2], 4) if enc_in_step else None,
+                        "back_to_back_ms": round(b2b_ms, 4)}
         out = {
             "metric": "offline grad-steps/sec (batch=256, 84x84 RGB)",
             "value": round(world * (B / 256.0) / (ms_step * 1e-3), 3),
@@ -979,23 +1043,9 @@ def main():
             "strong": strong,
             "feeder": feeder,
             "configs": configs,
-            "roofline": {"bound": "mfma", "achieved": round(tflops, 2), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(tflops / peak, 4), "traffic": measured_traffic(n_img, fused, a.dtype),
-                         "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE, profiles/)",
-                         "kernel": ("encoder_fused_kernel: the step's single LMPVisionEncoder forward launch "
-                                    "(all 27*B encoder images: frozen LMP B*T frames, actor/q1/q2 over "
-                                    "[obs;goal], actor(next), both targets)") if fused else
-                                   "LMPVisionEncoder forward, per-layer kernels (tacorl_encoder_fwd)",
-                         "images_per_launch": n_img, "avg_ms": round(enc_ms, 4),
-                         "how": ("HIP events around the launch inside 40 training steps (eager replays of the step), minus the "
-                                 "bracket's launch gaps, measured on a 120 us one-thread spin kernel that records its own "
-                                 "duration, bracketed right behind it"
-                                 if (fused and enc_in_step is not None) else "HIP events over 100 back-to-back launches"),
-                         "event_bracket_ms": round(enc_in_step[1], 4) if enc_in_step else None,
-                         "event_overhead_ms": round(enc_in_step[2], 4) if enc_in_step else None,
-                         "back_to_back_ms": round(b2b_ms, 4)},
+            "roofline": roofline,
         }
-        if world == 1 and not a.no_cpu_baseline and a.frames == "f32":
+        if world == 1 and a.full and not a.no_cpu_baseline and a.frames == "f32":
             bc = {"states": {"rgb_static": batch["states"]["rgb_static"].cpu()},
                   "goal": {"rgb_static": batch["goal"]["rgb_static"].cpu()}, "actions": batch["actions"].cpu(),
                   "disp": batch["disp"].cpu()}

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 tag=$1
 O=gpurun_out/ab_$tag; mkdir -p $O
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-distribution > $O/bench.json 2> $O/trace.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-distribution > $O/bench.json 2> $O/trace.err
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv 2>/dev/null
 python scratch/stats_top.py $O/trace 23 > $O/stats_top.txt
 rm -rf $O/trace

@@ -18,7 +18,7 @@ def test_two_ranks_stay_in_sync():
     env = dict(os.environ, TACORL_DIST_BACKEND="gloo", TACORL_BENCH_SINGLE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--batch", "64", "--no-cpu-baseline"]
+           "--batch", "64", "--full", "--no-cpu-baseline"]
     out = run_group(cmd, env, ROOT, timeout=420)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -35,7 +35,7 @@ def test_bench_self_launcher_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(TACORL_DIST_BACKEND="gloo", TACORL_BENCH_SINGLE_DEVICE="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "64",
-           "--no-cpu-baseline", "--no-distribution"]
+           "--full", "--no-cpu-baseline", "--no-distribution"]
     out = run_group(cmd, env, ROOT, timeout=420)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -52,7 +52,7 @@ def test_bench_supervisor_falls_back_when_a_rank_hangs_in_the_step():
                TACORL_BENCH_INJECT_HANG="segments:1", TACORL_BENCH_STAGE_TIMEOUT="45")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--batch", "64", "--no-cpu-baseline", "--no-distribution"]
+           "--batch", "64", "--full", "--no-cpu-baseline", "--no-distribution"]
     out = run_group(cmd, env, ROOT, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

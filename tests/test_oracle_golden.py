@@ -9,6 +9,18 @@ from tests.golden_util import Golden, check_stats, spec_for
 
 PARAM_ATOL = 1e-5  # ~3% of one Adam update (lr 3e-4): near-zero grads flip under g/(|g|+eps)
 RTOL = 2e-5  # fp32 re-association (de-duplicated encoders, fused grads) stays below this
+GRAD_RTOL = 5e-5
+# A spatial soft-argmax temperature's gradient is one fp32 sum over every activation of its encoder, most of which cancels,
+# so its last digits follow the CPU's vector kernels: on cql_n32 step 1 the reference's own fp32 value lies 7.7e-5 (relative)
+# from the fp64 evaluation, and the oracle's AVX2 / AVX-512 kernels land 7.0e-5 / 1.6e-5 from the reference's.
+TEMPERATURE_GRAD_RTOL = 2e-4
+
+
+def _check_grads(got, exp):
+    temp = {k: v for k, v in exp.items() if k.endswith(".temperature")}
+    rest = {k: v for k, v in exp.items() if k not in temp}
+    return (check_stats(got, rest, rtol=GRAD_RTOL, what="grad ")
+            + check_stats(got, temp, rtol=TEMPERATURE_GRAD_RTOL, what="grad "))
 
 
 def _check_logs(got, exp, rtol=RTOL):
@@ -37,7 +49,7 @@ def test_tacorl_step_matches_reference(name, faithful):
         assert set(exp) - set(logs) == set(), set(exp) - set(logs)
         bad = _check_logs(logs, exp)
         assert torch.allclose(plan, g.latent_plan(step), rtol=1e-5, atol=1e-6)
-        bad += check_stats(grads, g.stats(step, "grad"), rtol=5e-5, what="grad ")
+        bad += _check_grads(grads, g.stats(step, "grad"))
         bad += check_stats(P, g.stats(step, "param"), rtol=RTOL, atol=PARAM_ATOL, what="param ")
         assert not bad, "\n".join(bad[:20])
 
@@ -51,7 +63,7 @@ def test_cql_step_matches_reference(name):
     for step in range(g.cfg["steps"]):
         logs, grads = O.cql_step(P, opts, spec, g.batch(step), g.noise(step), g.cfg["epoch"])
         bad = _check_logs(logs, g.logged(step))
-        bad += check_stats(grads, g.stats(step, "grad"), rtol=5e-5, what="grad ")
+        bad += _check_grads(grads, g.stats(step, "grad"))
         bad += check_stats(P, g.stats(step, "param"), rtol=RTOL, atol=PARAM_ATOL, what="param ")
         assert not bad, "\n".join(bad[:20])
 
@@ -65,7 +77,7 @@ def test_playlmp_step_matches_reference(name):
         logs, grads = O.playlmp_step(P, opt, g.batch(step), g.noise(step), sorted(g.cams),
                                      dropout_p=g.cfg.get("dropout_p", 0.0))
         bad = _check_logs(logs, g.logged(step))
-        bad += check_stats(grads, g.stats(step, "grad"), rtol=5e-5, what="grad ")
+        bad += _check_grads(grads, g.stats(step, "grad"))
         bad += check_stats(P, g.stats(step, "param"), rtol=RTOL, atol=PARAM_ATOL, what="param ")
         assert not bad, "\n".join(bad[:20])
 
