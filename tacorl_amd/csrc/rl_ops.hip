@@ -576,7 +576,8 @@ __global__ __launch_bounds__(256) void alpha_loss_kernel(const float* __restrict
 // The same loss and gradient, then Adam's step on log_alpha in the same launch (one GPU: the gradient needs no
 // all-reduce between the two; with several ranks tacorl_alpha_loss + collective #1 + tacorl_adam_step stay separate).
 // alpha_loss is logged with the PRE-step log_alpha as the reference does; the update is adam_kernel's arithmetic for a
-// single element without clipping (bit-identical to tacorl_adam_step(n = 1, max_norm = 0)).
+// single element without clipping (bit-identical to tacorl_adam_step(n = 1, max_norm = 0); tests/test_heads_gpu.py
+// test_alpha_loss_step_equals_loss_then_adam).
 __global__ __launch_bounds__(256) void alpha_loss_step_kernel(const float* __restrict__ logp, int B, float* log_alpha,
                                                               float target_entropy, float* g_log_alpha, float* logs,
                                                               float* m, float* v, float lr, int* step_counter) {
@@ -918,7 +919,7 @@ __global__ void bump_step_kernel(int* step_counter) { step_counter[0] += 1; }
 
 // Several parameter blocks in two launches (norms + step counters, updates) instead of three each:
 // the optimiser phase is the tail of the step's dependent chain.  Same per-block partitioning as
-// tacorl_adam_step, so results are bit-identical to it.
+// tacorl_adam_step, so results are bit-identical to it (tests/test_heads_gpu.py test_adam_step_batch_mirror).
 #define ADAM_MAXB 8
 struct AdamTbl {
   float* p[ADAM_MAXB];
