@@ -402,7 +402,9 @@ __global__ __launch_bounds__(256) void logistic_mixture_kernel(const float* __re
       const float lz = mg + logf(expf(g0 - mg) + expf(g1 - mg));
       const int y = actions[((long)b * T + t) * (Da + 1) + Da] == -1.0f ? 0 : (int)actions[((long)b * T + t) * (Da + 1) + Da];
       loss += gripper_alpha * (lz - (y ? g1 : g0));
-      hits += ((g1 > g0) ? 1 : 0) == y ? 1.f : 0.f;  // gripper_bounds[argmax] vs ground truth (play_lmp_for_rl.py:166-176)
+      // the +-1 command of the argmax class (ties: class 0, -1) == the raw label, so a label 0 never counts
+      // (play_lmp_for_rl.py:166-176; pinned by tests/test_seq_gpu.py::test_logistic_mixture_loss)
+      hits += actions[((long)b * T + t) * (Da + 1) + Da] == (g1 > g0 ? 1.f : -1.f) ? 1.f : 0.f;
       if (d_heads) {
         float* d = d_heads + r * ldh;
         d[3 * Da * K] = gR * gripper_alpha * (expf(g0 - lz) - (y == 0 ? 1.f : 0.f));
@@ -424,7 +426,8 @@ __global__ __launch_bounds__(256) void logistic_mixture_kernel(const float* __re
 // The same loss with the K mixtures of a (row, action dim) pair on 16 lanes (K <= 16): the per-mixture log-probability -
 // a dozen transcendentals - is computed once per lane and the two logsumexps over k are 16-lane butterflies, instead of
 // one thread looping over 10 mixtures (15.8 us for 3 MB of heads, on the logging-only action-decoder branch that is the
-// last thing of the step to finish).  Sums over k are taken in butterfly order (fixed: deterministic), not 0..K-1.
+// last thing of the step to finish).  Sums over k are taken in butterfly order (fixed: deterministic), not 0..K-1
+// (tests/test_seq_gpu.py::test_logistic_mixture_loss: the same loss bits with and without d_heads and by the lazy finish).
 __device__ __forceinline__ float grp16_max(float v) {
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 16));
@@ -496,7 +499,7 @@ __global__ __launch_bounds__(256) void logistic_mixture_k16_kernel(const float* 
       const float lz = mg + logf(expf(g0 - mg) + expf(g1 - mg));
       const int y = actions[((long)b * T + t) * (Da + 1) + Da] == -1.0f ? 0 : (int)actions[((long)b * T + t) * (Da + 1) + Da];
       loss += gripper_alpha * (lz - (y ? g1 : g0));
-      hits += ((g1 > g0) ? 1 : 0) == y ? 1.f : 0.f;
+      hits += actions[((long)b * T + t) * (Da + 1) + Da] == (g1 > g0 ? 1.f : -1.f) ? 1.f : 0.f;
       if (d_heads) {
         float* d = d_heads + r * ldh;
         d[3 * Da * K] = gR * gripper_alpha * (expf(g0 - lz) - (y == 0 ? 1.f : 0.f));
@@ -886,7 +889,8 @@ __global__ __launch_bounds__(256) void add_layernorm_bwd_kernel(const float* __r
 }
 // column sums of the [rows][2D] partial matrix: first D columns -> dw, last D -> db
 // (256 threads per 64 columns: four row phases with eight independent loads in flight each, summed in fixed order - one
-// thread per column over 128 dependent-latency rows took 30 us, four times per PlayLMP step at B = 32)
+// thread per column over 128 dependent-latency rows took 30 us, four times per PlayLMP step at B = 32; the order is pinned
+// by tests/test_seq_gpu.py::test_add_layernorm: a second run gives the same bits)
 __global__ __launch_bounds__(256) void colsum2_kernel(const float* __restrict__ in, int rows, int D, float* __restrict__ dw,
                                                       float* __restrict__ db, int accumulate) {
   __shared__ float part[4][64];
