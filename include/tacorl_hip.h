@@ -86,6 +86,17 @@ int tacorl_rnn_linear_fwd_batch_ext(int nprob, const void* const* x_bf16, const 
                                     void* const* y_bf16, void* const* y2_bf16, int M, int M2, int K, int N,
                                     const int* acts, const void* const* x_ext, const void* const* x2_ext,
                                     const void* const* w_ext, const float* const* bias2, tacorl_stream_t stream);
+/* The ring GEMM with row strides, for the bidirectional ReLU-RNN plan recognition (reference
+ * plan_encoders/plan_recognition_tanh_net.py: nn.RNN(num_layers=2, bidirectional=True)): nprob <= 4 problems
+ * y[p] = act(x[p] W[p]^T + x_ext[p] w_ext[p]^T + bias[p] + bias2[p] + addend[p]) * [mask_src[p] > 0] of one shape (M, K, N),
+ * x rows ldx apart (ldx % 8 == 0), y / y_bf16 / mask_src rows ldy apart (ldy % 4 == 0): both directions' step of a layer in
+ * one launch over column slices of the interleaved [T][B][2H] state; BPTT steps with W^T as w and the saved state as mask_src.
+ * Any array entry but x / w / y may be NULL; x_ext [M][128], w_ext [N][128] bf16 as in tacorl_rnn_linear_fwd_batch_ext. */
+int tacorl_rnn_linear_ld_supported(int M, int K, int N, int ldx, int ldy);
+int tacorl_rnn_linear_ld(int nprob, const void* const* x_bf16, int ldx, const void* const* w_bf16, const float* const* bias,
+                         const float* const* bias2, const float* const* addend, int ld_add, const void* const* x_ext,
+                         const void* const* w_ext, const float* const* mask_src, float* const* y, void* const* y_bf16, int ldy,
+                         int M, int K, int N, int act, tacorl_stream_t stream);
 /* out_bf16[(t*B + b)][0..127] = bf16([plan[b] (P) | emb[(b*T + t)] (E) | zeros]) for t < Tm: the time-major RNN input rows
  * (reference action_decoder_logistic.py:279-281) as the K-extension operand above. */
 int tacorl_build_ad_input_bf16(const float* plan, const float* emb, int ld_emb, void* out_bf16, int B, int T, int Tm,
@@ -120,6 +131,12 @@ int tacorl_rnn_wgrad_slabs(const void* dz_bf16, int ld_dz, const void* x_bf16, i
 int tacorl_rnn_linear_bwd_batch(int nprob, const void* const* x_bf16, const void* const* wt_bf16,
                                 const float* const* addend, int ld_add, const float* const* mask_src,
                                 float* const* y, void* const* y_bf16, int M, int K, int N, tacorl_stream_t stream);
+/* Row-order change between batch-major [n_outer][n_inner] and time-major [n_inner][n_outer] row blocks:
+ * dst[(i*n_outer + o)][0..cols) = src[(o*n_inner + i)][0..cols).  The bidirectional ReLU-RNN plan recognition
+ * (reference plan_encoders/plan_recognition_tanh_net.py, nn.RNN(num_layers=2, bidirectional=True)) runs its recurrence
+ * over time-major slabs: its input embeddings come in and its input gradient goes out batch-major. */
+int tacorl_birnn_swap_rows(const float* src, int ld_src, float* dst, int ld_dst, int n_outer, int n_inner, int cols,
+                           tacorl_stream_t stream);
 /* dst[c][r] = bf16(src[r][c]); R, C multiples of 32. */
 int tacorl_transpose_to_bf16(const float* src, void* dst, int R, int C, tacorl_stream_t stream);
 /* n <= 16 such transposes (dst[j][c][r] = bf16(src[j][r][c]), R[j] x C[j], multiples of 32) in ONE launch: the weights-only

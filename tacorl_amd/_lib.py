@@ -35,6 +35,8 @@ _SIGS = {
     "tacorl_rnn_linear_fwd_batch": (_i, [_i, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p]),
     "tacorl_rnn_linear_fwd_batch_twin": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "tacorl_rnn_linear_fwd_batch_ext": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "tacorl_rnn_linear_ld_supported": (_i, [_i, _i, _i, _i, _i]),
+    "tacorl_rnn_linear_ld": (_i, [_i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "tacorl_rnn_linear_bwd_step": (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p]),
     "tacorl_rnn_linear_bwd_batch": (_i, [_i, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p]),
     "tacorl_rnn_wgrad_supported": (_i, [_i, _i, _i]),
@@ -42,6 +44,7 @@ _SIGS = {
     "tacorl_rnn_wgrad_batch": (_i, [_i, _p, _i, _p, _i, _p, _i, _i, _p, _p, _i, _p]),
     "tacorl_rnn_wgrad_slabs_ws_bytes": (_sz, [_i, _i, _i]),
     "tacorl_rnn_wgrad_slabs": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _sz, _p]),
+    "tacorl_birnn_swap_rows": (_i, [_p, _i, _p, _i, _i, _i, _i, _p]),
     "tacorl_transpose_to_bf16": (_i, [_p, _p, _i, _i, _p]),
     "tacorl_transpose_to_bf16_batch": (_i, [_i, _p, _p, _p, _p, _p]),
     "tacorl_transpose_pad_to_bf16": (_i, [_p, _p, _i, _i, _i, _p]),

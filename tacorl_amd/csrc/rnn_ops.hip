@@ -50,6 +50,9 @@ struct RnnArgs {
   const __bf16* x2_ext;
   const __bf16* w_ext;
   const float* bias2;
+  // optional row strides (0: dense, K for x and N for y / yb / mask_src): the bidirectional RNN's steps read and write
+  // column slices of its interleaved [T][B][2H] state (tacorl_rnn_linear_ld)
+  int ldx, ldy;
 };
 
 // One RB_M x RB_N output tile per workgroup (4 waves stacked along M), RB_S-stage ring.
@@ -88,6 +91,7 @@ __global__ __launch_bounds__(64 * NW) void rnn_gemm_kernel(RnnBatch ab, int MT, 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, g = lane >> 4;
   const int m0 = mt * RB_M, n0 = ntile * RB_N;
   const int nkm = a.K / RB_K, nk = nkm + (a.x_ext ? 1 : 0), mtot = a.M + a.M2;
+  const long ldx = a.ldx ? a.ldx : a.K, ldy = a.ldy ? a.ldy : a.N;
 
   auto issue = [&](int kt, int slot) {
     unsigned char* base = lds + slot * STAGE_BYTES;
@@ -98,7 +102,7 @@ __global__ __launch_bounds__(64 * NW) void rnn_gemm_kernel(RnnBatch ab, int MT, 
       const int xm = m0 + r < mtot ? m0 + r : mtot - 1;  // rows past the last one are loaded (clamped) but never stored
       const __bf16* src;
       if (kt < nkm) {
-        const __bf16* xrow = xm < a.M ? a.x + (long)xm * a.K : a.x2 + (long)(xm - a.M) * a.K;
+        const __bf16* xrow = xm < a.M ? a.x + xm * ldx : a.x2 + (long)(xm - a.M) * a.K;
         src = (r < RB_M ? xrow : a.w + (long)(n0 + r - RB_M) * a.K) + kt * RB_K + c * 8;
       } else {  // the extension tile
         const __bf16* xrow = xm < a.M ? a.x_ext + (long)xm * RB_K : a.x2_ext + (long)(xm - a.M) * RB_K;
@@ -165,12 +169,13 @@ __global__ __launch_bounds__(64 * NW) void rnn_gemm_kernel(RnnBatch ab, int MT, 
 #pragma unroll
       for (int r = 0; r < 4; r++) z[r] = act_apply(a.act, z[r]);
       if (a.mask_src && !twin) {
-        const f32x4 ms = *reinterpret_cast<const f32x4*>(a.mask_src + (long)m * a.N + n);
+        const f32x4 ms = *reinterpret_cast<const f32x4*>(a.mask_src + m * ldy + n);
 #pragma unroll
         for (int r = 0; r < 4; r++) z[r] = ms[r] > 0.f ? z[r] : 0.f;
       }
-      *reinterpret_cast<f32x4*>(y + (long)m * a.N + n) = z;
-      if (yb) *reinterpret_cast<bf16x4*>(yb + (long)m * a.N + n) = bf16x4{(__bf16)z[0], (__bf16)z[1], (__bf16)z[2], (__bf16)z[3]};
+      const long ldo = twin ? (long)a.N : ldy;
+      *reinterpret_cast<f32x4*>(y + (long)m * ldo + n) = z;
+      if (yb) *reinterpret_cast<bf16x4*>(yb + (long)m * ldo + n) = bf16x4{(__bf16)z[0], (__bf16)z[1], (__bf16)z[2], (__bf16)z[3]};
     }
   }
 }
@@ -682,4 +687,42 @@ extern "C" int tacorl_rnn_linear_fwd_batch_ext(int nprob, const void* const* x_b
                                                const void* const* w_ext, const float* const* bias2, tacorl_stream_t stream) {
   return rnn_fwd_batch(nprob, x_bf16, w_bf16, bias, addend, ld_add, y, y_bf16, M, K, N, acts, x2_bf16, addend2, y2, y2_bf16, M2,
                        stream, x_ext, x2_ext, w_ext, bias2);
+}
+
+/* Strided form for the bidirectional ReLU-RNN plan recognition (reference plan_encoders/plan_recognition_tanh_net.py, torch
+ * nn.RNN(num_layers=2, bidirectional=True)): nprob <= 4 problems y[p] = act(x[p] W[p]^T + x_ext[p] w_ext[p]^T + bias[p] + bias2[p]
+ * + addend[p]) * [mask_src[p] > 0] of one shape, x rows ldx apart, y / y_bf16 / mask_src rows ldy apart - a step of both
+ * directions reads and writes its [B][H] column slice of the interleaved [T][B][2H] state in one launch.  Every array entry but
+ * x / w / y may be NULL (whole arrays too); x_ext [M][128] and w_ext [N][128] as in tacorl_rnn_linear_fwd_batch_ext.  BPTT steps
+ * pass Wt = W^T as w and the saved state as mask_src. */
+extern "C" int tacorl_rnn_linear_ld_supported(int M, int K, int N, int ldx, int ldy) {
+  return tacorl_rnn_linear_supported(M, K, N) && ldx >= K && ldx % 8 == 0 && ldy >= N && ldy % 4 == 0 ? 1 : 0;
+}
+extern "C" int tacorl_rnn_linear_ld(int nprob, const void* const* x_bf16, int ldx, const void* const* w_bf16, const float* const* bias,
+                                    const float* const* bias2, const float* const* addend, int ld_add, const void* const* x_ext,
+                                    const void* const* w_ext, const float* const* mask_src, float* const* y, void* const* y_bf16,
+                                    int ldy, int M, int K, int N, int act, tacorl_stream_t stream) {
+  if (nprob < 1 || nprob > RNN_MAXP || !tacorl_rnn_linear_ld_supported(M, K, N, ldx, ldy) || ld_add % 4) return TACORL_EINVAL;
+  RnnBatch ab{};
+  for (int p = 0; p < nprob; p++) {
+    const float* bi = bias ? bias[p] : nullptr;
+    const float* b2 = bias2 ? bias2[p] : nullptr;
+    const float* ad = addend ? addend[p] : nullptr;
+    const float* ms = mask_src ? mask_src[p] : nullptr;
+    const void* xe = x_ext ? x_ext[p] : nullptr;
+    const void* we = w_ext ? w_ext[p] : nullptr;
+    void* yb = y_bf16 ? y_bf16[p] : nullptr;
+    if (!x_bf16[p] || !w_bf16[p] || !y[p] || (xe != nullptr) != (we != nullptr)) return TACORL_EINVAL;
+    if (((uintptr_t)x_bf16[p] | (uintptr_t)w_bf16[p] | (uintptr_t)y[p] | (uintptr_t)bi | (uintptr_t)b2 | (uintptr_t)ad |
+         (uintptr_t)ms | (uintptr_t)xe | (uintptr_t)we) & 15)
+      return TACORL_EINVAL;
+    if ((uintptr_t)yb & 7) return TACORL_EINVAL;
+    RnnArgs& a = ab.p[p];
+    a.x = (const __bf16*)x_bf16[p]; a.w = (const __bf16*)w_bf16[p]; a.bias = bi; a.bias2 = b2; a.addend = ad; a.mask_src = ms;
+    a.y = y[p]; a.yb = (__bf16*)yb; a.M = M; a.K = K; a.N = N; a.ld_add = ld_add; a.act = act;
+    a.x_ext = (const __bf16*)xe; a.w_ext = (const __bf16*)we; a.ldx = ldx; a.ldy = ldy;
+  }
+  // a sequence-wide projection (M = B * T rows) takes the larger tile (fewer re-reads of W), a recurrent step the small one
+  if ((long)M * N >= 256L * 64 * 128 && N % 64 == 0) return launch_ring<128, 64, 3>(ab, nprob, (hipStream_t)stream);
+  return launch_small(ab, nprob, (hipStream_t)stream);
 }

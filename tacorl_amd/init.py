@@ -24,6 +24,8 @@ def init_views_(views, gen=None, rnn_hidden=None):
 
         if leaf == "temperature":
             t.fill_(1.0)
+        elif ".birnn_model." in name or name.startswith("birnn_model."):  # nn.RNN: every tensor U(+-1/sqrt(hidden))
+            U(1.0 / math.sqrt(t.shape[0]))
         elif ".rnn." in name or name.startswith("rnn."):
             U(1.0 / math.sqrt(rnn_hidden))
         elif any(k in pre for k in ("fc_mean.", "fc_log_std.", "gripper_action.", "critic.Q.out.", "Q.out.")):

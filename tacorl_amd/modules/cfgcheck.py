@@ -72,11 +72,17 @@ def check_critic(cfg, what):
 
 
 def check_plan_recognition(cfg, what):
-    """config/networks/plan_recognition/transformer.yaml (reference plan_recognition_transformer.py:10-68)."""
-    return _require(cfg, what, "PlanRecognitionTransformersNetwork",
-                    dict(encoder_normalize=False, positional_normalize=False, position_embedding=True),
-                    free=("num_heads", "num_layers", "encoder_hidden_size", "fc_hidden_size", "state_dim",
-                          "latent_plan_dim", "min_std", "dropout_p", "max_position_embeddings"))
+    """config/networks/plan_recognition/transformer.yaml (reference plan_recognition_transformer.py:10-68) or tanh_net.yaml
+    (plan_recognition_tanh_net.py: the bidirectional ReLU-RNN posterior, birnn_dropout_p 0 only).  Returns (which network:
+    "transformer" / "birnn", the honoured keys)."""
+    t = dict(cfg or {}).get("_target_")
+    if t is not None and _leaf(t) == "PlanRecognitionTanhNetwork":
+        return "birnn", _require(cfg, what, "PlanRecognitionTanhNetwork", dict(birnn_dropout_p=(0, 0.0)),
+                                 free=("state_dim", "latent_plan_dim", "min_std", "hidden_dim"))
+    return "transformer", _require(cfg, what, "PlanRecognitionTransformersNetwork",
+                                   dict(encoder_normalize=False, positional_normalize=False, position_embedding=True),
+                                   free=("num_heads", "num_layers", "encoder_hidden_size", "fc_hidden_size", "state_dim",
+                                         "latent_plan_dim", "min_std", "dropout_p", "max_position_embeddings"))
 
 
 def check_action_decoder(cfg, what):

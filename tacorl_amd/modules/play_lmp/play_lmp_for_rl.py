@@ -16,6 +16,7 @@ from ...engine import NetBlock
 from ...init import init_views_
 from ...networks.action_decoder import ActionDecoderLogistic
 from ...networks.plan_recognition import PlanRecognition
+from ...networks.plan_recognition_birnn import PlanRecognitionBiRNN
 from ...lightning import LightningModuleBase
 from .. import cfgcheck
 from ..common import GraphMixin, ModuleMixin, register_views, to_plain
@@ -62,10 +63,10 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self.policy_layers, self.hidden = pol.get("num_layers", 2), pol.get("hidden_dim", 256)
         cfgcheck.check_representation(self.pe_cfg, "perceptual_encoder", cams)
         cfgcheck.check_goal_encoder(self.ge_cfg, "goal_encoder", self.hidden)
-        prc = cfgcheck.check_plan_recognition(self.pr_cfg, "plan_recognition")
+        pr_kind, prc = cfgcheck.check_plan_recognition(self.pr_cfg, "plan_recognition")
         state_dim = 32 * len(self.plan_recognition_modalities)
         prc["state_dim"] = state_dim
-        self.pr = PlanRecognition(device=self.dev, **prc)
+        self.pr = (PlanRecognitionBiRNN if pr_kind == "birnn" else PlanRecognition)(device=self.dev, **prc)
         A = self.pr.latent_plan_dim
         E = 64 * len(cams)
         pdims = [E] + [self.hidden] * self.policy_layers + [2 * A]
