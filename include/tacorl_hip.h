@@ -645,6 +645,32 @@ int tacorl_adam_step_batch_mirror(int nb, float* const* param, const float* cons
                                   void* const* mirror, void* const* target_mirror, void* ws, size_t ws_bytes,
                                   tacorl_stream_t stream);
 
+/* ---- evaluation: cross-entropy-method refinement ---------------------------------- */
+/* CEMOptimizer.get_action (reference modules/cem/cem.py:69-104; evaluation/rollout_manager.py:99-136, :331-369) for R
+ * independent problem rows in ONE launch, one workgroup per row: `iters` times { population = clamp(mean + std * eps, -1, 1)
+ * (last dimension snapped to +-1 with discrete_gripper) -> Q of the N candidates -> the n_elite largest -> mean / std
+ * blended with alpha towards the elites' mean / unbiased std, std clamped to [min_std, max_std] }; out[r] = the best elite of
+ * all iterations (strict >).
+ *   nnet = 1: Q = net 0 (what the reference executes: it evaluates q1 twice); nnet = 2: Q = min(net 0, net 1).
+ *   s[n]: [R][E] embedding of the observation as net n's own encoders see it; params[n]: the net's Q head,
+ *   tacorl_mlp_param_layout of [E + A, hidden x q_layers, 1] with SiLU hidden layers (16-byte aligned);
+ *   params_bf16[n]: its bf16 mirror at the same element offsets (8-byte aligned; TACORL_BF16 only, else may be NULL).
+ *   mean0: [R][A] or NULL (zeros); eps: [R][iters][N][A] standard-normal draws; out: [R][A].
+ *   t_*: optional per-iteration trace (each may be NULL): population [R][iters][N][A], Q [R][iters][N], elite indices by
+ *   descending Q [R][iters][n_elite], mean and std after the update [R][iters][A].
+ *   ws: tacorl_cem_ws_bytes; on return [R][1 + 2 A] floats: best Q, final mean, final std of every row.
+ * Supported: hidden = 256, N a multiple of 64 up to 256, A <= 32, E <= 256, 2 <= q_layers <= 4; 2 <= n_elite <= N.
+ * TACORL_F32: fp32 MFMA on the fp32 weights; TACORL_BF16: bf16 MFMA on the mirror, activations rounded to bf16, fp32
+ * accumulation.  Population, Q values, selection and statistics are fp32 in both.  Arguments are validated before
+ * anything touches the device. */
+int tacorl_cem_supported(int N, int A, int E, int hidden, int q_layers, int compute_dtype);
+size_t tacorl_cem_ws_bytes(int R, int N, int A, int E, int hidden, int q_layers, int compute_dtype); /* 0: not supported */
+int tacorl_cem_refine(int R, int nnet, const float* const* s, const float* const* params,
+                      const void* const* params_bf16, const float* mean0, const float* eps, float* out, int N, int A,
+                      int E, int hidden, int q_layers, int iters, int n_elite, float min_std, float max_std, float alpha,
+                      int discrete_gripper, int compute_dtype, float* t_pop, float* t_q, int* t_elite, float* t_mean,
+                      float* t_std, void* ws, size_t ws_bytes, tacorl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

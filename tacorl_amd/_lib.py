@@ -153,6 +153,10 @@ _SIGS = {
     "tacorl_adam_batch_ws_bytes": (_sz, [_i]),
     "tacorl_adam_step_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "tacorl_adam_step_batch_mirror": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "tacorl_cem_supported": (_i, [_i, _i, _i, _i, _i, _i]),
+    "tacorl_cem_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "tacorl_cem_refine": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p,
+                               _p, _sz, _p]),
 }
 
 _lib = None

@@ -117,7 +117,8 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
             self.log_alpha_prime = nn.Parameter(e.log_alpha_prime.param)
         from ..inference import attach_rollout_surface
 
-        attach_rollout_surface(self, e.actor, e.cams, self.goal_modalities, self.action_dim, e.dg)
+        attach_rollout_surface(self, e.actor, e.cams, self.goal_modalities, self.action_dim, e.dg,
+                               critics={"q1": e.q1, "q2": e.q2, "target_q1": e.tq1, "target_q2": e.tq2})
 
     def _all_blocks(self):
         e = self.engine

@@ -2,7 +2,9 @@
 `module.actor.get_actions(obs, deterministic, reparameterize)` (actor.py:65-111 through
 visual_actor_wrapper.py:41-76), `module.perceptual_encoder.get_state_from_observation(observation, modalities)`
 (representation_network.py:36-71), `module.action_decoder.act / clear_hidden_state`
-(action_decoder_logistic.py:73-97).  Small-batch latency path on the library's per-layer kernels (any number of
+(action_decoder_logistic.py:73-97), and the critics `module.q1(obs, action)` / `q2` / `target_q1` / `target_q2` with
+`get_emb_representation` / `get_emb_obs_representation` (visual_critic_wrapper.py:35-75), which CEM refinement
+(modules/cem.py) is built on.  Small-batch latency path on the library's per-layer kernels (any number of
 images, any camera geometry); nothing here is captured in a graph or keeps gradients.
 """
 import torch
@@ -104,9 +106,77 @@ class ActorSurface:
         return act, logp.view(n, 1)
 
 
+class CriticSurface:
+    """Bound onto `module.q1` (q2, target_q1, target_q2): VisualCriticWrapper + Critic + MLPQNetwork of one network block.
+    Calling the container returns Q(obs, action) as (n, 1)."""
+
+    def __init__(self, owner, net, cams, goal_cams, action_dim, runner=None):
+        self.owner, self.net, self.cams, self.goal_cams = owner, net, list(cams), list(goal_cams)
+        self.A = int(action_dim)
+        self.E = net.head_dims[0] - self.A
+        self.hidden, self.q_layers = net.head_dims[1], len(net.head_dims) - 2
+        self.runner = runner or EncoderRunner(owner)
+
+    def emb_obs_representation(self, obs):
+        """The observation's embedding without the goal (visual_critic_wrapper.py:35-48); a tensor passes through."""
+        if not isinstance(obs, dict):
+            return obs.to(self.owner.dev, torch.float32)
+        od = obs["observation"] if self.goal_cams and "goal" in obs else obs
+        return state_from_observation(self.owner, self.runner, self.net, od, self.cams)
+
+    def emb_representation(self, obs):
+        """[enc(obs) | goal_encoder(enc(goal))] with this critic's own encoders (visual_critic_wrapper.py:50-71)."""
+        if not isinstance(obs, dict):
+            return obs.to(self.owner.dev, torch.float32)
+        o, net = self.owner, self.net
+        if not (self.goal_cams and "goal" in obs):
+            return state_from_observation(o, self.runner, net, obs, self.cams)
+        e_obs = state_from_observation(o, self.runner, net, obs["observation"], self.cams)
+        e_goal = state_from_observation(o, self.runner, net, obs["goal"], self.goal_cams)
+        n = e_obs.shape[0]
+        gact = torch.zeros(ops.mlp_act_layout(n, net.genc_dims, net.genc_acts)[2], device=o.dev)
+        ops.mlp_fwd([e_goal], e_goal.shape[1], [net.genc()], [gact], [n], net.genc_dims, net.genc_acts, o.compute)
+        yo = ops.mlp_act_layout(n, net.genc_dims, net.genc_acts)[1][-1]
+        return torch.cat([e_obs, gact[yo: yo + n * net.G].view(n, net.G)], dim=-1)
+
+    def forward(self, obs, action):
+        """critic.py:92-97 on [embedding | action].  Images (n,3,H,W) or (3,H,W), an embedding (n,E) or (E,), actions (n,A)
+        or (A,); one observation row is shared by all action rows (the reference's expand_obs).  Returns (n, 1)."""
+        o, net = self.owner, self.net
+        s = self.emb_representation(obs)
+        s = s.unsqueeze(0) if s.dim() == 1 else s
+        a = action.to(o.dev, torch.float32)
+        a = a.unsqueeze(0) if a.dim() == 1 else a
+        if s.shape[1] != self.E or a.shape[1] != self.A:
+            raise ValueError(f"critic takes an embedding of {self.E} and an action of {self.A} columns, got {s.shape[1]} and "
+                             f"{a.shape[1]}")
+        n = a.shape[0]
+        if s.shape[0] not in (1, n):
+            raise ValueError(f"{s.shape[0]} observation rows for {n} action rows")
+        ldx = (self.E + self.A + 3) // 4 * 4
+        x = torch.zeros(n, ldx, device=o.dev)
+        x[:, :self.E] = s
+        x[:, self.E: self.E + self.A] = a
+        qact = torch.zeros(ops.mlp_act_layout(n, net.head_dims, net.head_acts)[2], device=o.dev)
+        ops.mlp_fwd([x], ldx, [net.head()], [qact], [n], net.head_dims, net.head_acts, o.compute)
+        yo = ops.mlp_act_layout(n, net.head_dims, net.head_acts)[1][-1]
+        return qact[yo: yo + n].view(n, 1).clone()
+
+    __call__ = forward
+
+
 def attach_rollout_surface(module, actor_net, cams, goal_cams, action_dim, discrete_gripper, lmp_net=None, lmp_cams=None,
-                           ad=None):
-    """Give the module's reference-named containers their rollout methods."""
+                           ad=None, critics=None):
+    """Give the module's reference-named containers their rollout methods.  critics: {container name: network block}."""
+    if critics:
+        runner = EncoderRunner(module)
+        for name, net in critics.items():
+            cs = CriticSurface(module, net, cams, goal_cams, action_dim, runner)
+            box = getattr(module, name)
+            box.forward = cs.forward  # nn.Module.__call__ finds the instance attribute: module.q1(obs, action)
+            box.get_emb_representation = cs.emb_representation
+            box.get_emb_obs_representation = cs.emb_obs_representation
+            box.__dict__["critic_surface"] = cs
     surf = ActorSurface(module, actor_net, cams, goal_cams, action_dim, discrete_gripper)
     module.__dict__["_actor_surface"] = surf
     module.actor.get_actions = surf.get_actions

@@ -410,6 +410,23 @@ def tanh_normal_sample(head, ld_head, eps, gumbel_u, hard, act_out, act_off, ld_
          ld_act, ptr(logp), ptr(grip_idx), n, M, Ac, stream())
 
 
+def cem_supported(N, A, E, hidden, q_layers, compute):
+    return bool(L.lib().tacorl_cem_supported(int(N), int(A), int(E), int(hidden), int(q_layers), int(compute)))
+
+
+def cem_refine(s, params, params_bf16, mean0, eps, out, N, A, E, hidden, q_layers, iters, n_elite, min_std, max_std, alpha,
+               discrete_gripper, compute, trace=None):
+    """One launch: the whole CEM refinement of out.shape[0] problem rows.  s / params / params_bf16: per net (1 = that net's
+    Q, 2 = the twin minimum); trace: None or (population, Q, elite indices int32, mean, std) tensors to fill."""
+    R = out.shape[0]
+    nb = L.lib().tacorl_cem_ws_bytes(R, N, A, E, hidden, q_layers, compute)
+    ws = workspace(nb, out.device, "cem")
+    call("tacorl_cem_refine", R, len(s), ptr_array([_f32(t) for t in s]), ptr_array(params),
+         ptr_array(params_bf16) if params_bf16 is not None else None, ptr(mean0), ptr(_f32(eps)), ptr(_f32(out)), N, A, E,
+         hidden, q_layers, iters, n_elite, float(min_std), float(max_std), float(alpha), int(bool(discrete_gripper)), compute,
+         *([ptr(t) for t in trace] if trace is not None else [None] * 5), ptr(ws), ws.numel(), stream())
+
+
 def adam_step_batch(items, mirrors=None):
     """items: list of (param, grad, m, v, lr, max_norm, step_counter, target_or_None, tau) - one
     norm (+ step counter) launch and one update launch for all of them.
