@@ -111,9 +111,17 @@ class ACEngine:
                  conservative_weight=1.0, lagrange_thresh=5.0, temp=1.0, with_lagrange=False,
                  discrete_gripper=False, target_entropy=-7.0, policy_layers=3, q_layers=3, hidden=256,
                  compute=F32, img_dtype=torch.float32, world_size=1):
-        if sorted(cams) != sorted(goal_cams):
-            raise NotImplementedError("observation and goal modalities must coincide (all in-scope configs)")
+        if not cams or not goal_cams:
+            raise NotImplementedError("observation and goal modalities must both be non-empty (the reference's no-goal "
+                                      "branch is not built)")
+        if len(set(cams)) != len(cams) or len(set(goal_cams)) != len(goal_cams):
+            raise ValueError(f"a modality is listed twice: obs {list(cams)}, goal {list(goal_cams)}")
         self.cams, self.hw, self.B, self.n, self.A = list(cams), dict(hw or {}), B, n, action_dim
+        # Two ordered camera lists (reference visual_actor_wrapper.py:41-62): the state embedding is the cameras of `cams`
+        # in list order, the goal encoder's input the cameras of `goal_cams` in list order; every network owns an encoder
+        # per camera of the union.  enc_cams: every camera the step encodes (the observation cameras first).
+        self.goal_cams = list(goal_cams)
+        self.enc_cams = self.cams + [c for c in self.goal_cams if c not in self.cams]
         self.dev, self.compute, self.img_dtype = device, compute, img_dtype
         self.dg = bool(discrete_gripper)
         self.Ac = action_dim - 1 if self.dg else action_dim
@@ -125,8 +133,7 @@ class ACEngine:
         self.with_lagrange = with_lagrange
         self.world = world_size
         self.hidden = hidden
-        nc = len(self.cams)
-        self.Eo = self.G = 32 * nc
+        self.Eo, self.G = 32 * len(self.cams), 32 * len(self.goal_cams)
         self.E = self.Eo + self.G
         self.ldq = _al4(self.E + action_dim)
         self.lds = self.E
@@ -190,14 +197,36 @@ class ACEngine:
         B, n, dev = self.B, self.n, self.dev
         ops.note_alloc()
         f = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
-        self.X3 = {c: torch.zeros(3 * B, *self.hw[c], 3, device=dev, dtype=self.img_dtype) for c in self.cams}
-        # encoder problems: (net, first image row in X3, n images, keep activations for backward)
-        self.enc_probs = [("a_og", self.actor, 0, 2 * B), ("a_nx", self.actor, 2 * B, B), ("q1", self.q1, 0, 2 * B),
-                          ("q2", self.q2, 0, 2 * B), ("tq1", self.tq1, B, 2 * B), ("tq2", self.tq2, B, 2 * B)]
-        self.enc_out = {(k, c): f(nimg, 32) for k, _, _, nimg in self.enc_probs for c in self.cams}
-        self.enc_act = {(k, c): f(ops.encoder_act_layout(nimg, *self.hw[c])[1])
-                        for k, _, _, nimg in self.enc_probs for c in self.cams}
-        self.enc_dout = {(k, c): f(2 * B, 32) for k in ("a_og", "q1", "q2") for c in self.cams}
+        # Image slots of a camera, in units of B images: [obs | goal | next] for a camera in both roles, [obs | next] for an
+        # observation-only camera, [goal] for a goal-only one (images that no role uses are neither packed nor encoded).
+        self.slot, self.cam_probs, self.erow, self.nbwd = {}, {}, {}, {}
+        for c in self.enc_cams:
+            names = [s_ for s_, used in (("obs", c in self.cams), ("goal", c in self.goal_cams), ("next", c in self.cams)) if used]
+            sl = self.slot[c] = {s_: i for i, s_ in enumerate(names)}
+            # encoder problems (key, net, first image row in X3, n images): each a run of adjacent slots.  Both roles:
+            # actor(obs, goal), actor(next), q1 / q2 (obs, goal), targets (goal, next) = 11*B images; observation only:
+            # actor(obs), actor(next), q1 / q2 (obs), targets (next) = 6*B; goal only: five networks (goal) = 5*B.
+            want = [("a_og", self.actor, ("obs", "goal")), ("a_nx", self.actor, ("next",)), ("q1", self.q1, ("obs", "goal")),
+                    ("q2", self.q2, ("obs", "goal")), ("tq1", self.tq1, ("goal", "next")), ("tq2", self.tq2, ("goal", "next"))]
+            pr = []
+            for k, net, roles in want:
+                have = [s_ for s_ in roles if s_ in sl]
+                if not have:
+                    continue
+                r0 = sl[have[0]]
+                assert [sl[s_] for s_ in have] == list(range(r0, r0 + len(have)))
+                pr.append((k, net, r0 * B, len(have) * B))
+                self.erow[(k, c)] = {s_: (sl[s_] - r0) * B for s_ in have}  # first enc_out row of each role's images
+            self.cam_probs[c] = pr
+            self.nbwd[c] = (("obs" in sl) + ("goal" in sl)) * B  # images of a problem that has a backward (GRAD_PROBS)
+        self.X3 = {c: torch.zeros(len(self.slot[c]) * B, *self.hw[c], 3, device=dev, dtype=self.img_dtype) for c in self.enc_cams}
+        # (the first camera's table - every camera's when the two lists name the same cameras)
+        self.enc_probs = self.cam_probs[self.enc_cams[0]]
+        nimg = {(k, c): n_ for c in self.enc_cams for k, _, _, n_ in self.cam_probs[c]}
+        keys = [kc for k in ("a_og", "a_nx", "q1", "q2", "tq1", "tq2") for c in self.enc_cams if (kc := (k, c)) in nimg]
+        self.enc_out = {kc: f(nimg[kc], 32) for kc in keys}
+        self.enc_act = {kc: f(ops.encoder_act_layout(nimg[kc], *self.hw[kc[1]])[1]) for kc in keys}
+        self.enc_dout = {(k, c): f(self.nbwd[c], 32) for k in ("a_og", "q1", "q2") for c in self.enc_cams}
         nets = [("a", self.actor), ("q1", self.q1), ("q2", self.q2), ("tq1", self.tq1), ("tq2", self.tq2)]
         self.nets = nets
         self.gin = {k: f(B, self.G) for k, _ in nets}
@@ -275,15 +304,17 @@ class ACEngine:
 
     def load_images(self, cam, obs, goal, nxt, nchw=True):
         """obs/goal/nxt: (B,3,H,W) [nchw] or (B,H,W,3) fp32 device tensors (may be strided views with a
-        uniform image pitch, e.g. states[:,0])."""
+        uniform image pitch, e.g. states[:,0]); the images of a role the camera does not have are not read (None)."""
         H, W = self.hw[cam]
         xd = BF16 if self.img_dtype == torch.bfloat16 else F32
         esz, img = self.X3[cam].element_size(), H * W * 3
         jobs = []
-        if obs.dtype == torch.uint8:
+        given = {"obs": obs, "goal": goal, "next": nxt}
+        srcs = [(i, given[s_]) for s_, i in self.slot[cam].items()]  # (slot, images)
+        if srcs[0][1].dtype == torch.uint8:
             # the dataset's uint8 HWC frames: ToTensor + Normalize(0.5, 0.5) applied by the pack (bit-identical to the
             # host-transformed fp32 route, a quarter of the bytes)
-            for i, t in enumerate((obs, goal, nxt)):
+            for i, t in srcs:
                 assert t.is_cuda and t.dtype == torch.uint8 and t[0].is_contiguous() and tuple(t.shape[-3:]) == (H, W, 3)
                 pitch = t.stride(0) if t.shape[0] > 1 else img
                 jobs.append((t.data_ptr(), pitch, self.X3[cam].data_ptr() + i * self.B * img * esz, self.B))
@@ -291,7 +322,7 @@ class ACEngine:
                 raise ValueError("uint8 frames: H*W*3 and the image pitch must be multiples of 16, tensors 16-byte aligned")
             ops.pack_images_u8_batch(jobs, xd, H, W)
             return
-        for i, t in enumerate((obs, goal, nxt)):
+        for i, t in srcs:
             assert t.is_cuda and t.dtype == torch.float32 and t[0].is_contiguous()
             pitch = t.stride(0) if t.shape[0] > 1 else 3 * H * W
             jobs.append((t.data_ptr(), pitch, self.X3[cam].data_ptr() + i * self.B * img * esz, self.B))
@@ -334,7 +365,7 @@ class ACEngine:
         """The per-image LDS-resident conv backward may exist for fewer geometries than the fused forward; where it does
         not, the problems that have a backward take the per-layer forward (fp32 activations)."""
         return self._fused_ok(c) and ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(
-            3, ops.int_array([2 * self.B] * 3), *self.hw[c]) > 0
+            3, ops.int_array([self.nbwd[c]] * 3), *self.hw[c]) > 0
 
     def _packed(self, net, c):
         key = (id(net), c)
@@ -348,7 +379,7 @@ class ACEngine:
         (which = "own": the update's networks only, "extra": the caller's frozen ones only - TACORL's LMP window)."""
         pr = [] if which == "extra" else [
             (self._img_ptr(c, r0), net, self.enc_out[(k, c)], self.enc_act[(k, c)], n, k in self.GRAD_PROBS, c)
-            for k, net, r0, n in self.enc_probs]
+            for k, net, r0, n in self.cam_probs[c]]
         if which != "own":
             pr += [(x["img"], x["net"], x["out"], x["act"], x["n"], False, c) for x in self.extra_enc if x["cam"] == c]
         return pr
@@ -359,7 +390,7 @@ class ACEngine:
         caller forks that branch there), then the update's own problems on TACORL_EF_SPLIT_BUDGET workgroups (default 160:
         96 CUs stay free for the branch; sweep 96 .. 240 on C4 / C3: 128 - 160 best).  Returns False when the split does not apply (nothing launched)."""
         groups = self._fused_groups()
-        if not self.extra_enc or len(groups) != 1 or sorted(groups[0]) != sorted(self.cams) or not all(self._fused_bwd_ok(c) for c in self.cams):
+        if not self.extra_enc or len(groups) != 1 or sorted(groups[0]) != sorted(self.enc_cams) or not all(self._fused_bwd_ok(c) for c in self.enc_cams):
             return False
         cs = groups[0]
         for which in ("extra", "own"):
@@ -403,14 +434,14 @@ class ACEngine:
         nets = {id(n_): n_ for n_ in self._late_pack_nets()}
         nets.update({id(x["net"]): x["net"] for x in self.extra_enc})
         return any(self._wpk_ver.get((i, c), n_.param._version) != n_.param._version
-                   for i, n_ in nets.items() for c in self.cams if (i, c) in self._wpk_ver)
+                   for i, n_ in nets.items() for c in self.enc_cams if (i, c) in self._wpk_ver)
 
     def packs_written(self):
         """The step's tail launch (eager, or the replayed graph's) has just re-packed the optimiser's networks: record it."""
         vers = getattr(self, "_wpk_ver", None)
         if self.ef_pack_late and vers:
             for n_ in self._late_pack_nets():
-                for c in self.cams:
+                for c in self.enc_cams:
                     if (id(n_), c) in vers:
                         vers[(id(n_), c)] = n_.param._version
 
@@ -428,7 +459,7 @@ class ACEngine:
         launch's table (round 5; C4: two 128 x 128 cameras, 7 problems each - one launch over 5 504 images instead of two over
         2 752: one prologue, one tail); every other fused camera alone.  TACORL_EF_MERGE_CAMS=0: one launch per camera."""
         groups, out = {}, []
-        for c in self.cams:
+        for c in self.enc_cams:
             if self._fused_ok(c):
                 groups.setdefault((tuple(self.hw[c]), bool(self._fused_bwd_ok(c))), []).append(c)
         for (_, bwd_ok), cs in groups.items():
@@ -454,7 +485,7 @@ class ACEngine:
         problems that have a backward; the per-layer path covers fp32 mode / images too large for LDS."""
         xd = BF16 if self.img_dtype == torch.bfloat16 else F32
         merged = {c: cs for cs in self._fused_groups() if len(cs) > 1 for c in cs}
-        for c in self.cams:
+        for c in self.enc_cams:
             H, W = self.hw[c]
             pr = self._all_problems(c)
             if c in merged:
@@ -556,7 +587,7 @@ class ACEngine:
                 if self._fused_bwd_ok(c):
                     H, W = self.hw[c]
                     np_ = 3 * len(cs)
-                    n3 = ops.int_array([2 * self.B] * np_)
+                    n3 = ops.int_array([self.nbwd[cc] for cc in cs for _ in nets])
                     nb = ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(np_, n3, H, W)
                     ws = ops.workspace(nb, self.dev, "enc_bwd_fused_" + "+".join(cs))
                     call("tacorl_encoder_bwd_fused_pack", np_, ops.ptr_array([x.enc(cc) for cc in cs for x in nets]), n3, H, W, ptr(ws),
@@ -588,31 +619,37 @@ class ACEngine:
                 M, net[0], net[1], ldx, self.compute, self._lean(tag))
         return cache[key]
 
-    def _emb_segs(self, ek, row0, gk, mod=0):
-        """[enc(obs or next) per camera | goal_enc(enc(goal))] as input segments."""
-        segs = [(self.enc_out[(ek, c)], row0 * 32, 32, 32 * j, mod) for j, c in enumerate(self.cams)]
+    def _emb_segs(self, ek, role, gk, mod=0):
+        """[enc(obs or next) per observation camera | goal_enc(enc(goal))] as input segments."""
+        segs = [(self.enc_out[(ek, c)], self.erow[(ek, c)][role] * 32, 32, 32 * j, mod) for j, c in enumerate(self.cams)]
         segs.append((self.gact[gk], self.g_yoff, self.G, self.Eo, mod))
         return segs
 
-    _OBS_SRC = {"a": ("a_og", 0, "a"), "a_nx": ("a_nx", 0, "a"), "q1": ("q1", 0, "q1"), "q2": ("q2", 0, "q2"),
-                "tq1": ("tq1", 1, "tq1"), "tq2": ("tq2", 1, "tq2")}  # (encoder problem, first row / B, goal-encoder net)
+    def _goal_rows(self, ek, c):
+        """First float of camera c's goal embeddings in the encoder problem ek's output."""
+        return self.erow[(ek, c)]["goal"] * 32
+
+    # (encoder problem, role of the state images, goal-encoder net)
+    _OBS_SRC = {"a": ("a_og", "obs", "a"), "a_nx": ("a_nx", "next", "a"), "q1": ("q1", "obs", "q1"), "q2": ("q2", "obs", "q2"),
+                "tq1": ("tq1", "next", "tq1"), "tq2": ("tq2", "next", "tq2")}
 
     def _assemble_states(self):
         B = self.B
-        # goal-encoder inputs: concat over cams of enc(goal)
-        src = {"a": ("a_og", B), "q1": ("q1", B), "q2": ("q2", B), "tq1": ("tq1", 0), "tq2": ("tq2", 0)}
+        # goal-encoder inputs: concat over the goal cameras of enc(goal)
+        src = {"a": "a_og", "q1": "q1", "q2": "q2", "tq1": "tq1", "tq2": "tq2"}
         nets = dict(self.nets)
         ks = ["a", "q1", "q2", "tq1", "tq2"]
         if self._gather_ok("genc"):
-            segs = [[(self.enc_out[(src[k][0], c)], src[k][1] * 32, 32, 32 * j, 0) for j, c in enumerate(self.cams)] for k in ks]
+            segs = [[(self.enc_out[(src[k], c)], self._goal_rows(src[k], c), 32, 32 * j, 0) for j, c in enumerate(self.goal_cams)]
+                    for k in ks]
             ops.mlp_fwd_gather(segs, [self.gin[k] for k in ks], self.G, [nets[k].genc() for k in ks],
                                [nets[k].genc_bf16() for k in ks], [self.gact[k] for k in ks], [B] * 5, self.actor.genc_dims,
                                self.actor.genc_acts, lean=self._lean("genc"))
         else:
             with ops.copy_batch():
-                for k, (ek, row0) in src.items():
-                    for j, c in enumerate(self.cams):
-                        ops.copy_cols(self.enc_out[(ek, c)], row0 * 32, 32, self.gin[k], 32 * j, self.G, B, 32)
+                for k, ek in src.items():
+                    for j, c in enumerate(self.goal_cams):
+                        ops.copy_cols(self.enc_out[(ek, c)], self._goal_rows(ek, c), 32, self.gin[k], 32 * j, self.G, B, 32)
             ops.mlp_fwd([self.gin[k] for k in ks], self.G, [nets[k].genc() for k in ks], [self.gact[k] for k in ks],
                         [B] * 5, self.actor.genc_dims, self.actor.genc_acts, self.compute,
                         params_bf16=[nets[k].genc_bf16() for k in ks], lean=self._lean("genc"))
@@ -621,19 +658,18 @@ class ACEngine:
         if need:
             with ops.copy_batch():
                 for k in need:
-                    ek, r0, gk = self._OBS_SRC[k]
+                    ek, role, gk = self._OBS_SRC[k]
                     for j, c in enumerate(self.cams):
-                        ops.copy_cols(self.enc_out[(ek, c)], r0 * B * 32, 32, self.S[k], 32 * j, self.lds, B, 32)
+                        ops.copy_cols(self.enc_out[(ek, c)], self.erow[(ek, c)][role] * 32, 32, self.S[k], 32 * j, self.lds, B, 32)
                     ops.copy_cols(self.gact[gk], self.g_yoff, self.G, self.S[k], self.Eo, self.lds, B, self.G)
 
     def _policy_fwd(self):
         ks = ["a", "a_nx"]
         if self._gather_ok("pi"):
-            B = self.B
-            segs = [self._emb_segs(self._OBS_SRC[k][0], self._OBS_SRC[k][1] * B, self._OBS_SRC[k][2]) for k in ks]
+            segs = [self._emb_segs(*self._OBS_SRC[k]) for k in ks]
             # (S["a"] is the policy head's layer-0 operand in the backward: written from the forward's registers)
             ops.mlp_fwd_gather(segs, [self.S["a"], None], self.lds, [self.actor.head()] * 2, [self.actor.head_bf16()] * 2,
-                               [self.pact[k] for k in ks], [B] * 2, self.actor.head_dims, self.actor.head_acts,
+                               [self.pact[k] for k in ks], [self.B] * 2, self.actor.head_dims, self.actor.head_acts,
                                lean=self._lean("pi"))
             return
         ops.mlp_fwd([self.S[k] for k in ks], self.lds, [self.actor.head()] * 2, [self.pact[k] for k in ks],
@@ -730,7 +766,7 @@ class ACEngine:
             # embeddings), the actions are acts_main = [data | uniform | n x pi(obs) | n x pi(next)]; only the two
             # problems with weight gradients (q1 / q2 over all R rows) also write their assembled rows
             E = self.E
-            seg = lambda k, mod, a_t: self._emb_segs(self._OBS_SRC[k][0], self._OBS_SRC[k][1] * B, self._OBS_SRC[k][2], mod) + [(a_t, 0, A, E, 0)]  # noqa: E731
+            seg = lambda k, mod, a_t: self._emb_segs(*self._OBS_SRC[k], mod) + [(a_t, 0, A, E, 0)]  # noqa: E731
             segs = [seg("q1", B, self.acts_main), seg("q2", B, self.acts_main), seg("q1", 0, self.act_pi), seg("q2", 0, self.act_pi),
                     seg("tq1", 0, self.act_next), seg("tq2", 0, self.act_next)]
             ops.mlp_fwd_gather(segs, [self.XQ["q1"], self.XQ["q2"], None, None, None, None], self.ldq, ps, pb, ac,
@@ -861,7 +897,7 @@ class ACEngine:
         """Camera groups that share one conv-backward launch sequence: the cameras of one (fused-backward) geometry, at
         most 8 problems (3 networks per camera); everything else one camera at a time."""
         groups = {}
-        for c in self.cams:
+        for c in self.enc_cams:
             groups.setdefault((tuple(self.hw[c]), bool(self._fused_bwd_ok(c))), []).append(c)
         merge = os.environ.get("TACORL_EBW_MERGE_CAMS", "1") == "1"
         seqs = []
@@ -883,17 +919,23 @@ class ACEngine:
                            self.actor.genc_dims, self.actor.genc_acts)
         ek = {"a": "a_og", "q1": "q1", "q2": "q2"}
         with ops.copy_batch():
-            for j, c in enumerate(self.cams):
+            # an observation camera's columns of dS are its index in `cams`, a goal camera's columns of dgin its index in
+            # `goal_cams`; a camera in both roles gets both (its weight gradients sum over the 2*B images)
+            for c in self.enc_cams:
                 for k in ks:
-                    ops.copy_cols(self.dS[k], 32 * j, self.lds, self.enc_dout[(ek[k], c)], 0, 32, B, 32)
-                    ops.copy_cols(self.dgin[k], 32 * j, self.G, self.enc_dout[(ek[k], c)], B * 32, 32, B, 32)
+                    rows = self.erow[(ek[k], c)]
+                    if "obs" in rows:
+                        ops.copy_cols(self.dS[k], 32 * self.cams.index(c), self.lds, self.enc_dout[(ek[k], c)], rows["obs"] * 32, 32, B, 32)
+                    if "goal" in rows:
+                        ops.copy_cols(self.dgin[k], 32 * self.goal_cams.index(c), self.G, self.enc_dout[(ek[k], c)], rows["goal"] * 32,
+                                      32, B, 32)
         # cameras of one geometry share a launch sequence (round 5; C4: both cameras 128 x 128 -> one 6-problem sequence
         # instead of two 3-problem ones - the conv-backward launches cost ~6-10 us each before their first image)
         for cs in self._ebw_sequences():
             c = cs[0]
             H, W = self.hw[c]
             imgs = [self._img_ptr(cc, 0) for cc in cs for _ in ks]
-            ops_n = [2 * B] * (3 * len(cs))
+            ops_n = [self.nbwd[cc] for cc in cs for _ in ks]
             pa = [ops.ptr_array(imgs), ops.ptr_array([nets[k].enc(cc) for cc in cs for k in ks]),
                   ops.ptr_array([self.enc_act[(ek[k], cc)] for cc in cs for k in ks]),
                   ops.ptr_array([self.enc_dout[(ek[k], cc)] for cc in cs for k in ks]),
@@ -913,6 +955,7 @@ class ACEngine:
                 call("tacorl_encoder_bwd_fused_fc_wgrad", np_, act_p, dout_p, grad_p, n_p, H, W, 0, ptr(ws), ws.numel(),
                      ops.stream())
                 continue
+            assert len(cs) == 1
             nb = ops.L.lib().tacorl_encoder_bwd_ws_bytes(3, ops.int_array(ops_n), H, W)
             ws = ops.workspace(nb, self.dev, "enc_bwd")
             call("tacorl_encoder_bwd", 3, ops.ptr_array(imgs), ops.ptr_array([nets[k].enc(c) for k in ks]),
@@ -938,7 +981,7 @@ class ACEngine:
             if write:  # (this launch rewrote every mirror from the updated parameters, whatever state they were in)
                 self.mirrors_written()
             if self.ef_pack_late:
-                for c in self.cams:
+                for c in self.enc_cams:
                     if self._fused_ok(c):
                         self._pack_encoders(c, self._late_pack_nets())
         ops.mark("c:adam")

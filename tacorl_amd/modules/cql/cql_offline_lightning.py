@@ -82,8 +82,12 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         a = self._arch()
         if a["hidden"] != (self.critic_cfg or {}).get("q_network", {}).get("hidden_dim", 256):
             raise NotImplementedError("actor and critic hidden sizes must match")
-        cfgcheck.check_representation(self.actor_encoder_cfg, "actor_encoder", self.obs_modalities)
-        cfgcheck.check_representation(self.critic_encoder_cfg, "critic_encoder", self.obs_modalities)
+        if not self.goal_modalities:
+            raise NotImplementedError("goal_modalities is empty: the reference's no-goal branch is not built")
+        # every network owns one encoder per camera of the union of the two lists (reference :149-227)
+        union = self.obs_modalities + [c for c in self.goal_modalities if c not in self.obs_modalities]
+        cfgcheck.check_representation(self.actor_encoder_cfg, "actor_encoder", union)
+        cfgcheck.check_representation(self.critic_encoder_cfg, "critic_encoder", union)
         cfgcheck.check_goal_encoder(self.goal_encoder_cfg, "goal_encoder", a["hidden"])
         self._make_engine(self.obs_modalities, self.goal_modalities, self.action_dim, a)
         # fresh networks start from the reference modules' torch initialisers (tacorl_amd/init.py); targets are
@@ -182,17 +186,21 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         return obs, batch["actions"].float(), nxt, batch["rewards"].float(), batch["terminals"].int()
 
     def _stage(self, obs, goal, nxt, action, reward, done, noise, nchw=True):
+        """Observation and next-observation images are read for the cameras of obs_modalities only, goal images for the
+        cameras of goal_modalities only (reference visual_actor_wrapper.py:41-62): whatever else the batch carries is
+        ignored, and images of a role a camera does not have need not be there."""
         e = self.engine
         B = action.shape[0]
         hw = {}
         if obs[e.cams[0]].dtype == torch.uint8:  # the dataset's uint8 HWC frames: normalised on the GPU (engine.load_images)
             nchw = False
-        for c in e.cams:
-            t = obs[c]
+        for c in e.enc_cams:
+            t = obs[c] if c in e.cams else goal[c]
             hw[c] = tuple(t.shape[-2:]) if nchw else tuple(t.shape[-3:-1])
         e.ensure_batch(B, hw)
-        for c in e.cams:
-            e.load_images(c, obs[c].to(self.dev), goal[c].to(self.dev), nxt[c].to(self.dev), nchw=nchw)
+        for c in e.enc_cams:
+            o, g, nx = (obs[c] if c in e.cams else None, goal[c] if c in e.goal_cams else None, nxt[c] if c in e.cams else None)
+            e.load_images(c, *(None if t is None else t.to(self.dev) for t in (o, g, nx)), nchw=nchw)
         e.load_transition(action.to(self.dev), reward.to(self.dev), done.to(self.dev))
         e.set_noise(noise)
 
