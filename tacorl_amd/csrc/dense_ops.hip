@@ -407,8 +407,8 @@ static int k_wgrad(LA& la, int nprob, const float* const* dz, int ld_dz, const i
   CHECK((gemm_launch<LA, RowMajorLoader, true, true, WgradStore>(la, lb, ep, g, cd, st)));
   // up to 1024 workgroups (256 before: the 24-slab sums ran as 4 waves per CU, latency-bound).  PlayLMP, two processes per
   // setting on one box: B = 32 1.195 -> 1.174 ms/step at 1024 (1.172 at 4096), B = 256 2.10 / 2.12 / 2.13 at 256 / 1024 / 4096
-  // (process noise +-1 %: wider crowds the step's other branches there) - round 5.  TACORL_SLAB_REDUCE_WGS overrides.
-  static const int cap = [] { const char* e = getenv("TACORL_SLAB_REDUCE_WGS"); return e && atoi(e) > 0 ? atoi(e) : 1024; }();
+  // (process noise +-1 %: wider crowds the step's other branches there) - round 5.
+  constexpr int cap = 1024;
   dim3 grid(cdiv(per, 256) > cap ? cap : cdiv(per, 256), nprob);
   hipLaunchKernelGGL(slab_reduce_kernel_tbl, grid, dim3(256), 0, st, t, ns, O, K, accumulate);
   return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;

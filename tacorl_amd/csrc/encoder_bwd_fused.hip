@@ -1046,11 +1046,11 @@ int run(int nprob, const EbwProblem* pr, int accumulate, void* ws, size_t ws_byt
   }
   d3.wpp = d2.wpp = g3.wpp = g2.wpp = g1.wpp = w.wpp;
   // the dgrads need < 40 KB of LDS and ~70 registers: two of their workgroups fit on a CU and hide each other's global
-  // latency (a workgroup's image loop waits for the next image's loads every iteration).  TACORL_EBW_DG2=0: one per CU
-  static const int dg2 = [] { const char* e = getenv("TACORL_EBW_DG2"); return e ? atoi(e) : 2; }();
+  // latency (a workgroup's image loop waits for the next image's loads every iteration)
+  constexpr int dg2 = 2;
   long maxn = 1;
   for (int p = 0; p < nprob; p++) maxn = n[p] > maxn ? n[p] : maxn;
-  auto per_cu = [&](size_t lds) { return dg2 > 1 && (size_t)dg2 * lds <= 160 * 1024 ? dg2 : 1; };  // 128 x 128: one
+  auto per_cu = [](size_t lds) { return (size_t)dg2 * lds <= 160 * 1024 ? dg2 : 1; };  // 128 x 128: one
   const int k3w = per_cu(dgrad_lds_bytes<L3>()), k2w = per_cu(dgrad_lds_bytes<L2>());
   d3.wpp = (int)((long)k3w * w.wpp < maxn ? (long)k3w * w.wpp : maxn);
   d2.wpp = (int)((long)k2w * w.wpp < maxn ? (long)k2w * w.wpp : maxn);

@@ -56,7 +56,7 @@ int mlp_fused_wgrad(int nprob, const float* const* x, int ldx, const float* cons
                     const int* acts = nullptr);
 // yoff[...] < 0 (forward: do not save that layer's output; wgrad: -(zoff + 1), recompute it from the pre-activation with acts[l])
 
-// ---- many-row problems (>= TACORL_MLP_BIG_ROWS = 16384 rows: C5's Q networks, 99 328): kernels of their own.  Eligible:
+// ---- many-row problems (>= MLP_BIG_ROWS = 2048 rows, mlp_fused.hip; C5's Q networks: 99 328): kernels of their own.  Eligible:
 // L >= 2, hidden widths 256 with SiLU, dims[0] <= 128, dims[L] <= 4.  A hidden layer l saves, instead of fp32 z / y:
 //   ybf[p*MF_MAXL + l]: bf16 [Mp][256] copy of its output (the next layer's MFMA operand and the weight gradients' x operand),
 //   sbf[p*MF_MAXL + l]: fp16 [Mp][256] copy of act'(z)   (Mp = M rounded up to 64; float offsets into act[p]);

@@ -737,7 +737,7 @@ struct MlpBigFwdArgs {
   long woff[MF_MAXL], boff[MF_MAXL];
   int dims[MF_MAXL + 1], acts[MF_MAXL];
   int L, ldx;
-  int dbg;  // scratch experiments of the persistent kernel (TACORL_MLP_PERS_DBG; 0 in production): 1 = no copy-out stores
+  int dbg;  // read only by -DMLP_PERS_DBG scratch builds of the persistent kernel (set by hand there); always 0 otherwise
 };
 
 // BMF_ rows per workgroup: 128 for >= 16 384 rows (C5), 32 for the thousands of rows of the other configurations' Q
@@ -940,7 +940,6 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
 }
 __global__ __launch_bounds__(MF_NT) void mlp_big_fwd_kernel(MlpBigFwdArgs a) { mlp_big_fwd_body<128>(a); }
 __global__ __launch_bounds__(MF_NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void mlp_mid_fwd_kernel(MlpBigFwdArgs a) { mlp_big_fwd_body<32>(a); }
-__global__ __launch_bounds__(MF_NT) __attribute__((amdgpu_waves_per_eu(5, 8))) void mlp_m64_fwd_kernel(MlpBigFwdArgs a) { mlp_big_fwd_body<64>(a); }
 
 // ---- persistent many-row forward (round 5).  The kernels above re-stream every layer's weights through the CU's L2 port for
 // each row block (300 KB per 128 rows, ~10 k clk at the ~29 B/clk a CU ingests), start every block with a prologue behind
@@ -1924,14 +1923,10 @@ int mlp_fused_wgrad(int nprob, const float* const* x, int ldx, const float* cons
 }
 
 // ---- many-row weight gradients (mlp_wgrad_big_kernel): eligibility, sizes, launch
-static int mlp_big_rows() {
-  // 2048 since round 5 (16384 before): below 16 384 rows the same saves come from 32-row workgroups (mlp_mid_*_kernel)
-  static const int v = [] { const char* e = getenv("TACORL_MLP_BIG_ROWS"); return e ? atoi(e) : 2048; }();
-  return v;
-}
+// 2048 since round 5 (16384 before): below 16 384 rows the same saves come from 32-row workgroups (mlp_mid_*_kernel)
+constexpr int MLP_BIG_ROWS = 2048;
 bool mlp_big_prob_ok(int M, int L, const int* dims, const int* acts) {
-  static const int on = [] { const char* e = getenv("TACORL_MLP_BIG"); return e ? atoi(e) : 1; }();  // A/B switch
-  if (!on || L < 2 || L > MF_MAXL || M < mlp_big_rows()) return false;
+  if (L < 2 || L > MF_MAXL || M < MLP_BIG_ROWS) return false;
   if (dims[0] < 8 || dims[0] > 128 || dims[L] < 1 || dims[L] > 4) return false;
   for (int l = 1; l < L; l++)
     if (dims[l] != 256) return false;
@@ -1949,10 +1944,6 @@ extern "C" int tacorl_dbg_mlp_stamps(unsigned long long* dst) {
 #endif
 // rows per workgroup of the many-row forward / input-gradient kernels: 128 / 64 at >= 16 384 rows, 32 / 32 below
 static bool mlp_rows_huge(int maxM) { return maxM >= 16384; }
-// experiment switches (rows per workgroup of the many-row forward / chain at >= 16 384 rows: 128 / 64 by default)
-static int mlp_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static int mlp_huge_fwd_rows() { static const int v = mlp_env_int("TACORL_MLP_HUGE_FWD_ROWS", 128); return v; }
-static int mlp_huge_bwd_rows() { static const int v = mlp_env_int("TACORL_MLP_HUGE_BWD_ROWS", 64); return v; }
 template <class Args>
 static int mlp_set_gather(Args& a, int p, int q, const MlpXGather* gather, int K0) {  // gather's problem q -> args' problem p
   const int ns = gather ? gather->nseg[q] : 0;
@@ -1988,32 +1979,27 @@ int mlp_big_fwd(int nprob, const float* const* x, int ldx, const float* const* p
   }
   a.dims[L] = dims[L]; a.L = L; a.ldx = ldx;
   if (maxM == 0) return TACORL_OK;
-  constexpr size_t lds = (size_t)2 * 128 * XP * 2, lds_mid = (size_t)2 * 32 * XP * 2, lds_64 = (size_t)2 * 64 * XP * 2;
+  constexpr size_t lds = (size_t)2 * 128 * XP * 2, lds_mid = (size_t)2 * 32 * XP * 2;
   static int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_big_fwd_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_m64_fwd_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_64) == hipSuccess &&
                      hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_mid_fwd_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mid) == hipSuccess) ? 0 : -1;
   if (once) return TACORL_ELAUNCH;
   const int maxMp = (maxM + 63) & ~63;  // (the blocks cover the zero rows up to a multiple of 64 too)
   {
     // tens of thousands of rows: the persistent kernel (one resident workgroup per CU, weights in registers).
-    // TACORL_MLP_PERS=0: the per-block kernels below, as before
+    // TACORL_MLP_PERS=0: the per-block kernels below (the bit-identity test's comparator)
     const char* pe = getenv("TACORL_MLP_PERS");
     bool pers = mlp_rows_huge(maxM) && (pe ? atoi(pe) : 1) && (L == 3 || L == 4) && dims[0] <= 32 * PF_K0S && dims[L] <= 4;
     for (int l = 0; l + 1 < L && pers; l++) pers = acts[l] == ACT_SILU && dims[l + 1] == 256;
     if (pers) {
-      { const char* de = getenv("TACORL_MLP_PERS_DBG"); a.dbg = de ? atoi(de) : 0; }
       static int once_p = (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_pers_fwd_kernel<1>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS) == hipSuccess &&
                            hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_pers_fwd_kernel<2>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, PF_LDS) == hipSuccess) ? 0 : -1;
       if (once_p) return TACORL_ELAUNCH;
       static const int ncu = [] { int d = 0, n = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 1) n = 256; return n; }();
-      // (TACORL_MLP_PERS_CUS: CUs the resident workgroups take together - fewer than all leaves room for another branch's launches)
-      const char* ce = getenv("TACORL_MLP_PERS_CUS");
-      int gx = (ce && atoi(ce) > 0 && atoi(ce) < ncu ? atoi(ce) : ncu) / nprob;
+      int gx = ncu / nprob;  // the resident workgroups take every CU together
       gx = gx < 1 ? 1 : gx;
       gx = gx > maxMp / PF_BM ? maxMp / PF_BM : gx;
       if (L == 3) hipLaunchKernelGGL(mlp_pers_fwd_kernel<1>, dim3(gx, nprob), dim3(PF_NT), PF_LDS, st, a);
@@ -2021,9 +2007,7 @@ int mlp_big_fwd(int nprob, const float* const* x, int ldx, const float* const* p
       return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
     }
   }
-  const int rows = mlp_rows_huge(maxM) ? mlp_huge_fwd_rows() : 32;
-  if (rows == 128) hipLaunchKernelGGL(mlp_big_fwd_kernel, dim3((maxMp + 127) / 128, nprob), dim3(MF_NT), lds, st, a);
-  else if (rows == 64) hipLaunchKernelGGL(mlp_m64_fwd_kernel, dim3(maxMp / 64, nprob), dim3(MF_NT), lds_64, st, a);
+  if (mlp_rows_huge(maxM)) hipLaunchKernelGGL(mlp_big_fwd_kernel, dim3((maxMp + 127) / 128, nprob), dim3(MF_NT), lds, st, a);
   else hipLaunchKernelGGL(mlp_mid_fwd_kernel, dim3(maxMp / 32, nprob), dim3(MF_NT), lds_mid, st, a);
   return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
 }
@@ -2053,7 +2037,7 @@ int mlp_big_bwd(int nprob, const float* const* act, const float* const* d_out, i
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mid) == hipSuccess) ? 0 : -1;
   if (once) return TACORL_ELAUNCH;
   {
-    const char* pe = getenv("TACORL_MLP_PERS_BWD");  // (=0: the per-block kernels below, as before)
+    const char* pe = getenv("TACORL_MLP_PERS_BWD");  // (=0: the per-block kernels below, the bit-identity test's comparator)
     bool pers = mlp_rows_huge(maxM) && (pe ? atoi(pe) : 1) && (L == 3 || L == 4) && dims[0] <= 96 && dims[L] <= 4;
     for (int l = 1; l < L && pers; l++) pers = dims[l] == 256;
     for (int p = 0; p < nprob && pers; p++) pers = !(d_x && d_x[p] && ((uintptr_t)d_x[p] & 15));
@@ -2065,8 +2049,7 @@ int mlp_big_bwd(int nprob, const float* const* act, const float* const* d_out, i
       if (once_p) return TACORL_ELAUNCH;
       static const int ncu = [] { int d = 0, n = 0; if (hipGetDevice(&d) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n < 1) n = 256; return n; }();
       const int nb = ((maxM + 63) & ~63) / PF_BM;
-      const char* ce = getenv("TACORL_MLP_PERS_CUS");
-      int gx = (ce && atoi(ce) > 0 && atoi(ce) < ncu ? atoi(ce) : ncu) / nprob;
+      int gx = ncu / nprob;
       gx = gx < 1 ? 1 : gx;
       gx = gx > nb ? nb : gx;
       if (L == 3) hipLaunchKernelGGL(mlp_pers_bwd_kernel<1>, dim3(gx, nprob), dim3(PF_NT), PB_LDS, st, a);
@@ -2074,7 +2057,7 @@ int mlp_big_bwd(int nprob, const float* const* act, const float* const* d_out, i
       return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
     }
   }
-  if (mlp_rows_huge(maxM) && mlp_huge_bwd_rows() == 64) hipLaunchKernelGGL(mlp_big_bwd_kernel, dim3((maxM + 63) / 64, nprob), dim3(MF_NT), lds, st, a);
+  if (mlp_rows_huge(maxM)) hipLaunchKernelGGL(mlp_big_bwd_kernel, dim3((maxM + 63) / 64, nprob), dim3(MF_NT), lds, st, a);
   else hipLaunchKernelGGL(mlp_mid_bwd_kernel, dim3(((maxM + 63) & ~63) / 32, nprob), dim3(MF_NT), lds_mid, st, a);
   return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
 }
@@ -2213,7 +2196,7 @@ int mlp_fused_bwd(int nprob, const float* const* params, const float* const* act
                      hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fused_bwd_big_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big) == hipSuccess) ? 0 : -1;
   if (once) return TACORL_ELAUNCH;
-  if (maxM >= mlp_big_rows())
+  if (maxM >= MLP_BIG_ROWS)
     hipLaunchKernelGGL(mlp_fused_bwd_big_kernel, dim3((maxM + 63) / 64, nprob), dim3(MF_NT), lds_big, st, a);
   else
     hipLaunchKernelGGL(mlp_fused_bwd_kernel, dim3((maxM + BMF - 1) / BMF, nprob), dim3(MF_NT), lds, st, a);
@@ -2256,7 +2239,7 @@ int mlp_fused_fwd(int nprob, const float* const* x, int ldx, const float* const*
                      hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fused_fwd_big_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_big) == hipSuccess) ? 0 : -1;
   if (once) return TACORL_ELAUNCH;
-  if (maxM >= mlp_big_rows())
+  if (maxM >= MLP_BIG_ROWS)
     hipLaunchKernelGGL(mlp_fused_fwd_big_kernel, dim3((maxM + 127) / 128, nprob), dim3(MF_NT), lds_big, st, a);
   else
     hipLaunchKernelGGL(mlp_fused_fwd_kernel, dim3((maxM + BMF - 1) / BMF, nprob), dim3(MF_NT), lds, st, a);

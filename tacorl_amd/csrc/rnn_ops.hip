@@ -202,19 +202,17 @@ int launch_ring(const RnnArgs& a, hipStream_t st, bool plain_map = false) {
 
 }  // namespace
 
+constexpr int RNN_SMALL_UPTO = 2;  // problems per batched launch up to which the 64 x 32 tile is used (see rnn_fwd_batch)
+
 // Batched launches as 64 x 32 tiles: a 4-stage ring (96 KB of LDS, one workgroup per CU) when the whole launch is at most
 // 192 workgroups (a 256-workgroup single problem of the headline step runs beside other branches, whose kernels the 96 KB
 // keep off its CUs: +2.5 us there) - with few rows (PlayLMP at B = 32: M = 64 with the twin rows, 192 workgroups) the launch is a chain of
 // 16 L2 round trips per workgroup and three stages in flight instead of one take 12.5 -> ~9 us off each of the step's 33
 // launches (1.340 -> 1.279 ms/step, same box) - and the 2-stage ring (48 KB, three workgroups per CU) otherwise.
-// TACORL_RNN_SMALL_STAGES = 2 / 3 / 4 overrides (A/B).
 static int launch_small(const RnnBatch& ab, int nprob, hipStream_t st) {
   const RnnArgs& a = ab.p[0];
   const int MT = (a.M + a.M2 + 63) / 64, NT = a.N / 32, NTX = (NT + 7) / 8;
-  const char* e = getenv("TACORL_RNN_SMALL_STAGES");
-  const int stages = e && atoi(e) ? atoi(e) : (8 * MT * NTX * nprob <= 192 ? 4 : 2);  // (0 / unset: by the launch's size)
-  if (stages == 4) return launch_ring<64, 32, 4>(ab, nprob, st);
-  if (stages == 3) return launch_ring<64, 32, 3>(ab, nprob, st);
+  if (8 * MT * NTX * nprob <= 192) return launch_ring<64, 32, 4>(ab, nprob, st);
   return launch_ring<64, 32, 2>(ab, nprob, st);
 }
 extern "C" int tacorl_rnn_linear_supported(int M, int K, int N) {
@@ -233,11 +231,8 @@ extern "C" int tacorl_rnn_linear_fwd(const void* x_bf16, const void* w_bf16, con
   if ((long)M * N >= 256L * 64 * 128 && N % 64 == 0) return launch_ring<128, 64, 3>(a, (hipStream_t)stream);
   // Few output columns over many rows (the decoder's output heads: 3 840 x 2048 -> 192): as 64 x 32 tiles under the XCD map
   // they were 360 one-per-CU workgroups (96 KB ring) on SIX of the eight XCDs - two rounds, 35.5 us in the headline step.
-  // 64 x 64 tiles with the plain map: 180 workgroups over all XCDs, one round (round 5; TACORL_RNN_HEADS_TILE=0: as before).
-  const char* hte = getenv("TACORL_RNN_HEADS_TILE");  // (read per call: launches are captured once)
-  const int heads_tile = hte ? atoi(hte) : 1;
-  if (heads_tile == 1 && N % 64 == 0 && N / 64 < 8 && M >= 1024) return launch_ring<64, 64, 3>(a, (hipStream_t)stream, true);
-  if (heads_tile == 2 && N / 32 < 8 && M >= 1024) return launch_ring<64, 32, 4>(a, (hipStream_t)stream, true);
+  // 64 x 64 tiles with the plain map: 180 workgroups over all XCDs, one round (round 5).
+  if (N % 64 == 0 && N / 64 < 8 && M >= 1024) return launch_ring<64, 64, 3>(a, (hipStream_t)stream, true);
   return launch_ring<64, 32, 4>(a, (hipStream_t)stream);
 }
 
@@ -269,10 +264,7 @@ extern "C" int tacorl_rnn_linear_bwd_batch(int nprob, const void* const* x_bf16,
     if ((uintptr_t)yb & 7) return TACORL_EINVAL;
     ab.p[p] = RnnArgs{(const __bf16*)x_bf16[p], (const __bf16*)wt_bf16[p], nullptr, ad, ms, y[p], (__bf16*)yb, M, K, N, ld_add, ACT_NONE};
   }
-  {
-    const char* se = getenv("TACORL_RNN_SMALL_UPTO");  // (see tacorl_rnn_linear_fwd_batch)
-    if (nprob <= (se ? atoi(se) : 2) && M % 64 == 0 && N % 32 == 0) return launch_small(ab, nprob, (hipStream_t)stream);
-  }
+  if (nprob <= RNN_SMALL_UPTO && M % 64 == 0 && N % 32 == 0) return launch_small(ab, nprob, (hipStream_t)stream);
   if (M % 128 == 0 && N % 64 == 0) return launch_ring<128, 64, 2, 8>(ab, nprob, (hipStream_t)stream);
   return launch_small(ab, nprob, (hipStream_t)stream);
 }
@@ -637,23 +629,15 @@ static int rnn_fwd_batch(int nprob, const void* const* x_bf16, const void* const
   // 128 x 64 tiles, 8 waves (two per SIMD): the launch itself takes as long as with 64 x 32 tiles and 4 waves
   // (20 us for three problems; a third stage changes nothing), but it is 192 workgroups instead of 768 and the
   // step's other branches get through beside it: 1.106 -> 1.089 ms/step
-  static const int tile = [] { const char* e = getenv("TACORL_RNN_TILE"); return e ? atoi(e) : 0; }();  // A/B switch
-  if (tile == 1 && M % 128 == 0 && N % 128 == 0) return launch_ring<128, 128, 2, 8>(ab, nprob, (hipStream_t)stream);
-  if (tile == 3 && M % 64 == 0 && N % 128 == 0) return launch_ring<64, 128, 2, 4>(ab, nprob, (hipStream_t)stream);
   // the first two and the last two launches of a wavefront hold one or two problems: 64 / 128 workgroups of 128 x 64
   // tiles - a quarter / half of the chip, each streaming 768 KB; as 64 x 32 tiles they are 256 / 512 workgroups streaming
   // 384 KB each.  Same-process A/B on the headline step: small tiles for nprob <= 1 / <= 2 / <= 3: -8.5 / -16 / +14 us
-  // (three problems as 768 small workgroups crowd the step's other branches).  TACORL_RNN_SMALL_UPTO overrides.
-  const char* se = getenv("TACORL_RNN_SMALL_UPTO");
-  const int small_upto = se ? atoi(se) : 2;  // problems per launch up to which the small tile is used
-  if (nprob <= small_upto && M % 64 == 0 && N % 32 == 0) return launch_small(ab, nprob, (hipStream_t)stream);
-  {
-    // twin launches of >= 512 rows: three problems as 128 x 64 tiles are 384 workgroups of 96 KB LDS - one and a half
-    // rounds over the chip; as 128 x 128 tiles they are 192, each streaming 1 MB instead of 768 KB for twice the outputs
-    const char* tw = getenv("TACORL_RNN_TWIN_WIDE");
-    if (M2 > 0 && (tw ? atoi(tw) : 1) && nprob > 2 && M >= 512 && M % 128 == 0 && N % 128 == 0)
-      return launch_ring<128, 128, 2, 8>(ab, nprob, (hipStream_t)stream);
-  }
+  // (three problems as 768 small workgroups crowd the step's other branches): hence RNN_SMALL_UPTO = 2.
+  if (nprob <= RNN_SMALL_UPTO && M % 64 == 0 && N % 32 == 0) return launch_small(ab, nprob, (hipStream_t)stream);
+  // twin launches of >= 512 rows: three problems as 128 x 64 tiles are 384 workgroups of 96 KB LDS - one and a half
+  // rounds over the chip; as 128 x 128 tiles they are 192, each streaming 1 MB instead of 768 KB for twice the outputs
+  if (M2 > 0 && nprob > 2 && M >= 512 && M % 128 == 0 && N % 128 == 0)
+    return launch_ring<128, 128, 2, 8>(ab, nprob, (hipStream_t)stream);
   if (M % 128 == 0 && N % 64 == 0) return launch_ring<128, 64, 2, 8>(ab, nprob, (hipStream_t)stream);
   return launch_small(ab, nprob, (hipStream_t)stream);
 }

@@ -13,9 +13,6 @@ gradients, optimiser steps and soft target update, but scheduled MI355X-first:
 
 Random draws are explicit inputs (`noise` dict, reference draw order - SURVEY 8a note 1).
 """
-import contextlib
-import os
-
 import torch
 
 from . import blocks, ops
@@ -347,14 +344,7 @@ class ACEngine:
     # also get their activations saved by that launch.  Otherwise: the per-layer path.
     GRAD_PROBS = ("a_og", "q1", "q2")
     use_fused = True  # tests flip this to compare the fused launch against the per-layer path
-    # MLP weight gradients on side streams (parallel graph branches): they are needed only by Adam, so
-    # they leave the dependent chain of the update (1.70 -> 1.60 ms/step at the bench shapes)
-    # MLP weight gradients on side streams (graph branches joined before the optimiser) or in line behind their input-gradient
-    # launch: True / False / a collection of site tags ("q", "pi", "genc").  In line since round 3: beside the action-decoder
-    # branch's chip-wide GEMMs a third set of concurrent launches costs the chain more than its own kernels' time
-    # (same-process A/B on the headline step: 0.8801 -> 0.8682 ms; TACORL_WGRAD_SIDE=1 restores the branches)
-    wgrad_side_streams = os.environ.get("TACORL_WGRAD_SIDE", "0") == "1"
-    conv_wgrad_side_stream = False  # measured: 0.97 -> 1.12 ms/step when on (co-resident workgroups slow the chain); conv3 / conv2 weight gradients beside the dgrad chain (see _encoders_backward)
+    EF_SPLIT_BUDGET = 160  # workgroups of the update's own encoder launch in encode_split
 
     def _fused_ok(self, c):
         if not self.use_fused or self.compute != BF16 or self.img_dtype != torch.bfloat16:
@@ -385,10 +375,10 @@ class ACEngine:
         return pr
 
     def encode_split(self, between):
-        """(TACORL_EF_SPLIT_LMP, fused path only): the frozen extra problems (TACORL: the LMP window, whose
-        embeddings the plan recognition -> action decoder branch waits for) as a launch of their own FIRST, `between()` (the
-        caller forks that branch there), then the update's own problems on TACORL_EF_SPLIT_BUDGET workgroups (default 160:
-        96 CUs stay free for the branch; sweep 96 .. 240 on C4 / C3: 128 - 160 best).  Returns False when the split does not apply (nothing launched)."""
+        """(Fused path only): the frozen extra problems (TACORL: the LMP window, whose embeddings the plan recognition ->
+        action decoder branch waits for) as a launch of their own FIRST, `between()` (the caller forks that branch there),
+        then the update's own problems on EF_SPLIT_BUDGET workgroups (160: 96 CUs stay free for the branch; sweep 96 .. 240
+        on C4 / C3: 128 - 160 best).  Returns False when the split does not apply (nothing launched)."""
         groups = self._fused_groups()
         if not self.extra_enc or len(groups) != 1 or sorted(groups[0]) != sorted(self.enc_cams) or not all(self._fused_bwd_ok(c) for c in self.enc_cams):
             return False
@@ -396,32 +386,36 @@ class ACEngine:
         for which in ("extra", "own"):
             pr = [x for c in cs for x in self._all_problems(c, which)]
             for c in cs:
-                self._pack_encoders(c, list({id(x[1]): x[1] for x in pr if x[6] == c}.values()), only_stale=self.ef_pack_late)
+                self._pack_stale_encoders(c, list({id(x[1]): x[1] for x in pr if x[6] == c}.values()))
             if which == "own":
-                self._launch_fused(cs[0], pr, max_wg=int(os.environ.get("TACORL_EF_SPLIT_BUDGET", "160")))
+                self._launch_fused(cs[0], pr, max_wg=self.EF_SPLIT_BUDGET)
             else:
                 self._launch_fused(cs[0], pr)
                 between()
         return True
 
-    # Packed conv weights of the fused encoder forward (bf16 MFMA fragments in the kernel's register order).  Round 5: the
-    # pack launch of the networks the optimiser moves runs BEHIND the Adam launch, at the end of the step - in the shadow of
+    # Packed conv weights of the fused encoder forward (bf16 MFMA fragments in the kernel's register order).  The pack launch
+    # of the networks the optimiser moves runs BEHIND the Adam launch, at the end of the step (phase_c) - in the shadow of
     # the action-decoder branch, which ends later - instead of in front of the encoder forward at the head of the next
     # step's chain; a packed copy counts as current while the block's torch version counter is the one recorded when it was
-    # packed (see mirrors_stale), so frozen networks (TACORL's LMP encoder) are packed once, not every step.
-    # TACORL_EF_PACK_LATE=0: every network in front of every forward, as before.
-    ef_pack_late = os.environ.get("TACORL_EF_PACK_LATE", "1") == "1"
+    # packed, so in front of a forward only what something else has written since is packed again (_pack_stale_encoders),
+    # and frozen networks (TACORL's LMP encoder) are packed once, not every step.
+    def _pack_versions(self):
+        """(id(net), camera) -> the block's version counter when its packed copy was written."""
+        return self.__dict__.setdefault("_wpk_ver", {})
 
-    def _pack_encoders(self, c, nets, only_stale=False):
-        vers = self.__dict__.setdefault("_wpk_ver", {})
-        if only_stale:
-            nets = [n_ for n_ in nets if vers.get((id(n_), c)) != n_.param._version]
+    def _pack_encoders(self, c, nets):
         if not nets:
             return
         call("tacorl_encoder_pack_weights", len(nets), ops.ptr_array([n_.enc(c) for n_ in nets]),
              ops.ptr_array([self._packed(n_, c) for n_ in nets]), ops.stream())
+        vers = self._pack_versions()
         for n_ in nets:
             vers[(id(n_), c)] = n_.param._version
+
+    def _pack_stale_encoders(self, c, nets):
+        vers = self._pack_versions()
+        self._pack_encoders(c, [n_ for n_ in nets if vers.get((id(n_), c)) != n_.param._version])
 
     def _late_pack_nets(self):
         return [self.actor, self.q1, self.q2, self.tq1, self.tq2]
@@ -429,7 +423,7 @@ class ACEngine:
     def packs_stale(self):
         """Would a replayed step read a packed copy that no longer matches its parameter block?  (Every network of the
         step's encoder launch: the optimiser's ones AND the extra, frozen ones.)"""
-        if not self.ef_pack_late or not getattr(self, "_wpk_ver", None):
+        if not getattr(self, "_wpk_ver", None):
             return False
         nets = {id(n_): n_ for n_ in self._late_pack_nets()}
         nets.update({id(x["net"]): x["net"] for x in self.extra_enc})
@@ -439,7 +433,7 @@ class ACEngine:
     def packs_written(self):
         """The step's tail launch (eager, or the replayed graph's) has just re-packed the optimiser's networks: record it."""
         vers = getattr(self, "_wpk_ver", None)
-        if self.ef_pack_late and vers:
+        if vers:
             for n_ in self._late_pack_nets():
                 for c in self.enc_cams:
                     if (id(n_), c) in vers:
@@ -457,14 +451,13 @@ class ACEngine:
     def _fused_groups(self):
         """Cameras whose fused encoder problems share ONE launch: the cameras of one geometry when their problems fit the
         launch's table (round 5; C4: two 128 x 128 cameras, 7 problems each - one launch over 5 504 images instead of two over
-        2 752: one prologue, one tail); every other fused camera alone.  TACORL_EF_MERGE_CAMS=0: one launch per camera."""
+        2 752: one prologue, one tail); every other fused camera alone."""
         groups, out = {}, []
         for c in self.enc_cams:
             if self._fused_ok(c):
                 groups.setdefault((tuple(self.hw[c]), bool(self._fused_bwd_ok(c))), []).append(c)
         for (_, bwd_ok), cs in groups.items():
-            if (bwd_ok and len(cs) > 1 and os.environ.get("TACORL_EF_MERGE_CAMS", "1") == "1"
-                    and sum(len(self._all_problems(c)) for c in cs) <= 16):
+            if bwd_ok and len(cs) > 1 and sum(len(self._all_problems(c)) for c in cs) <= 16:
                 out.append(cs)
             else:
                 out += [[c] for c in cs]
@@ -494,7 +487,7 @@ class ACEngine:
                 allp = []
                 for cc in merged[c]:
                     prc = self._all_problems(cc)
-                    self._pack_encoders(cc, list({id(x[1]): x[1] for x in prc}.values()), only_stale=self.ef_pack_late)
+                    self._pack_stale_encoders(cc, list({id(x[1]): x[1] for x in prc}.values()))
                     allp += prc
                 self._launch_fused(c, allp)
                 continue
@@ -505,7 +498,7 @@ class ACEngine:
                 slow = [] if saves else [x for x in pr if x[5]]
                 pr = [x for x in pr if not (slow and x[5])]
                 nets = {id(x[1]): x[1] for x in pr}
-                self._pack_encoders(c, list(nets.values()), only_stale=self.ef_pack_late)
+                self._pack_stale_encoders(c, list(nets.values()))
                 self._launch_fused(c, pr)
                 pr = slow
             if pr:
@@ -514,44 +507,18 @@ class ACEngine:
                      ops.ptr_array([x[3] for x in pr]), ops.int_array([x[4] for x in pr]), H, W, xd, self.compute,
                      ops.stream())
 
-    # bf16 mirrors of the MLP weights (the fused MLP kernels' MFMA operand).  Round 5: the Adam / Polyak launch writes them
-    # itself (ops.adam_step_batch(mirrors=...)), so the conversion launch at the head of the next step's chain is gone; a
-    # mirror counts as current while its block's torch version counter is the one recorded when it was written (every
-    # other writer - load_state_dict, broadcast, sync_targets, a user's in-place edit - moves the counter), and the
-    # conversion launch below runs only for blocks that are not (first step, after a load).
-    # MEASURED SLOWER, default off (round 5, separate processes on one box, ms/step: 0.8370 with the conversion launch
-    # against 0.8431 - 0.8485 without it): the plan recognition's 256 one-per-CU workgroups (351 registers: no fused-MLP
-    # workgroup fits beside one) start their launch beside the first kernels of phase_a; whatever delays phase_a's first
-    # MLP launch by a few microseconds lets all of them start at once, and the action-decoder branch behind them - the
-    # step's co-critical chain - starts that much earlier.  The conversion launch is such a delay and costs nothing else.
-    adam_writes_mirrors = os.environ.get("TACORL_ADAM_MIRRORS", "0") == "1"
-
-    def _mirror_nets(self):
-        return [self.actor, self.q1, self.q2, self.tq1, self.tq2]
-
-    def mirrors_stale(self):
-        return self.compute == BF16 and any(getattr(n_, "_mirror_ver", None) != n_.param._version for n_ in self._mirror_nets())
-
-    def mirrors_written(self):
-        """The optimiser launch (eager, or the replayed graph's) has just written every mirror: record the versions."""
-        if self.compute == BF16 and self.adam_writes_mirrors:
-            for n_ in self._mirror_nets():
-                n_._mirror_ver = n_.param._version
-
     def _refresh_bf16(self):
-        """bf16 copies of the five networks' MLP weights (one launch) where they are not current; the fp32 blocks stay the masters."""
+        """bf16 copies of the five networks' MLP weights, the fused MLP kernels' MFMA operand (one launch, every step); the
+        fp32 blocks stay the masters.  Having the Adam / Polyak launch write them instead measured slower (round 5, ms/step:
+        0.8370 with this launch against 0.8431 - 0.8485 without): the few microseconds by which it delays phase_a's first MLP
+        launch let the plan recognition's 256 one-per-CU workgroups all start at once, and the action-decoder branch behind
+        them - the step's co-critical chain - starts that much earlier."""
         if self.compute != BF16:
             return
-        nets = [n_ for n_ in self._mirror_nets()
-                if not self.adam_writes_mirrors or getattr(n_, "_mirror_ver", None) != n_.param._version
-                or os.environ.get("TACORL_ALWAYS_REFRESH") == "1"]
-        if not nets:
-            return
+        nets = [self.actor, self.q1, self.q2, self.tq1, self.tq2]
         call("tacorl_to_bf16_batch", len(nets), ops.ptr_array([n_.genc() for n_ in nets]),
              ops.ptr_array([n_.genc_bf16() for n_ in nets]), (ops.C.c_long * len(nets))(*[n_.size - n_.genc_off for n_ in nets]),
              ops.stream())
-        for n_ in nets:
-            n_._mirror_ver = n_.param._version
 
     def _mlp_bwd_sites(self):
         """(tag, params, M, dims) of every fused-MLP backward of the update, as _mlp_backward receives them."""
@@ -563,46 +530,34 @@ class ACEngine:
                 ("genc", [self.actor.genc(), self.q1.genc(), self.q2.genc()], [B] * 3, gd)]
 
     def _prepack_backward(self):
-        """Weight-only preparation of the backward kernels (transposed MLP weights, conv W^T fragments) on a
-        side stream while the forward runs: six small launches that would otherwise sit on the dependent
-        chain of the backward."""
+        """Weight-only preparation of the backward kernels (transposed MLP weights, conv W^T fragments) in front of the
+        forward: six small launches that would otherwise sit on the dependent chain of the backward.  In line (round 5): they
+        are small enough in registers to run beside the plan recognition's workgroups, which the fused MLP forwards that
+        follow are not, and on a side branch of the graph the fork / join made the step 8 us longer."""
         self._prepacked = False
         if self.compute != BF16:
             return
-        # in line since round 5 (TACORL_PACK_INLINE=0: a side branch of the graph, as before): these launches are small
-        # enough in registers to run beside the plan recognition's workgroups, which the fused MLP forwards that follow
-        # are not, and without the fork / join the step is 8 us shorter (0.8467 / 0.8432 -> 0.8370 ms, same box)
-        inline = os.environ.get("TACORL_PACK_INLINE", "1") == "1"
-        if getattr(self, "_pack_stream", None) is None:
-            self._pack_stream = torch.cuda.Stream(device=self.dev)
-        ps = torch.cuda.current_stream() if inline else self._pack_stream
-        if not inline:
-            ps.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(ps):
-            for tag, params, M, dims in self._mlp_bwd_sites():
-                ops.mlp_bwd_fused_pack(params, M, dims, "mlp_bwdf_" + tag, self.dev)
-            nets = [self.actor, self.q1, self.q2]
-            for cs in self._ebw_sequences():
-                c = cs[0]
-                if self._fused_bwd_ok(c):
-                    H, W = self.hw[c]
-                    np_ = 3 * len(cs)
-                    n3 = ops.int_array([self.nbwd[cc] for cc in cs for _ in nets])
-                    nb = ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(np_, n3, H, W)
-                    ws = ops.workspace(nb, self.dev, "enc_bwd_fused_" + "+".join(cs))
-                    call("tacorl_encoder_bwd_fused_pack", np_, ops.ptr_array([x.enc(cc) for cc in cs for x in nets]), n3, H, W, ptr(ws),
-                         ws.numel(), ops.stream())
+        for tag, params, M, dims in self._mlp_bwd_sites():
+            ops.mlp_bwd_fused_pack(params, M, dims, "mlp_bwdf_" + tag, self.dev)
+        nets = [self.actor, self.q1, self.q2]
+        for cs in self._ebw_sequences():
+            c = cs[0]
+            if self._fused_bwd_ok(c):
+                H, W = self.hw[c]
+                np_ = 3 * len(cs)
+                n3 = ops.int_array([self.nbwd[cc] for cc in cs for _ in nets])
+                nb = ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(np_, n3, H, W)
+                ws = ops.workspace(nb, self.dev, "enc_bwd_fused_" + "+".join(cs))
+                call("tacorl_encoder_bwd_fused_pack", np_, ops.ptr_array([x.enc(cc) for cc in cs for x in nets]), n3, H, W, ptr(ws),
+                     ws.numel(), ops.stream())
         self._prepacked = True
 
     # Gathered MLP inputs (round 5): the concatenations in front of the goal encoders, the policy head and the Q heads are
     # read by the fused forward's input stage where their producers left them (ops.mlp_fwd_gather) instead of being
-    # assembled by a copy launch first - three launches fewer on the step's dependent chain.  TACORL_MLP_GATHER=0 (or a
-    # shape the gathered forward does not take: f32 mode, C5's many-row Q problems) restores copy + forward.
-    gather_inputs = os.environ.get("TACORL_MLP_GATHER", "1") == "1"
-
+    # assembled by a copy launch first - three launches fewer on the step's dependent chain.  A shape the gathered forward
+    # does not take (f32 mode, C5's many-row Q problems) goes through copy + forward.
     def _gather_ok(self, tag):
-        if not (self.gather_inputs if self.gather_inputs is not None else os.environ.get("TACORL_MLP_GATHER", "1") == "1") \
-                or self.compute != BF16:
+        if self.compute != BF16:
             return False
         cache = self.__dict__.setdefault("_gather_cache", {})
         key = (tag, self.B)
@@ -707,7 +662,7 @@ class ACEngine:
         ops.mark("a:start")
         # (round 5: the weight-only launches of the two calls below - bf16 mirrors, transposed weights of the four MLP backward
         # sites and of the encoders' FC tails: 7 launches of 5 - 7 us on this chain - leave as ONE, ops.prep_batch)
-        with ops.prep_batch() if os.environ.get("TACORL_PACK_INLINE", "1") == "1" else contextlib.nullcontext():
+        with ops.prep_batch():
             self._refresh_bf16()
             self._prepack_backward()
         self._assemble_states()
@@ -715,7 +670,6 @@ class ACEngine:
         ops.mark("a:policy_fwd")
         head_cur, head_next = self._head("a"), self._head("a_nx")
         g = (lambda k: nz[k]) if self.dg else (lambda k: None)
-        # actor rsample on obs, critic-target sample on next_obs, CQL samples on both
         # one launch: rsample on obs, critic-target sample on next_obs, the n CQL samples on both, uniform actions
         at = ops._at
         jobs = [(head_cur, nz["eps_pi"], g("g_pi"), 1, ptr(self.act_pi), self.logp_pi, self.grip_pi if self.dg else None, 1),
@@ -738,8 +692,6 @@ class ACEngine:
             call("tacorl_alpha_loss", ptr(self.logp_pi), B, ptr(self.log_alpha.param), float(hp["target_entropy"]), gs,
                  ptr(self.log_alpha.grad), ptr(self.logs), ops.stream())
         ops.mark("a:alpha")
-        if getattr(self, "_prepacked", False) and os.environ.get("TACORL_PACK_INLINE", "1") != "1":  # the side branch ends inside this phase
-            torch.cuda.current_stream().wait_stream(self._pack_stream)
         ops.mark("a:end")
 
     def phase_b(self, bc_phase, optimize=True):
@@ -820,7 +772,6 @@ class ACEngine:
             main_stream.wait_stream(self._bwd_stream)
             self._encoders_backward()
             ops.mark("b:enc_bwd")
-            self._join_wgrads()
         ops.mark("b:end")
 
     lean_mlp_acts = True  # hidden-layer outputs of the fused MLPs are recomputed by the weight-gradient launch, not saved
@@ -840,10 +791,10 @@ class ACEngine:
         return cache[tag]
 
     def _mlp_backward(self, tag, xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts):
-        """MLP backward.  bf16 mode: the input-gradient chain is ONE launch on the current stream and the
-        weight gradients go to a side stream of their own (a parallel graph branch joined before the
-        optimiser) - they are needed only by Adam, not by anything downstream in the backward.
-        Otherwise: the per-layer path."""
+        """MLP backward.  bf16 mode: the input-gradient chain as ONE launch, the weight gradients as one launch in line
+        behind it (on side streams of their own - only Adam needs them - a third set of concurrent launches beside the
+        action-decoder branch's chip-wide GEMMs cost the chain more than their kernels' time: 0.8801 -> 0.8682 ms in line,
+        round 3).  Otherwise: the per-layer path."""
         n = len(xs)
         if not ops.mlp_bwd_fused_ok(n, dims, ldo, ldd, self.compute):
             ops.mlp_bwd(xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, self.compute,
@@ -851,26 +802,8 @@ class ACEngine:
             return
         ops.mlp_bwd_fused_dgrad(params, acts_buf, d_outs, ldo, d_xs, ldd, M, dims, acts, "mlp_bwdf_" + tag,
                                 prepacked=getattr(self, "_prepacked", False), lean=self._lean(tag))
-        if all(g is None for g in grads):
-            return
-        side = self.wgrad_side_streams
-        if not (side is True or (side and tag in side)):  # True / False / a collection of site tags
+        if any(g is not None for g in grads):
             ops.mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, "mlp_bwdf_" + tag, lean=self._lean(tag))
-            return
-        if not hasattr(self, "_wg_streams"):
-            self._wg_streams, self._wg_pending = {}, []
-        if tag not in self._wg_streams:
-            self._wg_streams[tag] = torch.cuda.Stream(device=self.dev)
-        ws_ = self._wg_streams[tag]
-        ws_.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(ws_):
-            ops.mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, "mlp_bwdf_" + tag, lean=self._lean(tag))
-        self._wg_pending.append(ws_)
-
-    def _join_wgrads(self):
-        for ws_ in getattr(self, "_wg_pending", []):
-            torch.cuda.current_stream().wait_stream(ws_)
-        self._wg_pending = []
 
     def _actor_backward(self, bc_phase, head_cur, q1p, q2p, gs):
         B, A, Ac, nz = self.B, self.A, self.Ac, self.noise
@@ -899,10 +832,9 @@ class ACEngine:
         groups = {}
         for c in self.enc_cams:
             groups.setdefault((tuple(self.hw[c]), bool(self._fused_bwd_ok(c))), []).append(c)
-        merge = os.environ.get("TACORL_EBW_MERGE_CAMS", "1") == "1"
         seqs = []
         for (_, ok), cs in groups.items():
-            if ok and merge and 3 * len(cs) <= 8:
+            if ok and 3 * len(cs) <= 8:
                 seqs.append(cs)
             else:
                 seqs += [[c] for c in cs]
@@ -970,20 +902,13 @@ class ACEngine:
         if optimize:
             a = self.actor
             items = [(lap.param, lap.grad, lap.m, lap.v, hp["critic_lr"], 0.0, lap.step, None, 0.0)] if self.with_lagrange else []
-            mir = [(None, None)] * len(items)
             items.append((a.param, a.grad, a.m, a.v, hp["actor_lr"], hp["clip"], a.step, None, 0.0))
-            mir.append((a.param_bf16, None))
             for q, t in ((self.q1, self.tq1), (self.q2, self.tq2)):
                 items.append((q.param, q.grad, q.m, q.v, hp["critic_lr"], hp["clip"], q.step, t.param, hp["tau"]))
-                mir.append((q.param_bf16, t.param_bf16))
-            write = self.compute == BF16 and self.adam_writes_mirrors
-            ops.adam_step_batch(items, mirrors=mir if write else None)  # two launches for all blocks
-            if write:  # (this launch rewrote every mirror from the updated parameters, whatever state they were in)
-                self.mirrors_written()
-            if self.ef_pack_late:
-                for c in self.enc_cams:
-                    if self._fused_ok(c):
-                        self._pack_encoders(c, self._late_pack_nets())
+            ops.adam_step_batch(items)  # two launches for all blocks
+            for c in self.enc_cams:  # (the fused encoder forward's packed conv weights: see _pack_encoders)
+                if self._fused_ok(c):
+                    self._pack_encoders(c, self._late_pack_nets())
         ops.mark("c:adam")
 
     def _allreduce(self, tensors):

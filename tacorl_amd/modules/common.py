@@ -293,9 +293,9 @@ class GraphMixin:
             self._graphs[key] = self._graphs.pop(key)
         stale = getattr(self, "_derived_stale", None)
         if gs is not None and stale is not None and stale():
-            # the captured step relies on weight-derived buffers that the previous step's optimiser launch left current
-            # (bf16 mirrors written by the Adam kernel); something else has written the parameters since - a user's
-            # in-place edit, a broadcast - so run the step in python once more (it refreshes what is stale) and re-capture
+            # the captured step relies on weight-derived buffers that the previous step's tail launch left current (the
+            # encoders' packed conv weights); something else has written the parameters since - a user's in-place edit,
+            # a broadcast - so run the step in python once more (it refreshes what is stale) and re-capture
             self._graphs = {}
             gs = None
         if gs is not None and gs[2] != ops.alloc_epoch():

@@ -7,8 +7,6 @@ Select with `module._target_=tacorl_amd.modules.tacorl.tacorl.TACORL`.
 """
 from pathlib import Path
 
-import os
-
 import torch
 import torch.nn as nn
 
@@ -247,8 +245,7 @@ class TACORL(CQL_Offline):
                 ops.pack_images_u8_batch(jobs, xd, H, W)  # pitches are in bytes = elements
             elif nchw and (H * W) % 4 == 0:  # one launch for the window frames and the obs / goal / next images
                 import ctypes as C
-                if (c in self.all_modalities and c in e.cams and len(jobs) == 4 and T >= 2
-                        and os.environ.get("TACORL_PACK_DEDUP", "1") == "1"):
+                if c in self.all_modalities and c in e.cams and len(jobs) == 4 and T >= 2:
                     # obs = window frame 0 and next = window frame T - 1 (get_rl_batch): written from the one read of the
                     # window; the goal image stays a job of its own
                     win, _, goal, _ = jobs
@@ -278,10 +275,7 @@ class TACORL(CQL_Offline):
         e = self.engine
         ops.mark("front:start")
         if getattr(self, "_pr_stream", None) is None:
-            # (TACORL_PR_PRIO=1, with the encoder-split experiment: the plan recognition's stream at high priority, so that
-            # its workgroups take the CUs the first encoder launch frees ahead of the second launch's)
-            prio = -1 if os.environ.get("TACORL_PR_PRIO", "0") == "1" else 0
-            self._pr_stream, self._side_stream = torch.cuda.Stream(device=self.dev, priority=prio), torch.cuda.Stream(device=self.dev)
+            self._pr_stream, self._side_stream = torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev)
         main = torch.cuda.current_stream()
         mods = self.plan_recognition_modalities
         # one camera: the frame embeddings are the transformer's input as they stand
@@ -303,10 +297,8 @@ class TACORL(CQL_Offline):
         # recurrent launches of 64 rows; `ad:end` 1 017 us against `c:adam` 864) 1.274 - 1.293 -> 1.222 - 1.238 ms/step in six
         # of seven runs (one read 1.337: whose workgroups get the freed CUs first is a race); the headline step (window 16,
         # balanced chains) +12 us; the same step with the decoder fine-tuned (C3: loss, BPTT, weight gradients and Adam make
-        # that branch the critical one) 1.518 -> 1.497.  TACORL_EF_SPLIT_LMP = auto (default: windows of 24 steps and more, or
-        # a fine-tuned decoder) / 0 / 1.
-        sp = os.environ.get("TACORL_EF_SPLIT_LMP", "auto")
-        split = with_ad and (sp == "1" or (sp == "auto" and (T >= 24 or (optimize and self.finetune_action_decoder))))
+        # that branch the critical one) 1.518 -> 1.497.  Hence: windows of 24 steps and more, or a fine-tuned decoder.
+        split = with_ad and (T >= 24 or (optimize and self.finetune_action_decoder))
         forked = []
 
         def fork_branches():

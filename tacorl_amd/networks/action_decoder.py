@@ -8,7 +8,6 @@ contiguous row range; the four heads (mean_fc | log_scale_fc | prob_fc | gripper
 back to back and evaluated as one GEMM.
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -131,7 +130,7 @@ class ActionDecoderLogistic:
         self.whb = [bf(H, H) for _ in range(self.L)]
         self.wib = [None] + [bf(H, H) for _ in range(1, self.L)]  # W_ih of layers >= 1 (H x H)
         self.headw_b, self.headb = bf(self.NHP, H), f(self.NHP)    # output heads, rows padded with zeros
-        # layer 0's input projection inside the ring GEMM (K extension, proj_in_ring): the bf16 input rows, zero padded to 128
+        # layer 0's input projection inside the ring GEMM (K extension, where _ring_proj() says the input fits): the bf16 input rows, zero padded to 128
         # columns, and W_ih_l0 likewise
         self.xb_seq, self.wih0_b = bf(R, 128), bf(H, 128)
         self._shape = (B, Tm)
@@ -164,11 +163,9 @@ class ActionDecoderLogistic:
     # Round 5: layer 0's input projection W_ih [plan | emb_t] + b_ih is no launch of its own (tacorl_ad_input_proj: 19.8 us at the
     # head of the action-decoder branch, 33.5 MB of fp32 addend written and read back) but ONE MORE K TILE of that layer's
     # recurrent ring-GEMM step (tacorl_rnn_linear_fwd_batch_ext); what remains in front is a 1 MB bf16 copy of the input rows.
-    # TACORL_AD_PROJ_RING=0 (or proj_in_ring = False): the separate projection launch, as before.
-    proj_in_ring = os.environ.get("TACORL_AD_PROJ_RING", "1") == "1"
-
+    # Inputs wider than that tile's 128 columns take the separate projection launch.
     def _ring_proj(self):
-        return bool(self.proj_in_ring) and os.environ.get("TACORL_AD_PROJ_RING", "1") == "1" and self.P + self.E <= 128
+        return self.P + self.E <= 128
 
     def twin_input_proj(self, plan, emb, ld_emb, B, T, Tm):
         """Layer-0 input projection of the twin pass (reads the fp32 weights: may run before forward(), on another stream)."""
@@ -407,8 +404,7 @@ class ActionDecoderLogistic:
         # (mirrors_current / prepared: the caller has issued refresh_mirrors() / prepare_backward() for the current weights)
         self.forward(plan, emb, ld, B, T, T - 1, module.compute, frozen=frozen and not optimize, mirrors_current=mirrors_current)
         slot = ops._at(module.engine.logs, LOG_SLOTS.index("action_loss"))
-        self.loss(acts, slot, B, T, T - 1, want_grad=optimize, grad_scale=1.0 / module.world_size,
-                  lazy=bool(getattr(module, "ad_loss_lazy", True)) and os.environ.get("TACORL_AD_LOSS_LAZY", "1") == "1")
+        self.loss(acts, slot, B, T, T - 1, want_grad=optimize, grad_scale=1.0 / module.world_size, lazy=True)
         if optimize:
             # (no wgrad_stream here.  This call already runs on a branch of the step's graph: a side stream joined back INTO
             # that branch crashed hipStreamEndCapture on ROCm 7.2; forked from and joined into the main stream instead - with
@@ -450,8 +446,8 @@ class ActionDecoderLogistic:
         do not qualify - the caller then goes layer by layer."""
         blk, H, R, L = self.blk, self.hidden, B * Tm, self.L
         sup = ops.L.lib().tacorl_rnn_wgrad_supported
-        if (os.environ.get("TACORL_AD_WGRAD_BATCH", "1") != "1" or not getattr(self, "wgrad_batched", True) or Tm < 2
-                or 2 * L - 1 > 4 or L < 2 or not sup((Tm - 1) * B, H, H) or not sup(R, H, H)):
+        if (not getattr(self, "wgrad_batched", True) or Tm < 2 or 2 * L - 1 > 4 or L < 2
+                or not sup((Tm - 1) * B, H, H) or not sup(R, H, H)):
             return False
         bfp = lambda t, off: C.c_void_p(t.data_ptr() + 2 * off)  # noqa: E731
         dz, x, rows, dw, db = [], [], [], [], []

@@ -1,7 +1,6 @@
 """Thin torch-tensor wrappers over the C ABI (device memory + streams are torch's; the
 arithmetic is libtacorl_hip.so's).  No function here computes anything itself."""
 import ctypes as C
-import os
 
 import torch
 
@@ -316,8 +315,8 @@ def mark(name):
 class prep_batch:
     """`with ops.prep_batch():` - the weight-only preparation launches issued inside (to_bf16 mirrors, the MLP backward
     sites' transposed weights, the encoders' FC-tail transposes) become ONE launch at the end of the block, on the
-    stream current THERE (tacorl_prep_batch_begin / _end).  TACORL_PREP_BATCH=0: every launch on its own, as before."""
-    enabled = os.environ.get("TACORL_PREP_BATCH", "1") == "1"
+    stream current THERE (tacorl_prep_batch_begin / _end).  enabled = False: every launch on its own (the tests' comparator)."""
+    enabled = True
 
     def __enter__(self):
         self.on = prep_batch.enabled
@@ -336,19 +335,18 @@ class prep_batch:
 class reduce_batch:
     """`with ops.reduce_batch():` - the slab reduces of the one-launch MLP weight gradients issued inside are summed by ONE
     launch at the end of the block (on the stream current there); the gradients are complete only after it.
-    MEASURED SLOWER on the headline step, default off (same-process A/B, scratch/ab_step.py ops:reduce_batch.enabled:
-    0.8201 -> 0.8276 ms/step): the five reduces run in launch gaps of the step's other branch where they stand; as one
-    launch at the end of the backward they are 10 us of their own in front of the optimiser.  TACORL_REDUCE_BATCH=1 enables."""
-    enabled = os.environ.get("TACORL_REDUCE_BATCH", "0") == "1"
+    Off unless the caller asks (auto) or a test sets enabled: it measured slower on the headline step (same-process A/B:
+    0.8201 -> 0.8276 ms/step) - the five reduces run in launch gaps of the step's other branch where they stand; as one
+    launch at the end of the backward they are 10 us of their own in front of the optimiser."""
+    enabled = False
 
     def __init__(self, auto=False):
         """auto: the caller's own judgement for this block (the actor-critic engine: many-row Q problems, where the reduces
-        are large enough for one launch to win - C5 1.597 -> 1.586 ms/step); TACORL_REDUCE_BATCH=0 / 1 overrides it."""
+        are large enough for one launch to win - C5 1.597 -> 1.586 ms/step)."""
         self.auto = bool(auto)
 
     def __enter__(self):
-        env = os.environ.get("TACORL_REDUCE_BATCH")
-        self.on = reduce_batch.enabled or (self.auto and env != "0")
+        self.on = reduce_batch.enabled or self.auto
         if self.on:
             call("tacorl_reduce_batch_begin")
         return self
