@@ -25,7 +25,13 @@ typedef void* tacorl_stream_t; /* hipStream_t */
 
 #define TACORL_MAXP 16 /* max problems per batched call */
 enum { TACORL_F32 = 0, TACORL_BF16 = 1 };               /* storage / MFMA operand dtype */
-enum { TACORL_ACT_NONE = 0, TACORL_ACT_RELU = 1, TACORL_ACT_SILU = 2 };
+enum { TACORL_ACT_NONE = 0, TACORL_ACT_RELU = 1, TACORL_ACT_SILU = 2, TACORL_ACT_TANH = 3 };
+/* TANH (goal encoders with last_layer_activation: Tanh): taken by tacorl_mlp_fwd / tacorl_mlp_bwd and the fused
+ * tacorl_mlp_fwd_fused* / tacorl_mlp_bwd_fused_* entry points, as a hidden or as the LAST activation; its derivative is
+ * taken from the saved output (1 - y^2).  A LAST-layer TANH is a pass d_out * (1 - y^2) in front of the usual chain;
+ * tacorl_mlp_bwd_fused_dgrad leaves its result in the workspace, where tacorl_mlp_bwd_fused_wgrad (same workspace, called
+ * after it, as for the hidden layers' dZ) reads it.  The many-row and persistent MLP kernels are SiLU-only and are not
+ * selected. */
 
 int tacorl_hip_version(void);
 int tacorl_hip_init(int device);             /* idempotent; checks the device is gfx950 */
@@ -305,7 +311,7 @@ int tacorl_to_bf16_batch(int n, const float* const* src, void* const* dst, const
                          tacorl_stream_t stream);
 size_t tacorl_mlp_bwd_ws_bytes(int nprob, const int* M, int n_layers, const int* dims);
 /* d_out: gradient w.r.t. the last layer's output [M][dims[n_layers]], leading dim ldo (last act
- * must be NONE).
+ * NONE, or TANH: d_out is then multiplied by 1 - y^2 of the saved output first).
  * grads[p] may be NULL (skip weight gradients); d_x[p] may be NULL (skip input gradient). */
 int tacorl_mlp_bwd(int nprob, const float* const* x, int ldx, const float* const* params,
                    const float* const* act, const float* const* d_out, int ldo, float* const* grads,
@@ -610,6 +616,13 @@ int tacorl_actor_head_bwd(const float* head, int ld_head, const float* eps, cons
                           const float* g_act1, const float* g_act2, int ld_g, const float* value,
                           int ld_value, const int* grip_idx, const float* log_alpha, float grad_scale,
                           float* d_head, int B, int Ac, int has_grip, float* logs, tacorl_stream_t stream);
+/* Behaviour-cloning loss of a policy head against a target (relay imitation learning): loss_out[0] = -mean_m
+ * Actor.log_prob(target_m) (actor.py:140-156: target clamped to +-0.999, mean to +-9, log-std to [-5, 2], the gripper's
+ * GumbelSoftmax.log_prob at has_grip) and d_head = grad_scale * d loss / d head ([M][ld_head], the columns of head), in one
+ * launch.  head: [M][ld_head] = [mean (Ac) | log-std (Ac) | gripper logits (2)]; target: [M][ld_target] = [Ac values |
+ * gripper +-1].  The per-element arithmetic is tacorl_actor_head_bwd's `value` term; the mean is a fixed-order sum. */
+int tacorl_tanh_normal_nll(const float* head, int ld_head, const float* target, int ld_target, int M, int Ac,
+                           int has_grip, float grad_scale, float* d_head, float* loss_out, tacorl_stream_t stream);
 
 /* ---- Bellman + CQL logsumexp (+ Lagrange), forward and backward fused (:284-406) -------------- */
 size_t tacorl_cql_ws_bytes(int B);

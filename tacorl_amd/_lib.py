@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TACORL_HIP_LIB") or os.path.join(HERE, "lib", "libtacorl_hip.so")
 
 F32, BF16 = 0, 1
-ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_SILU, ACT_TANH = 0, 1, 2, 3
 MAXP = 16
 
 LOG_SLOTS = [  # enum TACORL_LG_* -> reference self.log key
@@ -146,6 +146,7 @@ _SIGS = {
     "tacorl_alpha_loss_step": (_i, [_p, _i, _p, _f, _p, _p, _p, _p, _f, _p, _p]),
     "tacorl_actor_qmin": (_i, [_p, _p, _p, _i, _p, _p, _p, _f, _p, _p]),
     "tacorl_actor_head_bwd": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _f, _p, _i, _i, _i, _p, _p]),
+    "tacorl_tanh_normal_nll": (_i, [_p, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p]),
     "tacorl_cql_ws_bytes": (_sz, [_i]),
     "tacorl_cql_loss": (_i, [_p] * 13 + [_i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _p, _p, _p, _sz, _p]),
     "tacorl_adam_ws_bytes": (_sz, [_l]),

@@ -14,7 +14,7 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 #define TACORL_ELAUNCH (-5)
 
 // activation ids shared with the host side (include/tacorl_hip.h)
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2 };
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_TANH = 3 };
 
 // Reductions over the 16 lanes of a DPP row (lanes 16 r .. 16 r + 15), result in every lane: quad xor 1, quad
 // xor 2, row_half_mirror, row_mirror - four VALU-side lane exchanges, no LDS crossbar (ds_bpermute) round trips.
@@ -40,15 +40,17 @@ __device__ __forceinline__ float row16_max(float x) {
 __device__ __forceinline__ float act_apply(int act, float z) {
   if (act == ACT_RELU) return z > 0.f ? z : 0.f;
   if (act == ACT_SILU) return z / (1.f + expf(-z));
+  if (act == ACT_TANH) return tanhf(z);
   return z;
 }
-// derivative given the pre-activation z (SiLU) or the output y (ReLU: y > 0 <=> z > 0)
+// derivative given the pre-activation z (SiLU) or the output y (ReLU: y > 0 <=> z > 0; Tanh: 1 - y^2)
 __device__ __forceinline__ float act_grad(int act, float zy) {
   if (act == ACT_RELU) return zy > 0.f ? 1.f : 0.f;
   if (act == ACT_SILU) {
     float s = 1.f / (1.f + expf(-zy));
     return s * (1.f + zy * (1.f - s));
   }
+  if (act == ACT_TANH) return 1.f - zy * zy;
   return 1.f;
 }
 

@@ -1036,6 +1036,26 @@ extern "C" long tacorl_mlp_act_layout(int M, int L, const int* dims, const int* 
 }
 #define MLP_MAXL 8
 
+// An MLP whose LAST activation is not the identity (Tanh goal encoders): dZ_last = d_out * act'(y_last) from the saved
+// output, into a dense [M][N] buffer that the backward chains then treat as the last layer's dZ.
+struct OutActTbl { const float* d[GEMM_MAXP]; const float* y[GEMM_MAXP]; float* dz[GEMM_MAXP]; int M[GEMM_MAXP]; };
+__global__ __launch_bounds__(256) void out_act_grad_kernel(OutActTbl t, int ldo, int N, int act) {
+  const int p = blockIdx.y;
+  const long total = (long)t.M[p] * N;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long m = e / N;
+    t.dz[p][e] = t.d[p][m * ldo + (e - m * N)] * act_grad(act, t.y[p][e]);
+  }
+}
+static int out_act_grad(int nprob, const OutActTbl& t, int ldo, int N, int act, hipStream_t st) {
+  long mx = 0;
+  for (int p = 0; p < nprob; p++) mx = (long)t.M[p] * N > mx ? (long)t.M[p] * N : mx;
+  if (mx == 0) return TACORL_OK;
+  const int gx = cdiv(mx, 256) > 1024 ? 1024 : cdiv(mx, 256);
+  hipLaunchKernelGGL(out_act_grad_kernel, dim3(gx, nprob), dim3(256), 0, st, t, ldo, N, act);
+  return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
+}
+
 extern "C" int tacorl_mlp_fwd(int nprob, const float* const* x, int ldx, const float* const* params,
                               float* const* act, const int* M, int L, const int* dims, const int* acts, int cd,
                               tacorl_stream_t stream) {
@@ -1177,7 +1197,7 @@ extern "C" int tacorl_to_bf16_batch(int n, const float* const* src, void* const*
 // ---- MLP backward, bf16 mode: the input-gradient chain as one launch (mlp_fused.hip) and the weight
 // gradients as a separate call, so that a caller can take them off the dependent chain (another stream).
 // Workspace: [dZ_l of every problem, l = 0..L-2][transposed bf16 weights][wgrad slabs].
-struct MlpBwdWs { long dzoff[MF_MAXP * MF_MAXL]; size_t dz_floats, wt_off[MF_MAXP], wt_bytes_each, xb_off[MF_MAXP], slab_off, slab_bytes, total; };
+struct MlpBwdWs { long dzoff[MF_MAXP * MF_MAXL]; size_t dz_floats, wt_off[MF_MAXP], wt_bytes_each, xb_off[MF_MAXP], slab_off, slab_bytes, last_off[MF_MAXP], total; };
 static MlpBwdWs mlp_bwd_fused_plan(int nprob, const int* M, int L, const int* dims) {
   MlpBwdWs w{};
   long off = 0, maxM = 0;
@@ -1204,7 +1224,10 @@ static MlpBwdWs mlp_bwd_fused_plan(int nprob, const int* M, int L, const int* di
     const size_t s = mlp_big_wgrad_slab_floats(nb, Mb, L, dims) * sizeof(float);
     w.slab_bytes = s > w.slab_bytes ? s : w.slab_bytes;
   }
-  w.total = b + w.slab_bytes;
+  b = (b + w.slab_bytes + 255) & ~(size_t)255;
+  // behind everything else: dZ of the last layer when its activation is not the identity (out_act_grad_kernel)
+  for (int p = 0; p < nprob; p++) { w.last_off[p] = b; b += ((size_t)al4((long)(M[p] > 0 ? M[p] : 0) * dims[L]) * sizeof(float) + 255) & ~(size_t)255; }
+  w.total = b;
   return w;
 }
 extern "C" int tacorl_mlp_bwd_fused_supported(int nprob, int L, const int* dims, int ldo, int ldd) {
@@ -1219,9 +1242,24 @@ extern "C" int tacorl_mlp_bwd_fused_dgrad(int nprob, const float* const* params,
                                           int L, const int* dims, const int* acts, int prepacked, void* ws,
                                           size_t ws_bytes, tacorl_stream_t stream) {
   if (!mlp_fused_bwd_ok(nprob, L, dims, ldo, ldd)) FAIL(TACORL_EINVAL, "mlp_bwd_fused: shapes not supported");
-  if (acts[L - 1] != ACT_NONE) FAIL(TACORL_EINVAL, "mlp_bwd_fused: last activation must be NONE");
+  if (acts[L - 1] != ACT_NONE && acts[L - 1] != ACT_TANH) FAIL(TACORL_EINVAL, "mlp_bwd_fused: last activation must be NONE or TANH");
   const MlpBwdWs w = mlp_bwd_fused_plan(nprob, M, L, dims);
   if (ws_bytes < w.total) FAIL(TACORL_ENOMEM, "mlp_bwd_fused: workspace too small");
+  const float* d_last[MF_MAXP];
+  int acts_id[MLP_MAXL];
+  for (int l = 0; l < L; l++) acts_id[l] = acts[l];
+  if (acts[L - 1] != ACT_NONE) {  // dZ_last = d_out * act'(y_last) first; the chain (and _wgrad) read it from ws
+    OutActTbl t{};
+    for (int p = 0; p < nprob; p++) {
+      long zo[MLP_MAXL], yo[MLP_MAXL];
+      tacorl_mlp_act_layout(M[p], L, dims, acts, zo, yo);
+      t.d[p] = d_out[p]; t.y[p] = act[p] + yo[L - 1]; t.dz[p] = (float*)((unsigned char*)ws + w.last_off[p]); t.M[p] = M[p];
+      d_last[p] = t.dz[p];
+    }
+    const int rc = out_act_grad(nprob, t, ldo, dims[L], acts[L - 1], (hipStream_t)stream);
+    if (rc != TACORL_OK) FAIL(rc, "mlp_bwd_fused: output-activation launch failed (%d)", rc);
+    d_out = d_last; ldo = dims[L]; acts_id[L - 1] = ACT_NONE; acts = acts_id;
+  }
   long wo[MLP_MAXL], bo[MLP_MAXL], src[MF_MAXP * MF_MAXL];
   tacorl_mlp_param_layout(L, dims, wo, bo);
   // prepacked: bit 0 = the weight transposes are in ws already; bit 1 = the caller's forward and weight gradients run lean:
@@ -1240,7 +1278,7 @@ extern "C" int tacorl_mlp_bwd_fused_dgrad(int nprob, const float* const* params,
     for (int l = 0; l < L; l++) {
       dzo[b][q * MF_MAXL + l] = w.dzoff[p * MF_MAXL + l];
       if (b) sbf[q * MF_MAXL + l] = zo[l];
-      else src[q * MF_MAXL + l] = acts[l] == ACT_SILU ? zo[l] : (acts[l] == ACT_RELU ? yo[l] : -1);
+      else src[q * MF_MAXL + l] = acts[l] == ACT_SILU ? zo[l] : ((acts[l] == ACT_RELU || acts[l] == ACT_TANH) ? yo[l] : -1);
     }
   }
   hipStream_t st = (hipStream_t)stream;
@@ -1288,6 +1326,11 @@ extern "C" int tacorl_mlp_bwd_fused_wgrad(int nprob, const float* const* x, int 
   long wo[MLP_MAXL], bo[MLP_MAXL];
   tacorl_mlp_param_layout(L, dims, wo, bo);
   void* slab = (unsigned char*)ws + w.slab_off;
+  const float* d_last[MF_MAXP];
+  if (acts[L - 1] != ACT_NONE) {  // the last layer's dZ: what tacorl_mlp_bwd_fused_dgrad left in ws (same ws, called first)
+    for (int p = 0; p < nprob; p++) d_last[p] = (const float*)((unsigned char*)ws + w.last_off[p]);
+    d_out = d_last; ldo = dims[L];
+  }
   // many-row problems of a lean site: LDS-DMA over the bf16 copies left by the forward and the (lean-flagged) dgrad launch;
   // the others: the one-launch form / per-layer GEMMs below (both groups use the slab region, one after the other)
   const float *xs[2][MF_MAXP], *as[2][MF_MAXP], *ds[2][MF_MAXP], *dzp[2][MF_MAXP];
@@ -1356,7 +1399,7 @@ extern "C" int tacorl_mlp_bwd(int nprob, const float* const* x, int ldx, const f
                               int cd, int accumulate, void* ws, size_t ws_bytes, tacorl_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
   if (L < 1 || L > MLP_MAXL || nprob < 1 || nprob > GEMM_MAXP) FAIL(TACORL_EINVAL, "mlp_bwd: bad L/nprob");
-  if (acts[L - 1] != ACT_NONE) FAIL(TACORL_EINVAL, "mlp_bwd: last activation must be NONE");
+  if (acts[L - 1] != ACT_NONE && acts[L - 1] != ACT_TANH) FAIL(TACORL_EINVAL, "mlp_bwd: last activation must be NONE or TANH");
   long dzf; size_t slab_bytes;
   mlp_bwd_sizes(nprob, M, L, dims, dzf, slab_bytes);
   if (ws_bytes < (size_t)dzf * sizeof(float) + slab_bytes) FAIL(TACORL_ENOMEM, "mlp_bwd: workspace too small");
@@ -1372,6 +1415,18 @@ extern "C" int tacorl_mlp_bwd(int nprob, const float* const* x, int ldx, const f
   for (int p = 0; p < nprob; p++) { any_grads |= grads && grads[p]; any_dx |= d_x && d_x[p]; }
   const float* dz[GEMM_MAXP];
   for (int p = 0; p < nprob; p++) dz[p] = d_out[p];
+  if (acts[L - 1] != ACT_NONE) {
+    // dZ_last = d_out * act'(y_last) into the buffer layer L - 1 does not write (buf[L & 1]; its own output is buf[(L - 1) & 1])
+    OutActTbl t{};
+    for (int p = 0; p < nprob; p++) {
+      long zo[MLP_MAXL], yo[MLP_MAXL];
+      tacorl_mlp_act_layout(M[p], L, dims, acts, zo, yo);
+      t.d[p] = d_out[p]; t.y[p] = act[p] + yo[L - 1]; t.dz[p] = buf[L & 1][p]; t.M[p] = M[p];
+      dz[p] = buf[L & 1][p];
+    }
+    CHECK(out_act_grad(nprob, t, ldo, dims[L], acts[L - 1], st));
+    ldo = dims[L];
+  }
   for (int l = L - 1; l >= 0; l--) {
     const float *xin[GEMM_MAXP], *w[GEMM_MAXP], *src[GEMM_MAXP];
     float *dw[GEMM_MAXP], *db[GEMM_MAXP], *out[GEMM_MAXP];
@@ -1385,7 +1440,7 @@ extern "C" int tacorl_mlp_bwd(int nprob, const float* const* x, int ldx, const f
       dw[p] = hg ? grads[p] + wo[l] : nullptr; db[p] = hg ? grads[p] + bo[l] : nullptr;
       Mg[p] = hg ? M[p] : 0;
       if (l > 0) {
-        src[p] = acts[l - 1] == ACT_SILU ? act[p] + zo[l - 1] : (acts[l - 1] == ACT_RELU ? act[p] + yo[l - 1] : nullptr);
+        src[p] = acts[l - 1] == ACT_SILU ? act[p] + zo[l - 1] : ((acts[l - 1] == ACT_RELU || acts[l - 1] == ACT_TANH) ? act[p] + yo[l - 1] : nullptr);
         out[p] = buf[l & 1][p]; Md[p] = M[p];
       } else {
         src[p] = nullptr; out[p] = d_x ? d_x[p] : nullptr; Md[p] = out[p] ? M[p] : 0;

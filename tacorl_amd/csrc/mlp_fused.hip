@@ -61,6 +61,10 @@ __device__ __forceinline__ float sigmoid_fast(float z) {
 __device__ __forceinline__ float act_fast(int act, float z) {
   if (act == ACT_RELU) return z > 0.f ? z : 0.f;
   if (act == ACT_SILU) return z * sigmoid_fast(z);
+  if (act == ACT_TANH) {  // (1 - e) / (1 + e), e = exp(-2 |z|) <= 1: no overflow, the sign copied back
+    const float e = __builtin_amdgcn_exp2f(-2.88539008177792681f * fabsf(z));
+    return copysignf((1.f - e) * __builtin_amdgcn_rcpf(1.f + e), z);
+  }
   return z;
 }
 __device__ __forceinline__ float act_grad_fast(int act, float zy) {
@@ -69,6 +73,7 @@ __device__ __forceinline__ float act_grad_fast(int act, float zy) {
     const float sg = sigmoid_fast(zy);
     return sg * (1.f + zy * (1.f - sg));
   }
+  if (act == ACT_TANH) return 1.f - zy * zy;
   return 1.f;
 }
 

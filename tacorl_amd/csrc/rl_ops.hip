@@ -729,6 +729,80 @@ extern "C" int tacorl_actor_head_bwd(const float* head, int ld_head, const float
   return LAUNCH_OK();
 }
 
+// Behaviour cloning of a tanh-Gaussian (+ discrete gripper) policy head (relay_imitation_learning.py:129-131, 169-171):
+//   loss = -(1/M) sum_m Actor.log_prob(target_m)   (actor.py:140-156), d_head = grad_scale * d loss / d head,
+// forward and backward in one launch.  Per element this is actor_head_bwd_kernel's `value` term, operation for
+// operation (clamp to +-0.999, atanh as 0.5 log((1+v)/(1-v)), normal_lp + tanh_corr, c d/var, c (d^2/var - 1), the clamp
+// masks, the gripper's onehot - softmax): the two kernels share head_stats / normal_lp / tanh_corr.
+// One workgroup; a wave takes 64 / G rows at a time (G = the power of two >= Ac, lanes of a group = action dims; Ac > 64:
+// a lane strides over the dims), the row's log-probability is a shuffle reduction over the group's lanes.  The mean is
+// summed in two fixed-order stages - a wave's rows in row order, then the 16 wave partials in wave order - so the logged
+// loss does not depend on scheduling (no float atomics).
+__global__ __launch_bounds__(1024) void tanh_normal_nll_kernel(
+    const float* __restrict__ head, int ld_head, const float* __restrict__ target, int ld_target, int M, int Ac,
+    int has_grip, float grad_scale, float* __restrict__ d_head, float* loss_out) {
+  __shared__ float sh[16];
+  int G = 1;
+  while (G < Ac && G < 64) G <<= 1;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, rpw = 64 / G;  // rows per wave and pass
+  const int sub = lane / G, j0 = lane - sub * G;
+  const float c = -grad_scale / (float)M;
+  float nll = 0.f;  // (lane 0 of every group: the sum over this group's rows)
+  for (int m0 = wave * rpw; m0 < M; m0 += 16 * rpw) {  // (uniform trip count per wave: the shuffles below are wave-wide)
+    const int m = m0 + sub;
+    const bool on = m < M;
+    const float* h = head + (long)(on ? m : 0) * ld_head;
+    const float* tv = target + (long)(on ? m : 0) * ld_target;
+    float* dh = d_head + (long)(on ? m : 0) * ld_head;
+    float lp = 0.f;
+    if (on)
+      for (int j = j0; j < Ac; j += G) {
+        float mu, sd;
+        head_stats(h, j, Ac, mu, sd);
+        float v = fminf(fmaxf(tv[j], -0.999f), 0.999f);
+        const float zd = 0.5f * logf(fmaxf(1.f + v, 1e-6f) / fmaxf(1.f - v, 1e-6f));
+        const float d = zd - mu, var = sd * sd;
+        lp += normal_lp(zd, mu, sd) + tanh_corr(zd);
+        const float gm = c * (d / var), gs = c * ((d * d) / var - 1.f);
+        const float mr = h[j], lr = h[Ac + j];
+        dh[j] = (mr >= -9.f && mr <= 9.f) ? gm : 0.f;
+        dh[Ac + j] = (lr >= -5.f && lr <= 2.f) ? gs : 0.f;
+      }
+    for (int o = G >> 1; o > 0; o >>= 1) lp += __shfl_xor(lp, o, 64);  // (stays inside the aligned group of G lanes)
+    if (on && j0 == 0) {
+      if (has_grip) {
+        const float l0 = h[2 * Ac], l1 = h[2 * Ac + 1], mx = fmaxf(l0, l1);
+        const float e0 = expf(l0 - mx), e1 = expf(l1 - mx), p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
+        const int vi = (int)(tv[Ac] / 2.f + 0.5f);
+        dh[2 * Ac] = c * ((vi == 0 ? 1.f : 0.f) - p0);
+        dh[2 * Ac + 1] = c * ((vi == 1 ? 1.f : 0.f) - p1);
+        lp += (vi ? l1 : l0) - (mx + logf(e0 + e1));
+      }
+      nll -= lp;
+    }
+  }
+  // stage 1: the groups of a wave in group order (lane 0 of group s holds its rows' sum)
+  float wsum = 0.f;
+  for (int s = 0; s < rpw; s++) wsum += __shfl(nll, s * G, 64);
+  if (lane == 0) sh[wave] = wsum;
+  __syncthreads();
+  if (threadIdx.x == 0) {  // stage 2: the 16 waves in wave order
+    float t = 0.f;
+    for (int i = 0; i < 16; i++) t += sh[i];
+    loss_out[0] = t / (float)M;
+  }
+}
+extern "C" int tacorl_tanh_normal_nll(const float* head, int ld_head, const float* target, int ld_target, int M, int Ac,
+                                      int has_grip, float grad_scale, float* d_head, float* loss_out,
+                                      tacorl_stream_t stream) {
+  if (M < 1 || Ac < 1 || ld_head < 2 * Ac + (has_grip ? 2 : 0) || ld_target < Ac + (has_grip ? 1 : 0) || !head || !target ||
+      !d_head || !loss_out)
+    return TACORL_EINVAL;
+  hipLaunchKernelGGL(tanh_normal_nll_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, head, ld_head, target, ld_target,
+                     M, Ac, has_grip, grad_scale, d_head, loss_out);
+  return LAUNCH_OK();
+}
+
 // ================================================================= CQL + Bellman
 // q_i: Q outputs for rows [data B | rand nB | cur nB | nxt nB] (sample-major k*B+b).
 // One wave per sample b: the 3n logits live one per lane (3n <= 64), logsumexp / softmax by

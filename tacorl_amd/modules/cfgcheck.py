@@ -92,3 +92,40 @@ def check_action_decoder(cfg, what):
                     free=("n_mixtures", "num_layers", "hidden_size", "out_features", "act_max_bound", "act_min_bound",
                           "policy_rnn_dropout_p", "num_classes", "latent_plan_dim", "rnn_model", "include_goal",
                           "state_dim", "goal_dim", "gripper_alpha", "discrete_gripper"))
+
+
+# ---------------------------------------------------------------- relay imitation learning
+def check_ril_goal_encoder(cfg, what, hidden=256):
+    """The RIL module's goal encoder (config/module/relay_imitation_learning.yaml:12-13): as check_goal_encoder, and
+    `last_layer_activation: Tanh` is honoured here (the MLP kernels' TANH output activation).  Returns the activation name."""
+    cfg = _require(cfg, what, "VisualGoalEncoder",
+                   dict(hidden_size=hidden, activation_function="ReLU", last_layer_activation=("Identity", "Tanh"),
+                        normalize_output=False), free=("in_features", "out_features"))
+    return cfg.get("last_layer_activation", "Identity")
+
+
+def check_ril_policy(cfg, what):
+    """high_level_policy / low_level_policy: an Actor over an MLPPolicy of any depth and width (the two may differ).
+    Returns (policy options, discrete_gripper, action_dim or None)."""
+    cfg = dict(cfg or {})
+    pol = cfg.pop("policy", None) or {}
+    _require(cfg, what, "Actor", {}, free=("discrete_gripper", "state_dim", "goal_dim", "action_dim"))
+    pol = _require(pol, what + ".policy", "MLPPolicy", {}, free=("num_layers", "hidden_dim", "init_w", "input_dim", "action_dim",
+                                                                 "discrete_gripper"))
+    return pol, bool(cfg.get("discrete_gripper", False)), cfg.get("action_dim")
+
+
+def check_ril_modalities(low, high):
+    """Both policies read every camera: each list must be a permutation of the union (the goal encoder takes 32 * |union|
+    inputs and is fed each policy's own concatenation, so nothing else is shape-consistent in the reference either).
+    Returns the union in the low-level policy's order."""
+    low, high = list(low), list(high)
+    if not low or not high:
+        raise ValueError("low_level_policy_modalities and high_level_policy_modalities must both be non-empty")
+    for name, lst in (("low_level_policy_modalities", low), ("high_level_policy_modalities", high)):
+        if len(set(lst)) != len(lst):
+            raise ValueError(f"{name}: a modality is listed twice: {lst}")
+    if set(low) != set(high):
+        raise ValueError(f"the two modality lists must name the same cameras (each a permutation of their union): "
+                         f"low {low}, high {high}")
+    return low

@@ -1,0 +1,151 @@
+"""RelayImitationLearning - drop-in for reference modules/relay_imitation_learning/relay_imitation_learning.py:13-225
+(`experiment=relay_imitation_learning`, the hierarchical behaviour-cloning baseline).
+
+Same constructor kwargs (`_recursive_: False`: sub-configs arrive as dicts), same `training_step / validation_step /
+configure_optimizers` surface, same `state_dict()` keys and logged scalar names; the arithmetic runs in
+tacorl_amd.modules.relay_imitation_learning.engine.RILEngine (HIP kernels).  Select it with
+`module._target_=tacorl_amd.modules.relay_imitation_learning.relay_imitation_learning.RelayImitationLearning`.
+
+The reference optimises automatically (training_step returns the loss, the Trainer steps one Adam); here the Adam step is
+part of training_step's kernels, so the module runs in manual-optimisation mode like the other three and returns the total
+loss for logging only.  `env` is accepted and stored but never built (the reference calls make_env(env) and does not use it
+in the step)."""
+from typing import List
+
+import torch
+
+from ... import dist as _D
+from ...lightning import LightningModuleBase
+from ..common import GraphMixin, ModuleMixin, broadcast_blocks, register_views, to_plain
+from .engine import SLOTS, RILEngine
+
+
+class RelayImitationLearning(GraphMixin, ModuleMixin, LightningModuleBase):
+    def __init__(self, env={}, goal_encoder={}, perceptual_encoder={}, high_level_policy={}, low_level_policy={},
+                 high_level_policy_modalities: List[str] = [], low_level_policy_modalities: List[str] = [],
+                 lr: float = 1e-4, *args, device=None, compute_dtype="f32", image_dtype="f32", world_size=1, **kwargs):
+        super().__init__()
+        self._init_runtime(device, compute_dtype, image_dtype, world_size)
+        self.automatic_optimization = False
+        self.save_hyperparameters()
+        self.env_cfg, self.env = env, None
+        self.goal_encoder_cfg, self.perceptual_encoder_cfg = to_plain(goal_encoder), to_plain(perceptual_encoder)
+        self.high_level_policy_cfg, self.low_level_policy_cfg = to_plain(high_level_policy), to_plain(low_level_policy)
+        self.high_level_policy_modalities = list(high_level_policy_modalities)
+        self.low_level_policy_modalities = list(low_level_policy_modalities)
+        self.lr = lr
+        self.build_networks()
+        if _D.collectives_on(world_size):
+            self.sync_from_rank0()
+
+    # ------------------------------------------------------------------ construction
+    def build_networks(self):
+        from .. import cfgcheck
+        from ...init import init_views_
+
+        union = cfgcheck.check_ril_modalities(self.low_level_policy_modalities, self.high_level_policy_modalities)
+        self.all_modalities = set(union)
+        cfgcheck.check_representation(self.perceptual_encoder_cfg, "perceptual_encoder", union)
+        g = self.goal_encoder_cfg or {}
+        goal_act = cfgcheck.check_ril_goal_encoder(g, "goal_encoder", g.get("hidden_size", 256))
+        goal_out = int(g.get("out_features") or 32)
+        if g.get("in_features") not in (None, 32 * len(union)):
+            raise ValueError(f"goal_encoder.in_features is 32 per camera of the union ({32 * len(union)}), not {g['in_features']}")
+        hp, hdg, hA = cfgcheck.check_ril_policy(self.high_level_policy_cfg, "high_level_policy")
+        lp, ldg, lA = cfgcheck.check_ril_policy(self.low_level_policy_cfg, "low_level_policy")
+        if hdg:
+            raise NotImplementedError("high_level_policy: discrete_gripper - its action is the latent goal, which has no gripper")
+        if hA not in (None, goal_out):
+            raise ValueError(f"high_level_policy.action_dim {hA} must equal goal_encoder.out_features {goal_out}")
+        size = lambda p: (int(p.get("num_layers", 2)), int(p.get("hidden_dim", 256)))  # noqa: E731
+        self.engine = RILEngine(
+            self.low_level_policy_modalities, self.high_level_policy_modalities, None, None, self.dev, lr=self.lr,
+            goal_act=goal_act, goal_hidden=int(g.get("hidden_size", 256)), goal_out=goal_out, high=size(hp), low=size(lp),
+            low_action_dim=int(lA if lA is not None else 16), low_discrete_gripper=ldg, compute=self.compute,
+            img_dtype=self.img_dtype, world_size=self.world_size)
+        init_views_(self.engine.blk.views)
+        self._pv = register_views(self, "", self.engine.blk.views)
+
+    def sync_from_rank0(self):
+        """Broadcast rank 0's parameters and optimiser state (PL's DDP wrap does this for the reference module)."""
+        from ... import ops
+
+        broadcast_blocks([self.engine.blk])
+        ops.touched(self.engine.blk.param)
+
+    def _stepped_blocks(self):
+        return [self.engine.blk.param]
+
+    def _derived_stale(self):
+        return self.engine.packs_stale()
+
+    def _after_replay_touch(self):
+        self.engine.packs_written()
+
+    def named_gradients(self):
+        return dict(self.engine.blk.grad_views)
+
+    # ---------------------------------------------------------------------- stepping
+    def _stage(self, batch, nchw=True):
+        """The four image roles of every camera of the union and the low-level action; fp32 NCHW tensors, or the
+        dataset's uint8 HWC frames (normalised on the GPU, as CQL_Offline._stage)."""
+        e = self.engine
+        first = batch[SLOTS[0]][e.cams[0]]
+        if first.dtype == torch.uint8:
+            nchw = False
+        hw = {c: (tuple(batch[SLOTS[0]][c].shape[-2:]) if nchw else tuple(batch[SLOTS[0]][c].shape[-3:-1])) for c in e.cams}
+        e.ensure_batch(first.shape[0], hw)
+        for c in e.cams:
+            e.load_images(c, [batch[s][c].to(self.dev) for s in SLOTS], nchw=nchw)
+        e.load_action(batch["low_level_action"].to(self.dev))
+
+    def compute_loss(self, batch, stage: str = "train", optimize: bool = True):
+        self._sync_lrs()
+        self._stage(batch)
+        e = self.engine
+
+        def fwd_bwd():
+            e.forward()
+            if optimize:
+                e.backward()
+
+        def opt():
+            if optimize:
+                e.optimizer_step()
+
+        self._run_segments(("ril", e.B, tuple(sorted(e.hw.items())), optimize), [fwd_bwd, opt],
+                           [e.allreduce_grads if optimize else (lambda: None)])
+        self._step_count += 1
+        if self.log_every_n_steps > 1 and self._step_count % self.log_every_n_steps and self.__dict__.get("_last_total") is not None:
+            return self.__dict__["_last_total"]
+        m = e.metrics()
+        for k in ("low_level_loss", "high_level_loss", "total_loss"):
+            self.log(f"{stage}/{k}", m[k], on_step=True, on_epoch=True, sync_dist=True)
+        self.__dict__["_last_total"] = m["total_loss"]
+        return m["total_loss"]
+
+    def training_step(self, batch, batch_idx=0):
+        out = self.compute_loss(batch, stage="train", optimize=True)
+        self._tick_optimizers()
+        return out
+
+    def validation_step(self, batch, batch_idx=0):
+        return self.compute_loss(batch, stage="validation", optimize=False)
+
+    def configure_optimizers(self):
+        """reference :219-225: ONE Adam over every parameter - a BlockAdam over the flat block."""
+        b = self.engine.blk
+        self._optimizers = [self._make_adam("adam", [(b, self._pv, b.views_of(b.m), b.views_of(b.v))], self.lr)]
+        return self._optimizers[0]
+
+    def _sync_lrs(self):
+        """A learning rate edited on the optimiser's param_groups reaches the kernels: it is a launch argument, so a change
+        also drops the captured graphs."""
+        opts = getattr(self, "_optimizers", None)
+        if opts and opts[0].lr != self.engine.hp["lr"]:
+            self.lr = self.engine.hp["lr"] = opts[0].lr
+            self._graphs = {}
+
+    def _set_world_size(self, ws):
+        self.engine.world = ws
+        super()._set_world_size(ws)
