@@ -1,0 +1,172 @@
+"""The perceptual-encoder stage of a training step, stated once for the actor-critic step (engine.py), the relay-imitation
+step (modules/relay_imitation_learning/engine.py) and the PlayLMP step (modules/play_lmp/play_lmp_for_rl.py): image slots,
+which kernels apply, the packed conv weights, which cameras share a launch, and the forward / backward dispatch.
+
+An encoder problem is the 7-tuple (image pointer, parameter block, out, act, images, needs_backward, camera); a parameter
+block is anything with `.param` (the flat fp32 tensor) and `.enc(camera[, flat])` (address of that camera's encoder in it).
+Nothing here computes anything: it decides which entry point of the library runs over which problems.
+"""
+import torch
+
+from . import ops
+from ._lib import BF16, F32, call
+
+EF_MAXP = 16  # problems of one fused forward launch (the kernel's problem table)
+EBW_MAXP = 8  # problems of one fused backward launch sequence
+
+
+def image_flag(img_dtype):
+    return BF16 if img_dtype == torch.bfloat16 else F32
+
+
+# ------------------------------------------------------------------- 1. slot packing
+def pack_slots(X3, slots, B, hw, srcs, nchw, img_dtype):
+    """Images of one camera into slots of its NHWC image buffer X3 (slot i = rows [i*B, (i+1)*B)).  srcs[j] -> slot slots[j]:
+    (B,3,H,W) [nchw] or (B,H,W,3) fp32 device tensors, or the dataset's uint8 (B,H,W,3) frames (ToTensor + Normalize(0.5,
+    0.5) applied by the pack: bit-identical to the host-transformed fp32 route, a quarter of the bytes); strided views with a
+    uniform image pitch (states[:, 0]) are taken as they are.  One vectorised launch for all slots where the alignment allows."""
+    H, W = hw
+    xd, esz, img = image_flag(img_dtype), X3.element_size(), H * W * 3
+    u8 = srcs[0].dtype == torch.uint8
+    jobs = []
+    for i, t in zip(slots, srcs):
+        assert t.is_cuda and t.dtype == (torch.uint8 if u8 else torch.float32) and t[0].is_contiguous() and t.shape[0] == B
+        assert tuple(t.shape[-3:]) == ((H, W, 3) if (u8 or not nchw) else (3, H, W)), (tuple(t.shape), (H, W))
+        pitch = t.stride(0) if t.shape[0] > 1 else img
+        jobs.append((t.data_ptr(), pitch, X3.data_ptr() + i * B * img * esz, B))
+    if u8:
+        if img % 16 or any(j[0] % 16 or j[1] % 16 for j in jobs):
+            raise ValueError("uint8 frames: H*W*3 and the image pitch must be multiples of 16, tensors 16-byte aligned")
+        ops.pack_images_u8_batch(jobs, xd, H, W)
+    elif nchw and (H * W) % 4 == 0 and all(j[0] % 16 == 0 and j[1] % 4 == 0 for j in jobs):
+        ops.pack_images_batch(jobs, xd, H, W)
+    else:
+        for src, pitch, dst, n_ in jobs:
+            call("tacorl_pack_images", src, pitch, int(nchw), dst, xd, n_, 3, H, W, ops.stream())
+
+
+# ------------------------------------------------------------- 2. which kernels apply
+def fused_fwd_ok(hw, compute, img_dtype):
+    """The fused single-launch forward: bf16 images + bf16 MFMA + a templated camera geometry."""
+    return compute == BF16 and img_dtype == torch.bfloat16 and bool(ops.L.lib().tacorl_encoder_fused_supported(*hw))
+
+
+def fused_bwd_ok(hw, compute, img_dtype, n_imgs):
+    """The per-image LDS-resident conv backward over problems of n_imgs images each.  It may exist for fewer geometries than
+    the fused forward; where it does not, the problems that have a backward take the per-layer path."""
+    return fused_fwd_ok(hw, compute, img_dtype) and ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(
+        len(n_imgs), ops.int_array(n_imgs), *hw) > 0
+
+
+def fused_saves(hw, compute, img_dtype, n_imgs):
+    """Does the fused forward leave activations that this backward can read?  (Act format 2 - a geometry of encoder_ring.hip
+    without the LDS-resident backward: the fused launch saves fp32 activations, which the per-layer backward reads.)"""
+    return fused_bwd_ok(hw, compute, img_dtype, n_imgs) or (
+        fused_fwd_ok(hw, compute, img_dtype) and ops.L.lib().tacorl_encoder_fused_act_format(*hw) == 2)
+
+
+# ------------------------------------------------------------ 3. packed conv weights
+class PackedWeights:
+    """Packed conv weights of the fused encoder forward (bf16 MFMA fragments in the kernel's register order), one buffer per
+    (parameter block, camera).
+
+    The validity rule: a packed copy is current while the block's torch version counter (ops.touched) is the one recorded
+    when it was packed.  A step packs the networks its optimiser moves BEHIND its Adam launch, at the end of the step - in
+    the shadow of whatever else still runs there - instead of in front of the encoder forward at the head of the next step's
+    chain; in front of a forward only what something else has written since is packed again (pack_stale), so frozen networks
+    are packed once, not every step.  A captured graph replays that late pack but no python: after a replay the owner records
+    it (written), and before one it asks whether something else wrote the parameters (stale) - then the graph is dropped."""
+
+    def __init__(self, device):
+        self.dev, self.buf, self.ver = device, {}, {}
+
+    def buffer(self, blk, c):
+        if (blk, c) not in self.buf:
+            ops.note_alloc()
+            self.buf[(blk, c)] = torch.empty(ops.L.lib().tacorl_encoder_fused_wpk_bytes(), dtype=torch.uint8, device=self.dev)
+        return self.buf[(blk, c)]
+
+    def pack(self, pairs):
+        """One pack launch over the (block, camera) pairs, whatever their stamps say."""
+        pairs = list(pairs)
+        if not pairs:
+            return
+        call("tacorl_encoder_pack_weights", len(pairs), ops.ptr_array([b.enc(c) for b, c in pairs]),
+             ops.ptr_array([self.buffer(b, c) for b, c in pairs]), ops.stream())
+        for b, c in pairs:
+            self.ver[(b, c)] = b.param._version
+
+    def pack_stale(self, pairs):
+        self.pack([(b, c) for b, c in pairs if self.ver.get((b, c)) != b.param._version])
+
+    def _packed(self, blocks, cams):
+        return [(b, c) for b in blocks for c in cams if (b, c) in self.ver]
+
+    def stale(self, blocks, cams):
+        """Would a replayed step read a packed copy that no longer matches its parameter block?"""
+        return any(self.ver[(b, c)] != b.param._version for b, c in self._packed(blocks, cams))
+
+    def written(self, blocks, cams):
+        """The step's tail launch (eager, or the replayed graph's) has just re-packed these blocks: record it."""
+        for b, c in self._packed(blocks, cams):
+            self.ver[(b, c)] = b.param._version
+
+
+# ---------------------------------------------------------------- 4. geometry grouping
+def geometry_groups(cams, hw, ok, n_problems, limit):
+    """Cameras that share ONE launch (sequence): the cameras of one geometry for which ok(c) holds, when their problems
+    together - n_problems(c) each - fit `limit` (EF_MAXP forward: C4's two 128 x 128 cameras, 7 problems each, are one launch
+    over 5 504 images instead of two over 2 752, one prologue and one tail; EBW_MAXP backward: the conv-backward launches
+    cost ~6-10 us each before their first image); every other camera alone.
+    Two cases no compiled geometry reaches follow the actor-critic engine's rule: cameras with the fused forward but
+    without the LDS-resident backward do not merge (pass the backward's predicate as ok), and a geometry whose cameras do
+    not all fit the limit is not merged in part."""
+    groups, out = {}, []
+    for c in cams:
+        groups.setdefault((tuple(hw[c]), bool(ok(c))), []).append(c)
+    for (_, good), cs in groups.items():
+        out += [cs] if good and sum(n_problems(c) for c in cs) <= limit else [[c] for c in cs]
+    return out
+
+
+# ---------------------------------------------------------------- 5. forward dispatch
+def launch_fused(pr, packs, hw, max_wg=0):
+    """One fused encoder launch over the problems pr (each carries its camera: cameras of one geometry may share a launch)
+    on at most max_wg workgroups (0: one per CU); activations are saved only for the problems a backward follows."""
+    call("tacorl_encoder_fwd_fused_wg", len(pr), ops.ptr_array([x[0] for x in pr]),
+         ops.ptr_array([packs.buffer(x[1], x[6]) for x in pr]), ops.ptr_array([x[1].enc(x[6]) for x in pr]),
+         ops.ptr_array([x[2] for x in pr]), ops.ptr_array([x[3] if x[5] else None for x in pr]),
+         ops.int_array([x[4] for x in pr]), *hw, int(max_wg), ops.stream())
+
+
+def encode(groups, problems, hw, compute, img_dtype, packs, fused, saves, launch, pack_per_camera=True, per_layer_last=False):
+    """Every encoder forward of the camera groups: per group ONE fused launch - launch(first camera, problems) - over the
+    problems it takes, in front of it a pack of what is stale; the per-layer path for the cameras fused(c) does not hold for
+    (fp32 mode, no templated geometry) and for the problems whose backward could not read the fused launch's activations
+    (saves(c) false).  problems(c): the 7-tuples of camera c.
+    The two steps' launch orders are kept as they were measured: pack_per_camera - one pack launch per camera (several
+    blocks) or one per group (one block); per_layer_last - the per-layer launches behind every fused launch, or in line."""
+    def per_layer(pr):
+        for c in dict.fromkeys(x[6] for x in pr):
+            prc = [x for x in pr if x[6] == c]
+            call("tacorl_encoder_fwd", len(prc), ops.ptr_array([x[0] for x in prc]), ops.ptr_array([x[1].enc(c) for x in prc]),
+                 ops.ptr_array([x[2] for x in prc]), ops.ptr_array([x[3] for x in prc]), ops.int_array([x[4] for x in prc]),
+                 *hw[c], image_flag(img_dtype), compute, ops.stream())
+
+    slow = []
+    for cs in groups:
+        pr = [x for c in cs for x in problems(c)]
+        if fused(cs[0]):
+            unsaved = lambda x: x[5] and not saves(x[6])  # noqa: E731
+            slow += [x for x in pr if unsaved(x)]
+            pr = [x for x in pr if not unsaved(x)]
+            pairs = list(dict.fromkeys((x[1], x[6]) for c in cs for x in pr if x[6] == c))
+            for part in ([[p for p in pairs if p[1] == c] for c in cs] if pack_per_camera else [pairs]):
+                packs.pack_stale(part)
+            launch(cs[0], pr)
+        else:
+            slow += pr
+        if not per_layer_last:
+            per_layer(slow)
+            slow = []
+    per_layer(slow)

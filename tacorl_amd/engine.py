@@ -16,6 +16,7 @@ Random draws are explicit inputs (`noise` dict, reference draw order - SURVEY 8a
 import torch
 
 from . import blocks, ops
+from . import encoder_stage as stage
 from . import dist as D
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, BF16, F32, LOG_SLOTS, call, ptr
 
@@ -151,7 +152,7 @@ class ACEngine:
         # (plus the scalar one for log_alpha, which must be stepped before the actor loss)
         self.arena_extra = []
         self._bind_arena()
-        self.extra_enc, self._wpk = [], {}
+        self.extra_enc, self.packs, self._prepacked = [], stage.PackedWeights(device), False
         self.B = None
         if B:
             self.ensure_batch(B)
@@ -302,32 +303,9 @@ class ACEngine:
     def load_images(self, cam, obs, goal, nxt, nchw=True):
         """obs/goal/nxt: (B,3,H,W) [nchw] or (B,H,W,3) fp32 device tensors (may be strided views with a
         uniform image pitch, e.g. states[:,0]); the images of a role the camera does not have are not read (None)."""
-        H, W = self.hw[cam]
-        xd = BF16 if self.img_dtype == torch.bfloat16 else F32
-        esz, img = self.X3[cam].element_size(), H * W * 3
-        jobs = []
         given = {"obs": obs, "goal": goal, "next": nxt}
-        srcs = [(i, given[s_]) for s_, i in self.slot[cam].items()]  # (slot, images)
-        if srcs[0][1].dtype == torch.uint8:
-            # the dataset's uint8 HWC frames: ToTensor + Normalize(0.5, 0.5) applied by the pack (bit-identical to the
-            # host-transformed fp32 route, a quarter of the bytes)
-            for i, t in srcs:
-                assert t.is_cuda and t.dtype == torch.uint8 and t[0].is_contiguous() and tuple(t.shape[-3:]) == (H, W, 3)
-                pitch = t.stride(0) if t.shape[0] > 1 else img
-                jobs.append((t.data_ptr(), pitch, self.X3[cam].data_ptr() + i * self.B * img * esz, self.B))
-            if img % 16 or any(j[0] % 16 or j[1] % 16 for j in jobs):
-                raise ValueError("uint8 frames: H*W*3 and the image pitch must be multiples of 16, tensors 16-byte aligned")
-            ops.pack_images_u8_batch(jobs, xd, H, W)
-            return
-        for i, t in srcs:
-            assert t.is_cuda and t.dtype == torch.float32 and t[0].is_contiguous()
-            pitch = t.stride(0) if t.shape[0] > 1 else 3 * H * W
-            jobs.append((t.data_ptr(), pitch, self.X3[cam].data_ptr() + i * self.B * img * esz, self.B))
-        if nchw and (H * W) % 4 == 0 and all(j[0] % 16 == 0 and j[1] % 4 == 0 for j in jobs):
-            ops.pack_images_batch(jobs, xd, H, W)  # one vectorised launch for obs / goal / next
-        else:
-            for src, pitch, dst, n_ in jobs:
-                call("tacorl_pack_images", src, pitch, int(nchw), dst, xd, n_, 3, H, W, ops.stream())
+        sl = self.slot[cam]
+        stage.pack_slots(self.X3[cam], list(sl.values()), self.B, self.hw[cam], [given[s_] for s_ in sl], nchw, self.img_dtype)
 
     def load_transition(self, action, reward, done):
         self.action.copy_(action.reshape(self.B, self.A).float())
@@ -347,22 +325,13 @@ class ACEngine:
     EF_SPLIT_BUDGET = 160  # workgroups of the update's own encoder launch in encode_split
 
     def _fused_ok(self, c):
-        if not self.use_fused or self.compute != BF16 or self.img_dtype != torch.bfloat16:
-            return False
-        return bool(ops.L.lib().tacorl_encoder_fused_supported(*self.hw[c]))
+        return self.use_fused and stage.fused_fwd_ok(self.hw[c], self.compute, self.img_dtype)
 
     def _fused_bwd_ok(self, c):
-        """The per-image LDS-resident conv backward may exist for fewer geometries than the fused forward; where it does
-        not, the problems that have a backward take the per-layer forward (fp32 activations)."""
-        return self._fused_ok(c) and ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(
-            3, ops.int_array([self.nbwd[c]] * 3), *self.hw[c]) > 0
+        return self.use_fused and stage.fused_bwd_ok(self.hw[c], self.compute, self.img_dtype, [self.nbwd[c]] * 3)
 
-    def _packed(self, net, c):
-        key = (id(net), c)
-        if key not in self._wpk:
-            ops.note_alloc()
-            self._wpk[key] = torch.empty(ops.L.lib().tacorl_encoder_fused_wpk_bytes(), dtype=torch.uint8, device=self.dev)
-        return self._wpk[key]
+    def _fused_saves(self, c):
+        return self.use_fused and stage.fused_saves(self.hw[c], self.compute, self.img_dtype, [self.nbwd[c]] * 3)
 
     def _all_problems(self, c, which="all"):
         """(image pointer, net, out, act, n_img, needs_backward, camera) of every encoder problem of camera c
@@ -382,86 +351,36 @@ class ACEngine:
         groups = self._fused_groups()
         if not self.extra_enc or len(groups) != 1 or sorted(groups[0]) != sorted(self.enc_cams) or not all(self._fused_bwd_ok(c) for c in self.enc_cams):
             return False
-        cs = groups[0]
-        for which in ("extra", "own"):
-            pr = [x for c in cs for x in self._all_problems(c, which)]
-            for c in cs:
-                self._pack_stale_encoders(c, list({id(x[1]): x[1] for x in pr if x[6] == c}.values()))
-            if which == "own":
-                self._launch_fused(cs[0], pr, max_wg=self.EF_SPLIT_BUDGET)
-            else:
-                self._launch_fused(cs[0], pr)
-                between()
+        self._encode(groups, "extra")
+        between()
+        self._encode(groups, "own", max_wg=self.EF_SPLIT_BUDGET)
         return True
 
-    # Packed conv weights of the fused encoder forward (bf16 MFMA fragments in the kernel's register order).  The pack launch
-    # of the networks the optimiser moves runs BEHIND the Adam launch, at the end of the step (phase_c) - in the shadow of
-    # the action-decoder branch, which ends later - instead of in front of the encoder forward at the head of the next
-    # step's chain; a packed copy counts as current while the block's torch version counter is the one recorded when it was
-    # packed, so in front of a forward only what something else has written since is packed again (_pack_stale_encoders),
-    # and frozen networks (TACORL's LMP encoder) are packed once, not every step.
-    def _pack_versions(self):
-        """(id(net), camera) -> the block's version counter when its packed copy was written."""
-        return self.__dict__.setdefault("_wpk_ver", {})
-
-    def _pack_encoders(self, c, nets):
-        if not nets:
-            return
-        call("tacorl_encoder_pack_weights", len(nets), ops.ptr_array([n_.enc(c) for n_ in nets]),
-             ops.ptr_array([self._packed(n_, c) for n_ in nets]), ops.stream())
-        vers = self._pack_versions()
-        for n_ in nets:
-            vers[(id(n_), c)] = n_.param._version
-
-    def _pack_stale_encoders(self, c, nets):
-        vers = self._pack_versions()
-        self._pack_encoders(c, [n_ for n_ in nets if vers.get((id(n_), c)) != n_.param._version])
-
+    # The packed conv weights of the fused forward (stage.PackedWeights states the rule): the five networks the optimiser
+    # moves are packed BEHIND the Adam launch (phase_c) - in the shadow of the action-decoder branch, which ends later -
+    # and the frozen extra networks (TACORL's LMP encoder) once, in front of the first forward that reads them.
     def _late_pack_nets(self):
         return [self.actor, self.q1, self.q2, self.tq1, self.tq2]
 
     def packs_stale(self):
-        """Would a replayed step read a packed copy that no longer matches its parameter block?  (Every network of the
-        step's encoder launch: the optimiser's ones AND the extra, frozen ones.)"""
-        if not getattr(self, "_wpk_ver", None):
-            return False
-        nets = {id(n_): n_ for n_ in self._late_pack_nets()}
-        nets.update({id(x["net"]): x["net"] for x in self.extra_enc})
-        return any(self._wpk_ver.get((i, c), n_.param._version) != n_.param._version
-                   for i, n_ in nets.items() for c in self.enc_cams if (i, c) in self._wpk_ver)
+        """(Every network of the step's encoder launch: the optimiser's ones AND the extra, frozen ones.)"""
+        return self.packs.stale(self._late_pack_nets() + [x["net"] for x in self.extra_enc], self.enc_cams)
 
     def packs_written(self):
-        """The step's tail launch (eager, or the replayed graph's) has just re-packed the optimiser's networks: record it."""
-        vers = getattr(self, "_wpk_ver", None)
-        if vers:
-            for n_ in self._late_pack_nets():
-                for c in self.enc_cams:
-                    if (id(n_), c) in vers:
-                        vers[(id(n_), c)] = n_.param._version
+        self.packs.written(self._late_pack_nets(), self.enc_cams)
 
     def _launch_fused(self, c, pr, max_wg=0):
-        """One fused encoder launch over the problems pr (each carries its camera, x[6]: cameras of one geometry may share a
-        launch) on at most max_wg workgroups (0: one per CU)."""
-        H, W = self.hw[c]
-        call("tacorl_encoder_fwd_fused_wg", len(pr), ops.ptr_array([x[0] for x in pr]),
-             ops.ptr_array([self._packed(x[1], x[6]) for x in pr]), ops.ptr_array([x[1].enc(x[6]) for x in pr]),
-             ops.ptr_array([x[2] for x in pr]), ops.ptr_array([x[3] if x[5] else None for x in pr]),
-             ops.int_array([x[4] for x in pr]), H, W, int(max_wg), ops.stream())
+        """One fused encoder launch over the problems pr, cameras of camera c's geometry (bench.py times the step's fused
+        launches by replacing this method on the instance)."""
+        stage.launch_fused(pr, self.packs, self.hw[c], max_wg)
 
     def _fused_groups(self):
-        """Cameras whose fused encoder problems share ONE launch: the cameras of one geometry when their problems fit the
-        launch's table (round 5; C4: two 128 x 128 cameras, 7 problems each - one launch over 5 504 images instead of two over
-        2 752: one prologue, one tail); every other fused camera alone."""
-        groups, out = {}, []
-        for c in self.enc_cams:
-            if self._fused_ok(c):
-                groups.setdefault((tuple(self.hw[c]), bool(self._fused_bwd_ok(c))), []).append(c)
-        for (_, bwd_ok), cs in groups.items():
-            if bwd_ok and len(cs) > 1 and sum(len(self._all_problems(c)) for c in cs) <= 16:
-                out.append(cs)
-            else:
-                out += [[c] for c in cs]
-        return out
+        """Cameras whose fused encoder problems share ONE launch (stage.geometry_groups); cameras without the fused forward
+        are in no group."""
+        return [cs for cs in self._camera_groups(stage.EF_MAXP, lambda c: len(self._all_problems(c))) if self._fused_ok(cs[0])]
+
+    def _camera_groups(self, limit, n_problems):
+        return stage.geometry_groups(self.enc_cams, self.hw, self._fused_bwd_ok, n_problems, limit)
 
     def encode_fused_only(self):
         """Just the fused encoder launch(es) of the step (bench roofline probe).  Returns images per step."""
@@ -472,40 +391,15 @@ class ACEngine:
             n_total += sum(x[4] for x in pr)
         return n_total
 
+    def _encode(self, groups, which, max_wg=0):
+        stage.encode(groups, lambda c: self._all_problems(c, which), self.hw, self.compute, self.img_dtype, self.packs,
+                     self._fused_ok, self._fused_saves, lambda c, pr: self._launch_fused(c, pr, max_wg))
+
     def _encode_all(self):
-        """Every encoder forward of the step: ONE fused launch per camera (27*B images at TACORL shapes:
+        """Every encoder forward of the step: ONE fused launch per camera group (27*B images at TACORL shapes:
         frozen LMP window, actor(obs, goal, next), q1, q2 and both targets), activations saved only for the
         problems that have a backward; the per-layer path covers fp32 mode / images too large for LDS."""
-        xd = BF16 if self.img_dtype == torch.bfloat16 else F32
-        merged = {c: cs for cs in self._fused_groups() if len(cs) > 1 for c in cs}
-        for c in self.enc_cams:
-            H, W = self.hw[c]
-            pr = self._all_problems(c)
-            if c in merged:
-                if merged[c][0] != c:
-                    continue  # (launched with the group's first camera)
-                allp = []
-                for cc in merged[c]:
-                    prc = self._all_problems(cc)
-                    self._pack_stale_encoders(cc, list({id(x[1]): x[1] for x in prc}.values()))
-                    allp += prc
-                self._launch_fused(c, allp)
-                continue
-            if self._fused_ok(c):
-                # (act format 2 - a geometry of encoder_ring.hip without the LDS-resident backward: the fused launch saves fp32
-                # activations, which the per-layer backward reads)
-                saves = self._fused_bwd_ok(c) or ops.L.lib().tacorl_encoder_fused_act_format(H, W) == 2
-                slow = [] if saves else [x for x in pr if x[5]]
-                pr = [x for x in pr if not (slow and x[5])]
-                nets = {id(x[1]): x[1] for x in pr}
-                self._pack_stale_encoders(c, list(nets.values()))
-                self._launch_fused(c, pr)
-                pr = slow
-            if pr:
-                call("tacorl_encoder_fwd", len(pr), ops.ptr_array([x[0] for x in pr]),
-                     ops.ptr_array([x[1].enc(c) for x in pr]), ops.ptr_array([x[2] for x in pr]),
-                     ops.ptr_array([x[3] for x in pr]), ops.int_array([x[4] for x in pr]), H, W, xd, self.compute,
-                     ops.stream())
+        self._encode(self._camera_groups(stage.EF_MAXP, lambda c: len(self._all_problems(c))), "all")
 
     def _refresh_bf16(self):
         """bf16 copies of the five networks' MLP weights, the fused MLP kernels' MFMA operand (one launch, every step); the
@@ -541,15 +435,11 @@ class ACEngine:
             ops.mlp_bwd_fused_pack(params, M, dims, "mlp_bwdf_" + tag, self.dev)
         nets = [self.actor, self.q1, self.q2]
         for cs in self._ebw_sequences():
-            c = cs[0]
-            if self._fused_bwd_ok(c):
-                H, W = self.hw[c]
-                np_ = 3 * len(cs)
-                n3 = ops.int_array([self.nbwd[cc] for cc in cs for _ in nets])
-                nb = ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(np_, n3, H, W)
-                ws = ops.workspace(nb, self.dev, "enc_bwd_fused_" + "+".join(cs))
-                call("tacorl_encoder_bwd_fused_pack", np_, ops.ptr_array([x.enc(cc) for cc in cs for x in nets]), n3, H, W, ptr(ws),
-                     ws.numel(), ops.stream())
+            ws, n3 = self._ebw_workspace(cs)
+            if ws is not None:
+                H, W = self.hw[cs[0]]
+                call("tacorl_encoder_bwd_fused_pack", len(n3), ops.ptr_array([x.enc(cc) for cc in cs for x in nets]), ops.int_array(n3),
+                     H, W, ptr(ws), ws.numel(), ops.stream())
         self._prepacked = True
 
     # Gathered MLP inputs (round 5): the concatenations in front of the goal encoders, the policy head and the Q heads are
@@ -790,20 +680,8 @@ class ACEngine:
             cache[tag] = ops.mlp_lean_ok(n, dims, ldx, ldo, ldd, self.compute) and ops.mlp_bwd_fused_ok(n, dims, ldo, ldd, self.compute)
         return cache[tag]
 
-    def _mlp_backward(self, tag, xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts):
-        """MLP backward.  bf16 mode: the input-gradient chain as ONE launch, the weight gradients as one launch in line
-        behind it (on side streams of their own - only Adam needs them - a third set of concurrent launches beside the
-        action-decoder branch's chip-wide GEMMs cost the chain more than their kernels' time: 0.8801 -> 0.8682 ms in line,
-        round 3).  Otherwise: the per-layer path."""
-        n = len(xs)
-        if not ops.mlp_bwd_fused_ok(n, dims, ldo, ldd, self.compute):
-            ops.mlp_bwd(xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, self.compute,
-                        ws_tag="mlp_bwd_" + tag)
-            return
-        ops.mlp_bwd_fused_dgrad(params, acts_buf, d_outs, ldo, d_xs, ldd, M, dims, acts, "mlp_bwdf_" + tag,
-                                prepacked=getattr(self, "_prepacked", False), lean=self._lean(tag))
-        if any(g is not None for g in grads):
-            ops.mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, "mlp_bwdf_" + tag, lean=self._lean(tag))
+    def _mlp_backward(self, tag, *sites):
+        ops.mlp_backward(("mlp_bwd_" + tag, "mlp_bwdf_" + tag), *sites, self.compute, prepacked=self._prepacked, lean=self._lean(tag))
 
     def _actor_backward(self, bc_phase, head_cur, q1p, q2p, gs):
         B, A, Ac, nz = self.B, self.A, self.Ac, self.noise
@@ -827,18 +705,16 @@ class ACEngine:
                            self.actor.head_acts)
 
     def _ebw_sequences(self):
-        """Camera groups that share one conv-backward launch sequence: the cameras of one (fused-backward) geometry, at
-        most 8 problems (3 networks per camera); everything else one camera at a time."""
-        groups = {}
-        for c in self.enc_cams:
-            groups.setdefault((tuple(self.hw[c]), bool(self._fused_bwd_ok(c))), []).append(c)
-        seqs = []
-        for (_, ok), cs in groups.items():
-            if ok and 3 * len(cs) <= 8:
-                seqs.append(cs)
-            else:
-                seqs += [[c] for c in cs]
-        return seqs
+        """Camera groups that share one conv-backward launch sequence (3 networks per camera; C4: both cameras 128 x 128 -> one
+        6-problem sequence instead of two 3-problem ones)."""
+        return self._camera_groups(stage.EBW_MAXP, lambda c: 3)
+
+    def _ebw_workspace(self, cs):
+        """(scratch buffer of the group's fused backward - None where it takes the per-layer path -, images per problem)"""
+        n3 = [self.nbwd[cc] for cc in cs for _ in range(3)]
+        if not self._fused_bwd_ok(cs[0]):
+            return None, n3
+        return ops.encoder_bwd_fused_workspace(n3, *self.hw[cs[0]], self.dev, "enc_bwd_fused_" + "+".join(cs)), n3
 
     def _encoders_backward(self):
         """Goal encoders (3 nets, one batch), then the three encoders (actor(obs, goal), q1, q2)."""
@@ -861,40 +737,29 @@ class ACEngine:
                     if "goal" in rows:
                         ops.copy_cols(self.dgin[k], 32 * self.goal_cams.index(c), self.G, self.enc_dout[(ek[k], c)], rows["goal"] * 32,
                                       32, B, 32)
-        # cameras of one geometry share a launch sequence (round 5; C4: both cameras 128 x 128 -> one 6-problem sequence
-        # instead of two 3-problem ones - the conv-backward launches cost ~6-10 us each before their first image)
         for cs in self._ebw_sequences():
-            c = cs[0]
-            H, W = self.hw[c]
-            imgs = [self._img_ptr(cc, 0) for cc in cs for _ in ks]
-            ops_n = [self.nbwd[cc] for cc in cs for _ in ks]
-            pa = [ops.ptr_array(imgs), ops.ptr_array([nets[k].enc(cc) for cc in cs for k in ks]),
-                  ops.ptr_array([self.enc_act[(ek[k], cc)] for cc in cs for k in ks]),
-                  ops.ptr_array([self.enc_dout[(ek[k], cc)] for cc in cs for k in ks]),
-                  ops.ptr_array([nets[k].enc(cc, nets[k].grad) for cc in cs for k in ks]), ops.int_array(ops_n), H, W]
-            np_ = 3 * len(cs)
-            if self._fused_bwd_ok(c):  # per-image LDS-resident conv backward (encoder_bwd_fused.hip)
-                nb = ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(np_, ops.int_array(ops_n), H, W)
-                ws = ops.workspace(nb, self.dev, "enc_bwd_fused_" + "+".join(cs))
-                pk = int(getattr(self, "_prepacked", False))
-                img_p, par_p, act_p, dout_p, grad_p, n_p = pa[:6]
-                # dependent chain: FC-tail input gradients (one launch) -> soft-argmax + conv backward
-                call("tacorl_encoder_bwd_fused_head", np_, par_p, act_p, dout_p, n_p, H, W, pk, ptr(ws), ws.numel(), ops.stream())
-                call("tacorl_encoder_bwd_fused_conv", np_, img_p, par_p, act_p, grad_p, n_p, H, W, 0, pk, ptr(ws), ws.numel(),
-                     ops.stream())
-                # FC weight gradients last and in line: on a side branch they ran beside the conv-backward
-                # kernels, whose 255 one-per-CU workgroups then no longer fit in one round (+0.13 ms/step)
-                call("tacorl_encoder_bwd_fused_fc_wgrad", np_, act_p, dout_p, grad_p, n_p, H, W, 0, ptr(ws), ws.numel(),
-                     ops.stream())
+            H, W = self.hw[cs[0]]
+            pairs = [(nets[k], ek[k], cc) for cc in cs for k in ks]
+            imgs = [self._img_ptr(cc, 0) for _, _, cc in pairs]
+            acts, douts = [self.enc_act[(e_, cc)] for _, e_, cc in pairs], [self.enc_dout[(e_, cc)] for _, e_, cc in pairs]
+            params, grads = [n_.enc(cc) for n_, _, cc in pairs], [n_.enc(cc, n_.grad) for n_, _, cc in pairs]
+            ws, n3 = self._ebw_workspace(cs)
+            if ws is None:
+                ops.encoder_bwd(imgs, params, acts, douts, grads, H, W, self.compute, n=n3, xd=stage.image_flag(self.img_dtype),
+                                device=self.dev)
                 continue
-            assert len(cs) == 1
-            nb = ops.L.lib().tacorl_encoder_bwd_ws_bytes(3, ops.int_array(ops_n), H, W)
-            ws = ops.workspace(nb, self.dev, "enc_bwd")
-            call("tacorl_encoder_bwd", 3, ops.ptr_array(imgs), ops.ptr_array([nets[k].enc(c) for k in ks]),
-                 ops.ptr_array([self.enc_act[(ek[k], c)] for k in ks]),
-                 ops.ptr_array([self.enc_dout[(ek[k], c)] for k in ks]),
-                 ops.ptr_array([nets[k].enc(c, nets[k].grad) for k in ks]), ops.int_array(ops_n), H, W,
-                 BF16 if self.img_dtype == torch.bfloat16 else F32, self.compute, 0, ptr(ws), ws.numel(), ops.stream())
+            # per-image LDS-resident conv backward (encoder_bwd_fused.hip) as three calls
+            np_, pk = len(pairs), int(self._prepacked)
+            par_p, act_p, dout_p, grad_p, n_p = (ops.ptr_array(params), ops.ptr_array(acts), ops.ptr_array(douts), ops.ptr_array(grads),
+                                                 ops.int_array(n3))
+            # dependent chain: FC-tail input gradients (one launch) -> soft-argmax + conv backward
+            call("tacorl_encoder_bwd_fused_head", np_, par_p, act_p, dout_p, n_p, H, W, pk, ptr(ws), ws.numel(), ops.stream())
+            call("tacorl_encoder_bwd_fused_conv", np_, ops.ptr_array(imgs), par_p, act_p, grad_p, n_p, H, W, 0, pk, ptr(ws), ws.numel(),
+                 ops.stream())
+            # FC weight gradients last and in line: on a side branch they ran beside the conv-backward
+            # kernels, whose 255 one-per-CU workgroups then no longer fit in one round (+0.13 ms/step)
+            call("tacorl_encoder_bwd_fused_fc_wgrad", np_, act_p, dout_p, grad_p, n_p, H, W, 0, ptr(ws), ws.numel(),
+                 ops.stream())
 
     def phase_c(self, optimize=True):
         """Optimiser steps (grads were all taken on the pre-step graph, as in the reference)."""
@@ -906,9 +771,9 @@ class ACEngine:
             for q, t in ((self.q1, self.tq1), (self.q2, self.tq2)):
                 items.append((q.param, q.grad, q.m, q.v, hp["critic_lr"], hp["clip"], q.step, t.param, hp["tau"]))
             ops.adam_step_batch(items)  # two launches for all blocks
-            for c in self.enc_cams:  # (the fused encoder forward's packed conv weights: see _pack_encoders)
+            for c in self.enc_cams:  # (the fused encoder forward's packed conv weights, behind Adam: stage.PackedWeights)
                 if self._fused_ok(c):
-                    self._pack_encoders(c, self._late_pack_nets())
+                    self.packs.pack([(n_, c) for n_ in self._late_pack_nets()])
         ops.mark("c:adam")
 
     def _allreduce(self, tensors):

@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from ... import _lib
 from ... import dist as _D
+from ... import encoder_stage as stage
 from ..._lib import ACT_NONE, ACT_SILU
 from ...engine import NetBlock
 from ...init import init_views_
@@ -74,6 +75,8 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         parts = [("actor.policy.fc_mean", A), ("actor.policy.fc_log_std", A)]
         self.net = NetBlock(cams, cams, pdims, [ACT_SILU] * self.policy_layers + [ACT_NONE], pn, self.dev,
                             head_parts=parts, hidden=self.hidden)
+        # (packed conv weights of the fused encoder forward: this step packs them in FRONT of its forward, every step)
+        self.enc_packs = stage.PackedWeights(self.dev)
         adc = cfgcheck.check_action_decoder(self.ad_cfg, "action_decoder")
         adc["state_dim"] = 32 * len(self.action_decoder_modalities)
         adc["goal_dim"] = 32 * len(cams)
@@ -375,16 +378,12 @@ def _playlmp_fwd_bwd(self, B, T, hw, acts, gs):
     ops.mark("start")
     for j, c in enumerate(cams):
         H, W = hw[c]
-        fused = (cd == BF16 and xd == BF16 and bool(ops.L.lib().tacorl_encoder_fused_supported(H, W))
-                 and ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(1, ops.int_array([R]), H, W) > 0)  # forward and backward
-        if fused:  # one launch for the whole encoder, activations saved for the backward (encoder_fused.hip)
-            if getattr(self, "_wpk", None) is None:
-                self._wpk = {}
-            if c not in self._wpk:
-                ops.note_alloc()
-                self._wpk[c] = torch.empty(ops.L.lib().tacorl_encoder_fused_wpk_bytes(), dtype=torch.uint8, device=self.dev)
-            call("tacorl_encoder_pack_weights", 1, ops.ptr_array([net.enc(c)]), ops.ptr_array([self._wpk[c]]), ops.stream())
-            call("tacorl_encoder_fwd_fused", 1, ops.ptr_array([self.frames[c]]), ops.ptr_array([self._wpk[c]]),
+        # (the fused forward only where the LDS-resident backward follows it: one predicate for forward and backward)
+        if stage.fused_bwd_ok((H, W), cd, self.img_dtype, [R]):
+            # one launch for the whole encoder, activations saved for the backward (encoder_fused.hip); the pack in front of
+            # it is unconditional - part of the captured step, whatever the version stamps say
+            self.enc_packs.pack([(net, c)])
+            call("tacorl_encoder_fwd_fused", 1, ops.ptr_array([self.frames[c]]), ops.ptr_array([self.enc_packs.buffer(net, c)]),
                  ops.ptr_array([net.enc(c)]), ops.ptr_array([self.f_out[c]]), ops.ptr_array([self.f_act[c]]),
                  ops.int_array([R]), H, W, ops.stream())
         else:
@@ -505,10 +504,8 @@ def _playlmp_fwd_bwd(self, B, T, hw, acts, gs):
         H, W = hw[c]
         if not one:
             ops.copy_cols(self.d_emb, 32 * j, Ec, self.f_dout[c], 0, 32, R, 32)
-        fused = (cd == BF16 and xd == BF16 and bool(ops.L.lib().tacorl_encoder_fused_supported(H, W))
-                 and ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(1, ops.int_array([R]), H, W) > 0)  # forward and backward
         ops.encoder_bwd([self.frames[c]], [net.enc(c)], [self.f_act[c]], [self.f_dout[c]], [net.enc(c, net.grad)], H, W, cd,
-                        fused=fused)
+                        fused=stage.fused_bwd_ok((H, W), cd, self.img_dtype, [R]))
     ops.mark("enc:bwd")
     main.wait_stream(s_wg)
     main.wait_stream(s_rand)

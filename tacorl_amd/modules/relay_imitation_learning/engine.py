@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from ... import blocks, ops
+from ... import encoder_stage as stage
 from ... import dist as D
 from ..._lib import ACT_NONE, ACT_RELU, ACT_SILU, ACT_TANH, BF16, F32, call, ptr
 
@@ -103,7 +104,7 @@ class RILEngine:
         if self.dg:
             parts["low"].append(("gripper_action", 2))
         self.blk = RILBlock(self.cams, self.genc_dims, self.pol_dims, parts, device)
-        self._wpk, self._wpk_ver = {}, {}
+        self.packs = stage.PackedWeights(device)
         self.B, self.hw = None, dict(hw or {})
         if B:
             self.ensure_batch(B)
@@ -155,25 +156,7 @@ class RILEngine:
     def load_images(self, cam, imgs, nchw=True):
         """imgs: the four slots' images in SLOTS order, each (B,3,H,W) fp32 [nchw], (B,H,W,3) fp32, or the dataset's
         uint8 (B,H,W,3) frames (ToTensor + Normalize(0.5, 0.5) applied by the pack, as ACEngine.load_images)."""
-        H, W = self.hw[cam]
-        xd = BF16 if self.img_dtype == torch.bfloat16 else F32
-        esz, img = self.X3[cam].element_size(), H * W * 3
-        u8 = imgs[0].dtype == torch.uint8
-        jobs = []
-        for i, t in enumerate(imgs):
-            assert t.is_cuda and t.dtype == (torch.uint8 if u8 else torch.float32) and t[0].is_contiguous() and t.shape[0] == self.B
-            assert tuple(t.shape[-3:]) == ((H, W, 3) if (u8 or not nchw) else (3, H, W)), (tuple(t.shape), (H, W))
-            pitch = t.stride(0) if t.shape[0] > 1 else img
-            jobs.append((t.data_ptr(), pitch, self.X3[cam].data_ptr() + i * self.B * img * esz, self.B))
-        if u8:
-            if img % 16 or any(j[0] % 16 or j[1] % 16 for j in jobs):
-                raise ValueError("uint8 frames: H*W*3 and the image pitch must be multiples of 16, tensors 16-byte aligned")
-            ops.pack_images_u8_batch(jobs, xd, H, W)
-        elif nchw and (H * W) % 4 == 0 and all(j[0] % 16 == 0 and j[1] % 4 == 0 for j in jobs):
-            ops.pack_images_batch(jobs, xd, H, W)
-        else:
-            for src, pitch, dst, n_ in jobs:
-                call("tacorl_pack_images", src, pitch, int(nchw), dst, xd, n_, 3, H, W, ops.stream())
+        stage.pack_slots(self.X3[cam], range(len(SLOTS)), self.B, self.hw[cam], imgs, nchw, self.img_dtype)
 
     def load_action(self, action):
         self.action.copy_(action.reshape(self.B, self.A_low).float())
@@ -184,102 +167,41 @@ class RILEngine:
         return self.X3[cam].data_ptr() + first_row * H * W * 3 * self.X3[cam].element_size()
 
     def _fused_ok(self, c):
-        if self.compute != BF16 or self.img_dtype != torch.bfloat16:
-            return False
-        return bool(ops.L.lib().tacorl_encoder_fused_supported(*self.hw[c]))
+        return stage.fused_fwd_ok(self.hw[c], self.compute, self.img_dtype)
 
     def _fused_bwd_ok(self, c):
-        return self._fused_ok(c) and ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(
-            1, ops.int_array([N_GRAD_SLOTS * self.B]), *self.hw[c]) > 0
+        return stage.fused_bwd_ok(self.hw[c], self.compute, self.img_dtype, [N_GRAD_SLOTS * self.B])
 
     def _fused_saves(self, c):
-        """Does the fused forward leave activations a backward of this geometry can read?"""
-        return self._fused_bwd_ok(c) or ops.L.lib().tacorl_encoder_fused_act_format(*self.hw[c]) == 2
-
-    def _geometry_groups(self, pred, limit):
-        """Cameras of one geometry for which pred holds share a launch (at most `limit` cameras); the others go alone."""
-        groups, out = {}, []
-        for c in self.cams:
-            groups.setdefault((tuple(self.hw[c]), bool(pred(c))), []).append(c)
-        for (_, ok), cs in groups.items():
-            out += [cs[i: i + limit] for i in range(0, len(cs), limit)] if ok else [[c] for c in cs]
-        return out
-
-    def _packed(self, c):
-        if c not in self._wpk:
-            ops.note_alloc()
-            self._wpk[c] = torch.empty(ops.L.lib().tacorl_encoder_fused_wpk_bytes(), dtype=torch.uint8, device=self.dev)
-        return self._wpk[c]
-
-    def _pack_encoders(self, cams):
-        """Packed conv weights of the fused encoder forward: ONE copy per camera (a single network)."""
-        cams = list(cams)
-        if not cams:
-            return
-        call("tacorl_encoder_pack_weights", len(cams), ops.ptr_array([self.blk.enc(c) for c in cams]),
-             ops.ptr_array([self._packed(c) for c in cams]), ops.stream())
-        for c in cams:
-            self._wpk_ver[c] = self.blk.param._version
+        return stage.fused_saves(self.hw[c], self.compute, self.img_dtype, [N_GRAD_SLOTS * self.B])
 
     def packs_stale(self):
-        return any(v != self.blk.param._version for v in self._wpk_ver.values())
+        return self.packs.stale([self.blk], self.cams)
 
     def packs_written(self):
-        for c in self._wpk_ver:
-            self._wpk_ver[c] = self.blk.param._version
+        self.packs.written([self.blk], self.cams)
 
     def _encode(self):
         """4*B images per camera through the one encoder: a fused launch per geometry group where it applies (activations
-        saved for the first 3*B images only), the per-layer path otherwise."""
-        xd = BF16 if self.img_dtype == torch.bfloat16 else F32
-        slow = []  # (camera, first row, images, activation buffer) for the per-layer forward
-        for cs in self._geometry_groups(self._fused_ok, 8):
-            if not self._fused_ok(cs[0]):
-                slow += [(cs[0], r0, n, self.enc_act[cs[0]] if save else self.enc_act_t[cs[0]]) for r0, n, save in self.enc_problems(cs[0])]
-                continue
-            pr = []
-            for c in cs:
-                for r0, n, save in self.enc_problems(c):
-                    if save and not self._fused_saves(c):
-                        slow.append((c, r0, n, self.enc_act[c]))  # its backward reads the per-layer forward's activations
-                    else:
-                        pr.append((c, r0, n, self.enc_act[c] if save else None))
-            self._pack_encoders([c for c in cs if self._wpk_ver.get(c) != self.blk.param._version])
-            H, W = self.hw[cs[0]]
-            call("tacorl_encoder_fwd_fused_wg", len(pr), ops.ptr_array([self._img_ptr(c, r0) for c, r0, _, _ in pr]),
-                 ops.ptr_array([self._packed(c) for c, _, _, _ in pr]), ops.ptr_array([self.blk.enc(c) for c, _, _, _ in pr]),
-                 ops.ptr_array([self.enc_out[c].data_ptr() + 4 * 32 * r0 for c, r0, _, _ in pr]),
-                 ops.ptr_array([a for _, _, _, a in pr]), ops.int_array([n for _, _, n, _ in pr]), H, W, 0, ops.stream())
-        for c in self.cams:
-            pr = [x for x in slow if x[0] == c]
-            if pr:
-                H, W = self.hw[c]
-                call("tacorl_encoder_fwd", len(pr), ops.ptr_array([self._img_ptr(c, r0) for _, r0, _, _ in pr]),
-                     ops.ptr_array([self.blk.enc(c)] * len(pr)),
-                     ops.ptr_array([self.enc_out[c].data_ptr() + 4 * 32 * r0 for _, r0, _, _ in pr]),
-                     ops.ptr_array([a for _, _, _, a in pr]), ops.int_array([n for _, _, n, _ in pr]), H, W, xd, self.compute,
-                     ops.stream())
+        saved for the first 3*B images only), the per-layer path otherwise - behind every fused launch.  ONE packed copy of
+        the conv weights per camera (a single network): one pack launch per group."""
+        def problems(c):
+            return [(self._img_ptr(c, r0), self.blk, self.enc_out[c].data_ptr() + 4 * 32 * r0,
+                     self.enc_act[c] if save else self.enc_act_t[c], n, save, c) for r0, n, save in self.enc_problems(c)]
+
+        groups = stage.geometry_groups(self.cams, self.hw, self._fused_bwd_ok, lambda c: len(self.enc_problems(c)), stage.EF_MAXP)
+        stage.encode(groups, problems, self.hw, self.compute, self.img_dtype, self.packs, self._fused_ok, self._fused_saves,
+                     lambda c, pr: stage.launch_fused(pr, self.packs, self.hw[c]), pack_per_camera=False, per_layer_last=True)
 
     def _encoders_backward(self):
         """The encoder backward over the first 3*B images of every camera (one problem per camera)."""
-        n3 = N_GRAD_SLOTS * self.B
         g = self.blk.grad
-        for cs in self._geometry_groups(self._fused_bwd_ok, 8):
-            c0 = cs[0]
-            H, W = self.hw[c0]
-            np_, ns = len(cs), ops.int_array([n3] * len(cs))
-            args = [np_, ops.ptr_array([self._img_ptr(c, 0) for c in cs]), ops.ptr_array([self.blk.enc(c) for c in cs]),
-                    ops.ptr_array([self.enc_act[c] for c in cs]), ops.ptr_array([self.enc_dout[c] for c in cs]),
-                    ops.ptr_array([self.blk.enc(c, g) for c in cs]), ns, H, W]
-            if self._fused_bwd_ok(c0):
-                nb = ops.L.lib().tacorl_encoder_bwd_fused_ws_bytes(np_, ns, H, W)
-                ws = ops.workspace(nb, self.dev, "ril_enc_bwd_fused_" + "+".join(cs))
-                call("tacorl_encoder_bwd_fused", *args, 0, ptr(ws), ws.numel(), ops.stream())
-            else:
-                nb = ops.L.lib().tacorl_encoder_bwd_ws_bytes(np_, ns, H, W)
-                ws = ops.workspace(nb, self.dev, "ril_enc_bwd")
-                call("tacorl_encoder_bwd", *args, BF16 if self.img_dtype == torch.bfloat16 else F32, self.compute, 0, ptr(ws),
-                     ws.numel(), ops.stream())
+        for cs in stage.geometry_groups(self.cams, self.hw, self._fused_bwd_ok, lambda c: 1, stage.EBW_MAXP):
+            fused = self._fused_bwd_ok(cs[0])
+            ops.encoder_bwd([self._img_ptr(c, 0) for c in cs], [self.blk.enc(c) for c in cs], [self.enc_act[c] for c in cs],
+                            [self.enc_dout[c] for c in cs], [self.blk.enc(c, g) for c in cs], *self.hw[cs[0]], self.compute,
+                            fused=fused, n=[N_GRAD_SLOTS * self.B] * len(cs), xd=stage.image_flag(self.img_dtype), device=self.dev,
+                            ws_tag="ril_enc_bwd_fused_" + "+".join(cs) if fused else "ril_enc_bwd")
 
     # ----------------------------------------------------------------- the step
     def mlp_paths(self):
@@ -334,12 +256,8 @@ class RILEngine:
              self.Ac["high"], 0, gs, ptr(self.d_head["high"]), ops._at(self.logs, 1), ops.stream())
         ops.mark("nll")
 
-    def _mlp_backward(self, tag, xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts):
-        if ops.mlp_bwd_fused_ok(len(xs), dims, ldo, ldd, self.compute):
-            ops.mlp_bwd_fused_dgrad(params, acts_buf, d_outs, ldo, d_xs, ldd, M, dims, acts, "ril_bwdf_" + tag)
-            ops.mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, "ril_bwdf_" + tag)
-            return
-        ops.mlp_bwd(xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, self.compute, ws_tag="ril_bwd_" + tag)
+    def _mlp_backward(self, tag, *site):
+        ops.mlp_backward(("ril_bwd_" + tag, "ril_bwdf_" + tag), *site, self.compute)
 
     def backward(self):
         B, E, G, Eo, blk = self.B, self.E, self.G, self.Eo, self.blk
@@ -375,7 +293,7 @@ class RILEngine:
         """One Adam over the whole block (no clipping), then the fused encoder's packed conv weights behind it."""
         b = self.blk
         ops.adam_step_batch([(b.param, b.grad, b.m, b.v, self.hp["lr"], 0.0, b.step, None, 0.0)])
-        self._pack_encoders([c for c in self.cams if self._fused_ok(c)])
+        self.packs.pack([(b, c) for c in self.cams if self._fused_ok(c)])
         ops.mark("adam")
 
     def allreduce_grads(self):

@@ -109,23 +109,31 @@ def encoder_fwd(imgs, params, outs, acts, H, W, compute=F32):
          int_array(n), H, W, xd, compute, stream())
 
 
-def encoder_bwd(imgs, params, acts, d_outs, grads, H, W, compute=F32, accumulate=False, fused=False):
-    """fused=True: the per-image LDS-resident conv backward (bf16 images + bf16 MFMA + supported geometry)."""
-    n = [i.shape[0] for i in imgs]
-    xd = BF16 if imgs[0].dtype == torch.bfloat16 else F32
+def encoder_bwd_fused_workspace(n, H, W, device, ws_tag):
+    """Scratch buffer of the fused encoder backward over problems of n[p] images (its weight-only preparation writes there
+    too); None where the LDS-resident backward does not take the geometry / the problem count."""
+    nb = L.lib().tacorl_encoder_bwd_fused_ws_bytes(len(n), int_array(n), H, W)
+    return workspace(nb, device, ws_tag) if nb else None
+
+
+def encoder_bwd(imgs, params, acts, d_outs, grads, H, W, compute=F32, accumulate=False, fused=False, n=None, xd=None,
+                device=None, ws_tag=None):
+    """fused=True: the per-image LDS-resident conv backward (bf16 images + bf16 MFMA + supported geometry).
+    imgs: tensors, or raw addresses with n (images per problem), xd (image dtype flag) and device given; ws_tag: the scratch
+    buffer's name (steps that may share a process keep their own)."""
+    if n is None:
+        n, xd, device = [i.shape[0] for i in imgs], BF16 if imgs[0].dtype == torch.bfloat16 else F32, imgs[0].device
+    args = [len(imgs), ptr_array(imgs), ptr_array(params), ptr_array(acts), ptr_array(d_outs), ptr_array(grads), int_array(n), H, W]
     if fused:
         assert xd == BF16 and compute == BF16
-        nb = L.lib().tacorl_encoder_bwd_fused_ws_bytes(len(imgs), int_array(n), H, W)
-        if nb == 0:
+        ws = encoder_bwd_fused_workspace(n, H, W, device, ws_tag or "enc_bwd_fused")
+        if ws is None:
             raise L.TacorlHipError(f"encoder_bwd_fused: geometry {H}x{W} / {len(imgs)} problems not supported")
-        ws = workspace(nb, imgs[0].device, "enc_bwd_fused")
-        call("tacorl_encoder_bwd_fused", len(imgs), ptr_array(imgs), ptr_array(params), ptr_array(acts),
-             ptr_array(d_outs), ptr_array(grads), int_array(n), H, W, int(accumulate), ptr(ws), ws.numel(), stream())
+        call("tacorl_encoder_bwd_fused", *args, int(accumulate), ptr(ws), ws.numel(), stream())
         return
     nb = L.lib().tacorl_encoder_bwd_ws_bytes(len(imgs), int_array(n), H, W)
-    ws = workspace(nb, imgs[0].device, "enc_bwd")
-    call("tacorl_encoder_bwd", len(imgs), ptr_array(imgs), ptr_array(params), ptr_array(acts), ptr_array(d_outs),
-         ptr_array(grads), int_array(n), H, W, xd, compute, int(accumulate), ptr(ws), ws.numel(), stream())
+    ws = workspace(nb, device, ws_tag or "enc_bwd")
+    call("tacorl_encoder_bwd", *args, xd, compute, int(accumulate), ptr(ws), ws.numel(), stream())
 
 
 # ------------------------------------------------------------------------------- MLP
@@ -207,6 +215,21 @@ def mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, ws
     call("tacorl_mlp_bwd_fused_wgrad", len(xs), ptr_array(xs), ldx, ptr_array(acts_buf), ptr_array(d_outs), ldo,
          ptr_array(grads), int_array(M), len(dims) - 1, int_array(dims), int_array(acts), int(accumulate), int(lean), ptr(ws),
          ws.numel(), stream())
+
+
+def mlp_backward(tags, xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, compute, prepacked=False,
+                 lean=False):
+    """MLP backward.  bf16 mode: the input-gradient chain as ONE launch, the weight gradients as one launch in line
+    behind it (on side streams of their own - only Adam needs them - a third set of concurrent launches beside the
+    action-decoder branch's chip-wide GEMMs cost the chain more than their kernels' time: 0.8801 -> 0.8682 ms in line,
+    round 3).  Otherwise: the per-layer path.  tags = (per-layer, fused) scratch buffer names; prepacked / lean: see
+    mlp_bwd_fused_pack / mlp_lean_ok."""
+    if not mlp_bwd_fused_ok(len(xs), dims, ldo, ldd, compute):
+        mlp_bwd(xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, compute, ws_tag=tags[0])
+        return
+    mlp_bwd_fused_dgrad(params, acts_buf, d_outs, ldo, d_xs, ldd, M, dims, acts, tags[1], prepacked=prepacked, lean=lean)
+    if any(g is not None for g in grads):
+        mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, tags[1], lean=lean)
 
 
 # --------------------------------------------------------------------- data movement
