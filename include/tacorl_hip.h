@@ -427,6 +427,29 @@ int tacorl_pack_images_u8_aug_gather_batch(int njobs, const void* const* src, co
  * disp_dtype: 0 float32, 1 int64, 2 int32, 3 uint8 / bool. */
 int tacorl_stage_transition(const void* disp, int disp_dtype, float* reward, float* done, int B,
                             const float* acts_src, float* acts_dst, long n_acts, tacorl_stream_t stream);
+/* The transition sampler of CQL_Offline's dataset (reference datamodule/dataset/goal_cond_replay_buffer_dataset.py:
+ * 145-299) over resident tables, one thread per sample b < B:
+ *   step = possible_steps[idx[b]], end = ep_end[k] of the last episode with ep_start[k] <= step (binary search), and by
+ *   strategy[b]: 0 geometric      goal = min(end, step + disp[b])
+ *                1 similar_robot_obs  goal = nn_val[nn_ptr[step] + floor(u * count)] (CSR over steps [0, n_nn)); an empty
+ *                                 or missing list falls back to `random`
+ *                2 random         goal = possible_steps[j + (j >= idx[b])], j = floor(u * (n_possible - 1))
+ *                3 increasing_horizon  goal = step + 1 + floor(u * (min(end, step + current_horizon) - step))
+ *                4 episode_future goal = step + 1 + floor(u * (end - step))
+ *                5 next_state     goal = step + 1
+ *   with u = u_choice[b] in [0, 1).  ids: int64 (3, B) = [step | step + 1 | goal] (the id tables of the obs / next / goal
+ *   image packs, stride 1 at offsets 0, B, 2B); action[b] = actions[step] (A floats); reward[b] = done[b] = (goal == step+1).
+ * The tables are validated by the host (tacorl_amd/data/replay.py TransitionIndex) and every id they can produce lies in
+ * [0, n_frames); each id is nevertheless clamped to that range before it is written, and *status is set to 1 (it is never
+ * cleared here) when a clamp changed a value, idx[b] lay outside [0, n_possible) or strategy[b] is none of the above.
+ * All pointers are device pointers, 8-byte (int64 / double) or 4-byte (float / int) aligned; nn_ptr / nn_val may be
+ * NULL when n_nn == 0.  Nothing is allocated; B <= 0, A <= 0, an empty table or a NULL / misaligned pointer is refused
+ * with TACORL_EINVAL before anything is launched. */
+int tacorl_sample_transitions(const long* possible_steps, long n_possible, const long* ep_start, const long* ep_end,
+                              int n_episodes, const long* nn_ptr, long n_nn, const long* nn_val, const float* actions,
+                              const long* idx, const long* strategy, const long* disp, const double* u_choice,
+                              long current_horizon, long n_frames, int B, int A, long* ids, float* action,
+                              float* reward, float* done, int* status, tacorl_stream_t stream);
 /* dst[r][0:cols] (+)= src[r % src_row_mod][0:cols]  (src_row_mod <= 0: r).  expand_obs on
  * embeddings instead of images (reference utils/misc.py:132-153) and torch.cat plumbing. */
 int tacorl_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, int rows, int cols,

@@ -135,6 +135,7 @@ _SIGS = {
     "tacorl_gather_frames_u8": (_i, [_p, _l, _p, _p, _l, _p]),
     "tacorl_pack_images_u8_aug_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "tacorl_stage_transition": (_i, [_p, _i, _p, _p, _i, _p, _p, _l, _p]),
+    "tacorl_sample_transitions": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p]),
     "tacorl_copy_cols": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "tacorl_copy_cols_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "tacorl_reduce_rows_mod": (_i, [_p, _i, _p, _i, _i, _i, _i, _p]),

@@ -169,7 +169,107 @@ __global__ __launch_bounds__(256) void pack_u8_aug_kernel(AugTbl t, int H, int W
   }
 }
 
+// Transition sampling (reference datamodule/dataset/goal_cond_replay_buffer_dataset.py:145-299) as index arithmetic: one
+// thread per sample.  The tables were validated on the host (tacorl_amd/data/replay.py TransitionIndex), so every id below
+// lies in [0, n_frames) by construction; the clamps are a second line of defence in front of the unchecked frame gathers,
+// and a clamp that had to change a value raises the status word (plain store: every writer stores the same 1).
+struct TransTbl {
+  const long* steps; long n_steps;              // possible_steps, sorted
+  const long* ep_start; const long* ep_end; int n_ep;
+  const long* nn_ptr; long n_nn; const long* nn_val;  // CSR neighbour lists of steps [0, n_nn)
+  const float* actions;                         // (n_frames, A)
+  const long* idx; const long* strategy; const long* disp; const double* u;
+  long horizon, n_frames;
+  long* ids; float* action; float* reward; float* done; int* status;
+};
+enum { TS_GEOMETRIC = 0, TS_SIMILAR = 1, TS_RANDOM = 2, TS_HORIZON = 3, TS_EPISODE = 4, TS_NEXT = 5 };
+
+__device__ __forceinline__ long pick_of(double u, long n) {  // floor(u * n) kept inside [0, n)
+  long k = (long)(u * (double)n);
+  return k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
+}
+
+__global__ __launch_bounds__(256) void sample_transitions_kernel(TransTbl t, int B, int A) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  bool bad = false;
+  long pos = t.idx[b];
+  if (pos < 0 || pos >= t.n_steps) { bad = true; pos = pos < 0 ? 0 : t.n_steps - 1; }
+  const long step = t.steps[pos];
+  // episode end: the last episode whose start is <= step (binary search over the sorted starts)
+  int lo = 0, hi = t.n_ep;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (t.ep_start[mid] <= step) lo = mid + 1; else hi = mid;
+  }
+  const long end = t.ep_end[lo > 0 ? lo - 1 : 0];
+  const double u = t.u[b];
+  long strat = t.strategy[b];
+  long goal = step + 1;
+  bool fallback = false;  // the reference's `return self.get_goal_step(step, strategy="random")`
+  if (strat == TS_GEOMETRIC) {
+    const long d = t.disp[b];
+    goal = d >= end - step ? end : step + d;  // min(end, step + disp) without the overflow of a huge draw
+  } else if (strat == TS_SIMILAR) {
+    long cnt = 0, first = 0;
+    if (step >= 0 && step < t.n_nn) { first = t.nn_ptr[step]; cnt = t.nn_ptr[step + 1] - first; }
+    if (cnt > 0) goal = t.nn_val[first + pick_of(u, cnt)];
+    else fallback = true;
+  } else if (strat == TS_HORIZON || strat == TS_EPISODE) {
+    const long last = (strat == TS_HORIZON && t.horizon < end - step) ? step + t.horizon : end;
+    if (last > step) goal = step + 1 + pick_of(u, last - step);
+    else fallback = true;
+  } else if (strat == TS_RANDOM) {
+    fallback = true;
+  } else if (strat != TS_NEXT) {
+    bad = true;
+  }
+  if (fallback) {
+    if (t.n_steps > 1) {
+      const long j = pick_of(u, t.n_steps - 1);
+      goal = t.steps[j + (j >= pos ? 1 : 0)];  // possible_steps with `step` removed, as an index shift
+    } else {
+      bad = true;
+    }
+  }
+  const long top = t.n_frames - 1;
+  long id[3] = {step, step + 1, goal};
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const long c = id[k] < 0 ? 0 : (id[k] > top ? top : id[k]);
+    bad |= c != id[k];
+    t.ids[(long)k * B + b] = c;
+    id[k] = c;
+  }
+  const float r = goal == step + 1 ? 1.f : 0.f;
+  t.reward[b] = r;
+  t.done[b] = r;
+  const float* __restrict__ a = t.actions + id[0] * A;
+  for (int k = 0; k < A; k++) t.action[(long)b * A + k] = a[k];
+  if (bad) *t.status = 1;
+}
+
 }  // namespace
+
+extern "C" int tacorl_sample_transitions(const long* possible_steps, long n_possible, const long* ep_start,
+                                         const long* ep_end, int n_episodes, const long* nn_ptr, long n_nn,
+                                         const long* nn_val, const float* actions, const long* idx, const long* strategy,
+                                         const long* disp, const double* u_choice, long current_horizon, long n_frames,
+                                         int B, int A, long* ids, float* action, float* reward, float* done, int* status,
+                                         tacorl_stream_t stream) {
+  if (B <= 0 || A <= 0 || n_possible <= 0 || n_episodes <= 0 || n_frames <= 0 || n_nn < 0) return TACORL_EINVAL;
+  const void* p8[] = {possible_steps, ep_start, ep_end, idx, strategy, disp, u_choice, ids};
+  const void* p4[] = {actions, action, reward, done, status};
+  for (const void* p : p8)
+    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
+  for (const void* p : p4)
+    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
+  if (n_nn > 0 && (!nn_ptr || !nn_val || ((uintptr_t)nn_ptr & 7) || ((uintptr_t)nn_val & 7))) return TACORL_EINVAL;
+  const TransTbl t{possible_steps, n_possible, ep_start, ep_end, n_episodes, nn_ptr, n_nn, nn_val, actions, idx, strategy,
+                   disp, u_choice, current_horizon, n_frames, ids, action, reward, done, status};
+  hipLaunchKernelGGL(sample_transitions_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, B, A);
+  return LAUNCH_OK();
+}
 
 extern "C" int tacorl_gather_frames_u8(const void* frames, long frame_bytes, const long* index, void* dst, long n,
                                        tacorl_stream_t stream) {

@@ -43,3 +43,18 @@ def draw_play_batch_augmentation(specs, B, T, device, generator=None):
         aug["goal"][cam] = {"shift": s, "jitter": j}
         aug["pad"][cam] = sp.pad
     return aug
+
+
+def draw_transition_batch_augmentation(specs, B, device, generator=None):
+    """batch["aug"] for a transition batch: per camera three independent draws, for the observation, the next observation
+    and the goal frame - the reference's transition dataset transforms the three in three separate calls
+    (goal_cond_replay_buffer_dataset.py:276-282)."""
+    aug = {"obs": {}, "next": {}, "goal": {}, "pad": {}, "resize": {}}
+    for cam, sp in specs.items():
+        if sp.resize is not None:
+            aug["resize"][cam] = sp.resize
+        for role in ("obs", "next", "goal"):
+            s, j = sp.draw(B, device, generator)
+            aug[role][cam] = {"shift": s, "jitter": j}
+        aug["pad"][cam] = sp.pad
+    return aug

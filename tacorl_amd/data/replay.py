@@ -392,3 +392,240 @@ class PinnedReplay:
             t.record_stream(cs)
         self._pending = None
         return b
+
+
+# ------------------------------------------------------------------------------------------ transitions (CQL_Offline)
+# Goal strategies of the reference's GoalCondReplayBufferDataset (datamodule/dataset/goal_cond_replay_buffer_dataset.py:
+# 224-264) as the codes the sampler kernel takes (include/tacorl_hip.h tacorl_sample_transitions).
+STRATEGIES = ("geometric", "similar_robot_obs", "random", "increasing_horizon", "episode_future", "next_state")
+S_GEOMETRIC, S_SIMILAR, S_RANDOM, S_HORIZON, S_EPISODE, S_NEXT = range(6)
+
+
+class TransitionIndex:
+    """The sampling of GoalCondReplayBufferDataset.__getitem__ (:145-299) as a deterministic function of explicit draws,
+    as PlayIndex is for the play windows: item idx is the transition at possible_steps[idx], its goal frame is chosen by
+    one of the strategies above, reward = done = (goal == step + 1).  tests/golden/transition_sampler.npz (recorded from
+    the reference class) pins it; `tacorl_sample_transitions` is the same arithmetic on the device.
+    The tables are validated here, once: every id the arithmetic can then produce lies in [0, n_frames) - the step and
+    step + 1 inside their episode (the end step is no item), a geometric / horizon / future goal at most the episode end, a
+    neighbour id checked one by one, a random goal another item - which is what the unchecked device gathers rely on."""
+
+    def __init__(self, ep_start_end_ids, n_frames=None, goal_strategy_prob=None, goal_sampling_prob=0.3, initial_horizon=8,
+                 horizon_step=4, max_horizon=256, nn_steps_from_step=None, filter_by_tasks=False, tasks=(), train=True):
+        gs = dict(goal_strategy_prob or {"geometric": 0.5, "similar_robot_obs": 0.5})
+        if "task_future" in gs or filter_by_tasks:
+            raise NotImplementedError("task_future / filter_by_tasks need the language annotations (not built)")
+        unknown = [k for k in gs if k not in STRATEGIES]
+        if unknown:
+            raise ValueError(f"unknown goal strategies {unknown}; known: {STRATEGIES}")
+        if not np.isclose(sum(gs.values()), 1.0) or min(gs.values()) < 0:
+            raise ValueError("Goal strategy probability must sum to 1")  # :50-52
+        if not 0.0 < float(goal_sampling_prob) <= 1.0:
+            raise ValueError(f"goal_sampling_prob {goal_sampling_prob} outside (0, 1]")
+        self.goal_strategy_prob, self.train = gs, train
+        self._codes = np.array([STRATEGIES.index(k) for k in gs], dtype=np.int64)  # np.random.choice(options, p): dict order
+        self._cum = np.cumsum([float(v) for v in gs.values()])
+        self.p_geom_goal = float(goal_sampling_prob)
+        self.initial_horizon, self.horizon_step, self.max_horizon = int(initial_horizon), int(horizon_step), int(max_horizon)
+        self.current_horizon = self.initial_horizon
+        self.ep = np.asarray(ep_start_end_ids, dtype=np.int64).reshape(-1, 2)
+        if len(self.ep) == 0:
+            raise ValueError("no episodes")
+        self.n_frames = int(n_frames) if n_frames is not None else int(self.ep[:, 1].max()) + 1
+        if self.ep.min() < 0 or self.ep.max() >= self.n_frames:
+            raise ValueError(f"episode bounds outside [0, {self.n_frames})")
+        if (self.ep[:, 0] > self.ep[:, 1]).any() or (self.ep[1:, 0] <= self.ep[:-1, 1]).any():
+            raise ValueError("episodes must be sorted by start and must not overlap")
+        # set_possible_steps (:174-178): every step but the episodes' end steps, so step + 1 always exists
+        self.possible_steps = np.concatenate([np.arange(s, e) for s, e in self.ep])
+        if len(self.possible_steps) < 2:
+            raise ValueError("fewer than two possible steps: the `random` strategy has nothing to choose from")
+        self.nn = {int(k): np.asarray(v, dtype=np.int64).reshape(-1) for k, v in (nn_steps_from_step or {}).items()}
+        for k, v in self.nn.items():
+            if not 0 <= k < self.n_frames or (len(v) and (v.min() < 0 or v.max() >= self.n_frames)):
+                raise ValueError(f"nn_steps_from_step[{k}]: a step outside [0, {self.n_frames})")
+        top = (max(self.nn) + 1) if self.nn else 0
+        cnt = np.zeros(top, dtype=np.int64)
+        for k, v in self.nn.items():
+            cnt[k] = len(v)
+        self._nn_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        self._nn_val = np.concatenate([self.nn[k] for k in sorted(self.nn)] + [np.zeros(0, np.int64)]).astype(np.int64)
+
+    def __len__(self):
+        return len(self.possible_steps)
+
+    def increase_horizon(self, epoch):  # :132-134
+        self.current_horizon = min(self.initial_horizon + int(epoch) * self.horizon_step, self.max_horizon)
+
+    def increase_horizon_to(self, desired_horizon):  # :136-137
+        self.current_horizon = min(int(desired_horizon), self.max_horizon)
+
+    def strategy_of(self, u):
+        """np.random.choice(options, p=prob) (:145-148) as a function of its uniform: the first strategy, in the dict's
+        order, whose cumulative probability exceeds u."""
+        k = np.minimum(np.searchsorted(self._cum, np.asarray(u), side="right"), len(self._codes) - 1)
+        return self._codes[k]
+
+    def draw(self, n, rng):
+        """The random quantities n items consume: the item, its strategy, the geometric displacement (:231) and the one
+        uniform that picks among a strategy's options (np.random.choice over a list, :222,228,247)."""
+        return {"idx": rng.integers(0, len(self), size=n), "strategy": self.strategy_of(rng.random(n)),
+                "disp": rng.geometric(self.p_geom_goal, size=n).astype(np.int64), "u_choice": rng.random(n)}
+
+    def draw_device(self, n, device, generator=None):
+        """`draw` made by torch on the device (nothing crosses PCIe): int64 idx / strategy / disp, float64 u_choice."""
+        dev = torch.device(device)
+        tabs = self.__dict__.setdefault("_dev_draw_tables", {})
+        if dev not in tabs:
+            tabs[dev] = (torch.from_numpy(self._cum).to(dev), torch.from_numpy(self._codes).to(dev))
+        cum, codes = tabs[dev]
+        g = generator
+        idx = torch.randint(0, len(self), (n,), device=dev, generator=g, dtype=torch.int64)
+        k = torch.searchsorted(cum, torch.rand(n, device=dev, generator=g, dtype=torch.float64), right=True)
+        disp = torch.empty(n, device=dev, dtype=torch.float64).geometric_(self.p_geom_goal, generator=g)
+        return {"idx": idx, "strategy": codes[k.clamp_(max=len(codes) - 1)], "disp": disp.to(torch.int64),
+                "u_choice": torch.rand(n, device=dev, generator=g, dtype=torch.float64)}
+
+    def episode_end(self, step):
+        """find_episode_end (:203-207) by binary search: the end of the episode with start <= step <= end."""
+        k = np.maximum(np.searchsorted(self.ep[:, 0], np.asarray(step), side="right") - 1, 0)
+        return self.ep[k, 1]
+
+    def sample(self, idx, d):
+        """idx (n,) items (None: d["idx"]); d = draw(...).  Returns step, next (= step + 1), goal frame ids, reward, done."""
+        idx = np.asarray(d["idx"] if idx is None else idx, dtype=np.int64)
+        strat, disp = np.asarray(d["strategy"], dtype=np.int64), np.asarray(d["disp"], dtype=np.int64)
+        u = np.asarray(d["u_choice"], dtype=np.float64)
+        pick = lambda n: np.clip((u * n).astype(np.int64), 0, np.maximum(n - 1, 0))  # noqa: E731  floor(u n) in [0, n)
+        step = self.possible_steps[idx]
+        end = self.episode_end(step)
+        goal = step + 1  # next_state
+        goal = np.where(strat == S_GEOMETRIC, np.where(disp >= end - step, end, step + disp), goal)  # min(end, step + disp)
+        # similar_robot_obs: one of the step's recorded neighbours (CSR)
+        inside = step < len(self._nn_ptr) - 1
+        kc = np.where(inside, step, 0)
+        lo = self._nn_ptr[kc] if len(self._nn_ptr) > 1 else np.zeros(len(idx), np.int64)
+        cnt = np.where(inside, self._nn_ptr[np.minimum(kc + 1, len(self._nn_ptr) - 1)] - lo, 0)
+        if len(self._nn_val):
+            goal = np.where((strat == S_SIMILAR) & (cnt > 0), self._nn_val[np.minimum(lo + pick(cnt), len(self._nn_val) - 1)], goal)
+        # increasing_horizon / episode_future: uniform over [step + 1, last] (get_random_future_step, :216-222)
+        last = np.where((strat == S_HORIZON) & (self.current_horizon < end - step), step + self.current_horizon, end)
+        future = (strat == S_HORIZON) | (strat == S_EPISODE)
+        goal = np.where(future & (last > step), step + 1 + pick(last - step), goal)
+        # random, and the reference's fallback to it: possible_steps without `step`, the removal as an index shift
+        fallback = (strat == S_RANDOM) | ((strat == S_SIMILAR) & (cnt == 0)) | (future & (last <= step))
+        j = pick(np.full(len(idx), len(self) - 1))
+        goal = np.where(fallback, self.possible_steps[j + (j >= idx)], goal)
+        r = (goal == step + 1).astype(np.int64)
+        return {"step": step, "next": step + 1, "goal": goal, "reward": r, "done": r.copy(), "idx": idx}
+
+
+class HbmTransitionReplay:
+    """CQL_Offline's transition batches out of a dataset resident in HBM: frames[cam] = (N,H,W,3) uint8, the (N,A) action
+    table and the index tables all live on the device, and `batch()` is one launch of the sampler kernel
+    (`tacorl_sample_transitions`) on the current stream - no host synchronisation, nothing over PCIe.
+    The returned tensors are views of this object's own buffers, a ring of `slots` sets (as HbmReplay's staging ring): a
+    batch stays valid until `slots - 1` more have been drawn, so a trainer that fetches a batch or two ahead of the step
+    it runs (pytorch_lightning looks one ahead to learn which batch is the last) still trains on the batch it was given."""
+
+    def __init__(self, frames, actions, index, device=None, batch_size=256, slots=6):
+        self.dev = torch.device(device) if device is not None else next(iter(frames.values())).device
+        self.index, self.batch_size = index, int(batch_size)
+        self.frames = {c: v.to(self.dev).contiguous() for c, v in frames.items()}
+        acts = torch.as_tensor(np.asarray(actions, dtype=np.float32) if not torch.is_tensor(actions) else actions)
+        acts = acts.to(self.dev, torch.float32).contiguous()
+        short = [c for c, v in self.frames.items() if v.dtype != torch.uint8 or v.dim() != 4 or v.shape[0] < index.n_frames]
+        if short or acts.dim() != 2 or acts.shape[0] < index.n_frames:
+            raise ValueError(f"frames (uint8 (N,H,W,3)) and actions (N,A) must cover the index's {index.n_frames} frames")
+        i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)  # noqa: E731
+        self.tables = {"steps": i64(index.possible_steps), "ep_start": i64(index.ep[:, 0]), "ep_end": i64(index.ep[:, 1]),
+                       "nn_ptr": i64(index._nn_ptr), "nn_val": i64(index._nn_val if len(index._nn_val) else [0]),
+                       "actions": acts, "n_nn": len(index._nn_ptr) - 1, "n_frames": index.n_frames}
+        self.A = int(acts.shape[1])
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        if int(slots) < 1:
+            raise ValueError("slots must be >= 1")
+        self._cap, self._ring, self._k, self._u8 = 0, [{} for _ in range(int(slots))], 0, {}
+        self._grow(self.batch_size)
+
+    def _grow(self, B):
+        """The batch buffers exist before the first batch and are replaced only for a larger one - under the capture lock,
+        and captured graphs that could hold an old address are dropped (as _PinnedRing.put_all)."""
+        if B <= self._cap:
+            return
+        with ops.capture_lock:
+            for k in range(len(self._ring)):
+                self._ring[k] = {"ids": torch.zeros(3 * B, dtype=torch.int64, device=self.dev),
+                                 "action": torch.zeros(B * self.A, device=self.dev), "reward": torch.zeros(B, device=self.dev),
+                                 "done": torch.zeros(B, device=self.dev)}
+            self._cap = B
+            ops.note_alloc()
+
+    def _out(self, key, shape):
+        n = int(np.prod(shape))
+        t = self._u8.get(key)
+        if t is None or t.numel() < n:
+            with ops.capture_lock:
+                t = self._u8[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
+                ops.note_alloc()
+        return t[:n].view(shape)
+
+    def check(self):
+        """Reads the sampler's status word back (a host synchronisation: call it when you ask, not per step)."""
+        if int(self.status.item()) != 0:
+            raise IndexError("transition replay: the sampler had to clamp a frame id (tables or draws outside the dataset)")
+
+    def batch(self, draws=None, aug=None, fused=True, batch_size=None):
+        """draws: TransitionIndex.draw_device(...) (None: drawn here for `batch_size`), or the host form `draw(...)`.
+        fused=True: no frame moves here - the batch carries the dataset tensors and the id table [step | step+1 | goal]
+        (`batch["replay"]`), and CQL_Offline's image pack reads the frames by index on their way into the encoders.
+        fused=False: the reference dataset's schema with the uint8 frames gathered (tacorl_gather_frames_u8)."""
+        if draws is None:
+            draws = self.index.draw_device(batch_size or self.batch_size, self.dev)
+        d = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))).to(self.dev).contiguous()
+             for k, v in draws.items() if k in ("idx", "strategy", "disp", "u_choice")}
+        B = int(d["idx"].numel())
+        self._grow(B)
+        self._k = slot = (self._k + 1) % len(self._ring)
+        buf = self._ring[slot]
+        ids = buf["ids"][: 3 * B].view(3, B)
+        act, rew, done = buf["action"][: B * self.A].view(B, self.A), buf["reward"][:B], buf["done"][:B]
+        ops.sample_transitions(self.tables, d, self.index.current_horizon, ids, act, rew, done, self.status)
+        b = {"actions": act, "rewards": rew, "terminals": done}
+        if aug is not None:
+            b["aug"] = aug
+        if fused:
+            b["replay"] = {"kind": "transition", "frames": self.frames, "ids": ids, "B": B}
+            return b
+        obs, nxt, goal = {}, {}, {}
+        for c, fr in self.frames.items():
+            shape = (B,) + tuple(fr.shape[1:])
+            obs[c] = ops.gather_frames_u8(fr, ids[0], self._out((slot, "s", c), shape))
+            nxt[c] = ops.gather_frames_u8(fr, ids[1], self._out((slot, "n", c), shape))
+            goal[c] = ops.gather_frames_u8(fr, ids[2], self._out((slot, "g", c), shape))
+        b.update(observations={"observation": obs, "goal": goal}, next_observations={"observation": nxt, "goal": goal})
+        return b
+
+
+class TransitionLoader:
+    """`steps_per_epoch` batches of `batch_size` fresh device draws per pass: what Trainer.fit takes as train_dataloaders /
+    val_dataloaders for CQL_Offline.  train=False (validation) draws no augmentation.  A batch is views of the replay's ring
+    of buffers (HbmTransitionReplay(slots=6)): a trainer may hold up to `slots - 1` batches ahead of the one it is running."""
+
+    def __init__(self, replay, batch_size, steps_per_epoch, aug_specs=None, generator=None, train=True, fused=True):
+        self.replay, self.batch_size, self.steps_per_epoch = replay, int(batch_size), int(steps_per_epoch)
+        self.aug_specs, self.generator, self.train, self.fused = aug_specs, generator, train, fused
+
+    def __len__(self):
+        return self.steps_per_epoch
+
+    def __iter__(self):
+        from .augment import draw_transition_batch_augmentation
+
+        rp = self.replay
+        for _ in range(self.steps_per_epoch):
+            draws = rp.index.draw_device(self.batch_size, rp.dev, self.generator)
+            aug = None
+            if self.train and self.aug_specs:
+                aug = draw_transition_batch_augmentation(self.aug_specs, self.batch_size, rp.dev, self.generator)
+            yield rp.batch(draws, aug=aug, fused=self.fused)

@@ -179,7 +179,16 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
     # ---------------------------------------------------------------------- stepping
     def overwrite_batch(self, batch):
         """reference :118-147 (shape/dtype normalisation of the transition batch)."""
+        rp = batch.get("replay") if isinstance(batch, dict) else None
+        if rp is not None:
+            # HbmTransitionReplay.batch(fused=True): no frames, the dataset and the id table [step | step+1 | goal]; the
+            # small tensors are the sampler kernel's own f32 device outputs (data/replay.py)
+            if rp.get("kind") != "transition":
+                raise ValueError("CQL_Offline takes the transition replay (HbmTransitionReplay), not the play-window one")
+            return dict(batch), batch["actions"], None, batch["rewards"], batch["terminals"]
         obs, nxt = batch["observations"], batch["next_observations"]
+        if batch.get("aug") is not None:  # the gathered uint8 batch with its augmentation tables
+            obs = dict(obs, aug=batch["aug"])
         return obs, batch["actions"].float(), nxt, batch["rewards"].float(), batch["terminals"].int()
 
     def _stage(self, obs, goal, nxt, action, reward, done, noise, nchw=True):
@@ -201,10 +210,82 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         e.load_transition(action.to(self.dev), reward.to(self.dev), done.to(self.dev))
         e.set_noise(noise)
 
+    def _stage_u8(self, B, src_hw, jobs_of, aug, action, reward, done, noise):
+        """uint8 frames into the engine's image slots by the gathering / augmenting pack.  jobs_of(cam, role) -> (source
+        pointer, bytes per source frame, index pointer or None): the dataset and an id table (the fused replay batch), or a
+        gathered (B,H,W,3) tensor.  Obs and next images are packed for the cameras of obs_modalities only, goal images for the
+        cameras of goal_modalities only, into the slots engine.slot[cam] defines; aug (None: the plain normalising pack) holds
+        per role and camera the shift / jitter tables, the pad and, optionally, the encoders' geometry (`resize`)."""
+        from ... import ops
+
+        e = self.engine
+        rs = (aug or {}).get("resize") or {}
+        hw = {c: tuple(rs.get(c, src_hw[c])) for c in e.enc_cams}
+        e.ensure_batch(B, hw)
+        xd = _lib.BF16 if self.img_dtype == torch.bfloat16 else _lib.F32
+        for c in e.enc_cams:
+            (H, W), (Hs, Ws) = hw[c], src_hw[c]
+            esz, ob = e.X3[c].element_size(), 3 * H * W  # (ob: elements per packed image)
+            jobs = []
+            for role, k in e.slot[c].items():  # obs / goal / next, as far as the camera has the role
+                src, fb, ip = jobs_of(c, role)
+                if fb != 3 * Hs * Ws or fb % 16 or src % 16:
+                    raise ValueError("uint8 frames: H*W*3 must be a multiple of 16 and the tensor 16-byte aligned")
+                job = (src, fb, e.X3[c].data_ptr() + k * B * ob * esz, B, ip, 1)
+                if aug is not None:
+                    t = aug[role][c]
+                    job += (t.get("shift"), t.get("jitter"))
+                jobs.append(job)
+            if aug is None:
+                ops.pack_images_u8_gather_batch(jobs, xd, H, W)
+            else:
+                ops.pack_images_u8_resize_aug_batch(jobs, xd, (Hs, Ws), H, W, aug["pad"][c])
+        e.load_transition(action, reward, done)
+        e.set_noise(noise)
+
+    def _stage_replay(self, batch, action, reward, done, noise):
+        """The fused transition-replay batch: every image is read by frame id straight out of the resident dataset."""
+        rp = batch["replay"]
+        B, ids, frames = rp["B"], rp["ids"], rp["frames"]
+        if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == 3 * B):
+            raise ValueError("transition replay batch: ids must be a contiguous device int64 (3, B) table")
+        row = {"obs": 0, "next": 1, "goal": 2}  # the id table's rows: [step | step + 1 | goal]
+        e = self.engine
+        for c in e.enc_cams:
+            v = frames.get(c)
+            if v is None or not (v.is_cuda and v.is_contiguous() and v.dtype == torch.uint8 and v.dim() == 4):
+                raise ValueError(f"transition replay batch: camera {c} needs a contiguous device uint8 (N,H,W,3) dataset")
+        self._stage_u8(B, {c: tuple(frames[c].shape[1:3]) for c in e.enc_cams},
+                       lambda c, role: (frames[c].data_ptr(), frames[c][0].numel(), ids.data_ptr() + 8 * B * row[role]),
+                       batch.get("aug"), action, reward, done, noise)
+
+    def _stage_gathered_aug(self, obs, goal, nxt, aug, action, reward, done, noise):
+        """The gathered uint8 batch with augmentation tables: the same pack, reading image i of each tensor."""
+        e = self.engine
+        given = {"obs": obs, "goal": goal, "next": nxt}
+        roles = {c: (["obs", "next"] if c in e.cams else []) + (["goal"] if c in e.goal_cams else []) for c in e.enc_cams}
+        for c in e.enc_cams:
+            for role in roles[c]:
+                t = given[role][c]
+                if t.dtype != torch.uint8 or not (t.is_cuda and t.is_contiguous()):
+                    raise ValueError("batch['aug'] needs the dataset's uint8 frames on the device (the augmentation is part of the uint8 pack)")
+        B = action.shape[0]
+        self._stage_u8(B, {c: tuple(given[roles[c][0]][c].shape[-3:-1]) for c in e.enc_cams},
+                       lambda c, role: (given[role][c].data_ptr(), given[role][c][0].numel(), None),
+                       aug, action.to(self.dev), reward.to(self.dev), done.to(self.dev), noise)
+
     def compute_update(self, batch, optimize: bool = True, log_type: str = "train", noise=None):
         obs, action, nxt, reward, done = batch
         self._sync_lrs()
-        self._stage(obs["observation"], obs["goal"], nxt["observation"], action, reward, done, noise)
+        if "replay" in obs:
+            from ...data.replay import wait_ready
+
+            wait_ready(obs)
+            self._stage_replay(obs, action, reward, done, noise)
+        elif obs.get("aug") is not None:
+            self._stage_gathered_aug(obs["observation"], obs["goal"], nxt["observation"], obs["aug"], action, reward, done, noise)
+        else:
+            self._stage(obs["observation"], obs["goal"], nxt["observation"], action, reward, done, noise)
         bc = self.current_epoch < self.bc_epochs
         e = self.engine
         self._run_segments(("cql", e.B, bc, optimize),

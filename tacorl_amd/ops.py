@@ -300,6 +300,26 @@ def gather_frames_u8(frames, index, out):
     return out
 
 
+def sample_transitions(tables, draws, current_horizon, ids, action, reward, done, status):
+    """The transition sampler over resident tables (data/replay.py HbmTransitionReplay): tables = device tensors
+    `steps`, `ep_start`, `ep_end`, `nn_ptr`, `nn_val` (int64), `actions` (N, A) f32 and the int `n_nn`, `n_frames`;
+    draws = device `idx`, `strategy`, `disp` (int64) and `u_choice` (f64), B each.  Writes ids (3, B) int64
+    [step | step+1 | goal], action (B, A), reward (B), done (B) f32 and raises the int32 `status` word on a clamped id."""
+    B, A = ids.shape[1], tables["actions"].shape[1]
+    i64 = [tables[k] for k in ("steps", "ep_start", "ep_end", "nn_ptr", "nn_val")] + [draws[k] for k in ("idx", "strategy", "disp")]
+    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64 + [ids])
+    assert all(draws[k].numel() == B for k in ("idx", "strategy", "disp", "u_choice")) and ids.shape == (3, B)
+    assert draws["u_choice"].dtype == torch.float64 and draws["u_choice"].is_cuda and draws["u_choice"].is_contiguous()
+    assert tables["nn_ptr"].numel() == tables["n_nn"] + 1 and tables["actions"].shape[0] >= tables["n_frames"]
+    for t, n in ((_f32(tables["actions"]), None), (_f32(action), B * A), (_f32(reward), B), (_f32(done), B)):
+        assert n is None or t.numel() == n
+    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+    call("tacorl_sample_transitions", ptr(tables["steps"]), tables["steps"].numel(), ptr(tables["ep_start"]), ptr(tables["ep_end"]),
+         tables["ep_start"].numel(), ptr(tables["nn_ptr"]), tables["n_nn"], ptr(tables["nn_val"]), ptr(tables["actions"]),
+         ptr(draws["idx"]), ptr(draws["strategy"]), ptr(draws["disp"]), ptr(draws["u_choice"]), int(current_horizon),
+         int(tables["n_frames"]), B, A, ptr(ids), ptr(action), ptr(reward), ptr(done), ptr(status), stream())
+
+
 def _at(t, off):
     return C.c_void_p(t.data_ptr() + 4 * off)
 
