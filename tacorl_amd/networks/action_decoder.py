@@ -16,6 +16,9 @@ from .._lib import ACT_NONE, ACT_RELU, call, ptr
 from ..blocks import TensorBlock
 
 
+RNN_MAXP = 4  # problems one batched ring-GEMM launch takes (RNN_MAXP in csrc/rnn_ops.hip)
+
+
 class ActionDecoderLogistic:
     def __init__(self, device, state_dim=32, goal_dim=32, latent_plan_dim=16, hidden_size=256, out_features=7,
                  act_max_bound=(1.0,) * 7, act_min_bound=(-1.0,) * 7, gripper_alpha=1.0, policy_rnn_dropout_p=0.0,
@@ -133,6 +136,9 @@ class ActionDecoderLogistic:
         # layer 0's input projection inside the ring GEMM (K extension, where _ring_proj() says the input fits): the bf16 input rows, zero padded to 128
         # columns, and W_ih_l0 likewise
         self.xb_seq, self.wih0_b = bf(R, 128), bf(H, 128)
+        # (the mirrors above are new and hold zeros: whatever the caller says about them - frozen weights at an unchanged
+        # version, mirrors_current - the next forward refreshes them)
+        self._mirror_shape = self._bf16_version = None
         self._shape = (B, Tm)
 
     # ------------------------------------------------------------------ twin pass (logging-only second plan)
@@ -187,7 +193,7 @@ class ActionDecoderLogistic:
         dsts = self.whb + self.wib[1:] + [self.headw_b]
         call("tacorl_to_bf16_batch", len(srcs), ops.ptr_array(srcs), ops.ptr_array(dsts),
              (C.c_long * len(srcs))(*([H * H] * (len(srcs) - 1) + [self.NH * H])), ops.stream())
-        self._mirror_ring = self._ring_proj()
+        self._mirror_ring, self._mirror_shape = self._ring_proj(), (B, Tm)
         if self._mirror_ring:
             call("tacorl_pad_to_bf16", blk.p("rnn.weight_ih_l0"), self.P + self.E, ptr(self.wih0_b), 128, H, self.P + self.E, ops.stream())
         ob = blk.off["mean_fc.bias"][0]  # the four heads' biases sit back to back
@@ -273,7 +279,7 @@ class ActionDecoderLogistic:
         ver = blk.param._version
         # bf16 weight copies still valid: frozen weights at an unchanged version, or the caller has just run another forward
         # on these weights (PlayLMP: the logging-only random-plan pass and the real pass of one step - mirrors_current)
-        fresh = (frozen and getattr(self, "_bf16_version", None) == ver) or (mirrors_current and getattr(self, "_shape", None) == (B, Tm))
+        fresh = ((frozen and getattr(self, "_bf16_version", None) == ver) or mirrors_current) and getattr(self, "_mirror_shape", None) == (B, Tm)
         if fast:
             self._bf16_version = ver if frozen else None
         if fast and getattr(self, "_mirror_ring", None) != self._ring_proj():  # (the padded W_ih_l0 mirror exists only in ring mode)
@@ -323,21 +329,22 @@ class ActionDecoderLogistic:
                         if twin is not None:
                             x2.append(hbp(l - 1, t, twin)); ad2.append(None); y2.append(at(twin.xin[l], t * B * H)); yb2.append(None)
                             xe2.append(None)
-                if ring:
+                # (a launch takes RNN_MAXP problems; three or more layers reach 5 from step 4 on.  The problems of a launch
+                # are independent of each other, so any cut of the list is the same computation)
+                for i in range(0, len(xs), RNN_MAXP):
+                    c = lambda a, i=i: ops.ptr_array(a[i: i + RNN_MAXP])  # noqa: E731
+                    n, acs = len(xs[i: i + RNN_MAXP]), ops.int_array(ac[i: i + RNN_MAXP])
                     tw_ = twin is not None
-                    call("tacorl_rnn_linear_fwd_batch_ext", len(xs), ops.ptr_array(xs), ops.ptr_array(x2) if tw_ else None,
-                         ops.ptr_array(wt), ops.ptr_array(bs), ops.ptr_array(ad), ops.ptr_array(ad2) if tw_ else None, H,
-                         ops.ptr_array(ys), ops.ptr_array(y2) if tw_ else None, ops.ptr_array(yb), ops.ptr_array(yb2) if tw_ else None,
-                         B, B if tw_ else 0, H, H, ops.int_array(ac), ops.ptr_array(xe), ops.ptr_array(xe2) if tw_ else None,
-                         ops.ptr_array(we), ops.ptr_array(b2), ops.stream())
-                    continue
-                if twin is not None:
-                    call("tacorl_rnn_linear_fwd_batch_twin", len(xs), ops.ptr_array(xs), ops.ptr_array(x2), ops.ptr_array(wt),
-                         ops.ptr_array(bs), ops.ptr_array(ad), ops.ptr_array(ad2), H, ops.ptr_array(ys), ops.ptr_array(y2),
-                         ops.ptr_array(yb), ops.ptr_array(yb2), B, B, H, H, ops.int_array(ac), ops.stream())
-                    continue
-                call("tacorl_rnn_linear_fwd_batch", len(xs), ops.ptr_array(xs), ops.ptr_array(wt), ops.ptr_array(bs),
-                     ops.ptr_array(ad), H, ops.ptr_array(ys), ops.ptr_array(yb), B, H, H, ops.int_array(ac), ops.stream())
+                    if ring:
+                        call("tacorl_rnn_linear_fwd_batch_ext", n, c(xs), c(x2) if tw_ else None, c(wt), c(bs), c(ad),
+                             c(ad2) if tw_ else None, H, c(ys), c(y2) if tw_ else None, c(yb), c(yb2) if tw_ else None,
+                             B, B if tw_ else 0, H, H, acs, c(xe), c(xe2) if tw_ else None, c(we), c(b2), ops.stream())
+                    elif tw_:
+                        call("tacorl_rnn_linear_fwd_batch_twin", n, c(xs), c(x2), c(wt), c(bs), c(ad), c(ad2), H, c(ys), c(y2),
+                             c(yb), c(yb2), B, B, H, H, acs, ops.stream())
+                    else:
+                        call("tacorl_rnn_linear_fwd_batch", n, c(xs), c(wt), c(bs), c(ad), H, c(ys), c(yb), B, H, H, acs,
+                             ops.stream())
             x, K = self.h[L - 1], H
         for l in range(self.L if fast else 0, self.L):  # exact / generic path: layer by layer, step by step
             self._lin(x, K, blk.p(f"rnn.weight_ih_l{l}"), blk.p(f"rnn.bias_ih_l{l}"), self.xin[l], R, K, H, ACT_NONE,
