@@ -1,6 +1,7 @@
 """The perceptual-encoder stage of a training step, stated once for the actor-critic step (engine.py), the relay-imitation
-step (modules/relay_imitation_learning/engine.py) and the PlayLMP step (modules/play_lmp/play_lmp_for_rl.py): image slots,
-which kernels apply, the packed conv weights, which cameras share a launch, and the forward / backward dispatch.
+step (modules/relay_imitation_learning/engine.py) and the PlayLMP step (modules/play_lmp/play_lmp_for_rl.py): which
+kernels apply, the packed conv weights, which cameras share a launch, and the forward / backward dispatch.  It begins at the
+NHWC image buffers that image_ingest.py fills.
 
 An encoder problem is the 7-tuple (image pointer, parameter block, out, act, images, needs_backward, camera); a parameter
 block is anything with `.param` (the flat fp32 tensor) and `.enc(camera[, flat])` (address of that camera's encoder in it).
@@ -19,33 +20,7 @@ def image_flag(img_dtype):
     return BF16 if img_dtype == torch.bfloat16 else F32
 
 
-# ------------------------------------------------------------------- 1. slot packing
-def pack_slots(X3, slots, B, hw, srcs, nchw, img_dtype):
-    """Images of one camera into slots of its NHWC image buffer X3 (slot i = rows [i*B, (i+1)*B)).  srcs[j] -> slot slots[j]:
-    (B,3,H,W) [nchw] or (B,H,W,3) fp32 device tensors, or the dataset's uint8 (B,H,W,3) frames (ToTensor + Normalize(0.5,
-    0.5) applied by the pack: bit-identical to the host-transformed fp32 route, a quarter of the bytes); strided views with a
-    uniform image pitch (states[:, 0]) are taken as they are.  One vectorised launch for all slots where the alignment allows."""
-    H, W = hw
-    xd, esz, img = image_flag(img_dtype), X3.element_size(), H * W * 3
-    u8 = srcs[0].dtype == torch.uint8
-    jobs = []
-    for i, t in zip(slots, srcs):
-        assert t.is_cuda and t.dtype == (torch.uint8 if u8 else torch.float32) and t[0].is_contiguous() and t.shape[0] == B
-        assert tuple(t.shape[-3:]) == ((H, W, 3) if (u8 or not nchw) else (3, H, W)), (tuple(t.shape), (H, W))
-        pitch = t.stride(0) if t.shape[0] > 1 else img
-        jobs.append((t.data_ptr(), pitch, X3.data_ptr() + i * B * img * esz, B))
-    if u8:
-        if img % 16 or any(j[0] % 16 or j[1] % 16 for j in jobs):
-            raise ValueError("uint8 frames: H*W*3 and the image pitch must be multiples of 16, tensors 16-byte aligned")
-        ops.pack_images_u8_batch(jobs, xd, H, W)
-    elif nchw and (H * W) % 4 == 0 and all(j[0] % 16 == 0 and j[1] % 4 == 0 for j in jobs):
-        ops.pack_images_batch(jobs, xd, H, W)
-    else:
-        for src, pitch, dst, n_ in jobs:
-            call("tacorl_pack_images", src, pitch, int(nchw), dst, xd, n_, 3, H, W, ops.stream())
-
-
-# ------------------------------------------------------------- 2. which kernels apply
+# ------------------------------------------------------------- 1. which kernels apply
 def fused_fwd_ok(hw, compute, img_dtype):
     """The fused single-launch forward: bf16 images + bf16 MFMA + a templated camera geometry."""
     return compute == BF16 and img_dtype == torch.bfloat16 and bool(ops.L.lib().tacorl_encoder_fused_supported(*hw))
@@ -65,7 +40,7 @@ def fused_saves(hw, compute, img_dtype, n_imgs):
         fused_fwd_ok(hw, compute, img_dtype) and ops.L.lib().tacorl_encoder_fused_act_format(*hw) == 2)
 
 
-# ------------------------------------------------------------ 3. packed conv weights
+# ------------------------------------------------------------ 2. packed conv weights
 class PackedWeights:
     """Packed conv weights of the fused encoder forward (bf16 MFMA fragments in the kernel's register order), one buffer per
     (parameter block, camera).
@@ -112,7 +87,7 @@ class PackedWeights:
             self.ver[(b, c)] = b.param._version
 
 
-# ---------------------------------------------------------------- 4. geometry grouping
+# ---------------------------------------------------------------- 3. geometry grouping
 def geometry_groups(cams, hw, ok, n_problems, limit):
     """Cameras that share ONE launch (sequence): the cameras of one geometry for which ok(c) holds, when their problems
     together - n_problems(c) each - fit `limit` (EF_MAXP forward: C4's two 128 x 128 cameras, 7 problems each, are one launch
@@ -129,7 +104,7 @@ def geometry_groups(cams, hw, ok, n_problems, limit):
     return out
 
 
-# ---------------------------------------------------------------- 5. forward dispatch
+# ---------------------------------------------------------------- 4. forward dispatch
 def launch_fused(pr, packs, hw, max_wg=0):
     """One fused encoder launch over the problems pr (each carries its camera: cameras of one geometry may share a launch)
     on at most max_wg workgroups (0: one per CU); activations are saved only for the problems a backward follows."""

@@ -17,6 +17,7 @@ import torch
 
 from . import blocks, ops
 from . import encoder_stage as stage
+from . import image_ingest as ingest
 from . import dist as D
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, BF16, F32, LOG_SLOTS, call, ptr
 
@@ -305,7 +306,7 @@ class ACEngine:
         uniform image pitch, e.g. states[:,0]); the images of a role the camera does not have are not read (None)."""
         given = {"obs": obs, "goal": goal, "next": nxt}
         sl = self.slot[cam]
-        stage.pack_slots(self.X3[cam], list(sl.values()), self.B, self.hw[cam], [given[s_] for s_ in sl], nchw, self.img_dtype)
+        ingest.pack_slots(self.X3[cam], list(sl.values()), self.B, self.hw[cam], [given[s_] for s_ in sl], nchw, self.img_dtype)
 
     def load_transition(self, action, reward, done):
         self.action.copy_(action.reshape(self.B, self.A).float())

@@ -10,8 +10,8 @@ from typing import List
 import torch
 import torch.nn as nn
 
-from ... import _lib
 from ... import dist as _D
+from ... import image_ingest as ingest
 from ...engine import ACEngine
 from ...lightning import LightningModuleBase
 from ..common import GraphMixin, ModuleMixin, broadcast_blocks, register_views, to_plain
@@ -196,50 +196,31 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         cameras of goal_modalities only (reference visual_actor_wrapper.py:41-62): whatever else the batch carries is
         ignored, and images of a role a camera does not have need not be there."""
         e = self.engine
-        B = action.shape[0]
-        hw = {}
-        if obs[e.cams[0]].dtype == torch.uint8:  # the dataset's uint8 HWC frames: normalised on the GPU (engine.load_images)
-            nchw = False
-        for c in e.enc_cams:
-            t = obs[c] if c in e.cams else goal[c]
-            hw[c] = tuple(t.shape[-2:]) if nchw else tuple(t.shape[-3:-1])
-        e.ensure_batch(B, hw)
+        f = ingest.transition_form({c: obs[c] if c in e.cams else goal[c] for c in e.enc_cams}, nchw)
+        e.ensure_batch(action.shape[0], f.hw)
         for c in e.enc_cams:
             o, g, nx = (obs[c] if c in e.cams else None, goal[c] if c in e.goal_cams else None, nxt[c] if c in e.cams else None)
-            e.load_images(c, *(None if t is None else t.to(self.dev) for t in (o, g, nx)), nchw=nchw)
+            e.load_images(c, *(None if t is None else t.to(self.dev) for t in (o, g, nx)), nchw=f.form == "f32_nchw")
         e.load_transition(action.to(self.dev), reward.to(self.dev), done.to(self.dev))
         e.set_noise(noise)
 
-    def _stage_u8(self, B, src_hw, jobs_of, aug, action, reward, done, noise):
-        """uint8 frames into the engine's image slots by the gathering / augmenting pack.  jobs_of(cam, role) -> (source
-        pointer, bytes per source frame, index pointer or None): the dataset and an id table (the fused replay batch), or a
-        gathered (B,H,W,3) tensor.  Obs and next images are packed for the cameras of obs_modalities only, goal images for the
-        cameras of goal_modalities only, into the slots engine.slot[cam] defines; aug (None: the plain normalising pack) holds
-        per role and camera the shift / jitter tables, the pad and, optionally, the encoders' geometry (`resize`)."""
-        from ... import ops
-
-        e = self.engine
-        rs = (aug or {}).get("resize") or {}
-        hw = {c: tuple(rs.get(c, src_hw[c])) for c in e.enc_cams}
-        e.ensure_batch(B, hw)
-        xd = _lib.BF16 if self.img_dtype == torch.bfloat16 else _lib.F32
+    def _stage_u8(self, f, jobs_of, action, reward, done, noise):
+        """uint8 frames into the engine's image slots engine.slot[cam] by the gathering / augmenting pack: obs and next for the
+        cameras of obs_modalities only, goal for those of goal_modalities only.  f: the batch form (f.aug None: the plain
+        normalising pack); jobs_of(cam, role) -> (source address, bytes per source frame, index address or None): the dataset
+        and an id table (the fused replay batch), or a gathered (B,H,W,3) tensor."""
+        e, B, aug = self.engine, f.B, f.aug
+        e.ensure_batch(B, f.hw)
         for c in e.enc_cams:
-            (H, W), (Hs, Ws) = hw[c], src_hw[c]
-            esz, ob = e.X3[c].element_size(), 3 * H * W  # (ob: elements per packed image)
+            slot = B * 3 * f.hw[c][0] * f.hw[c][1] * e.X3[c].element_size()  # bytes of one role's packed images
             jobs = []
             for role, k in e.slot[c].items():  # obs / goal / next, as far as the camera has the role
                 src, fb, ip = jobs_of(c, role)
-                if fb != 3 * Hs * Ws or fb % 16 or src % 16:
-                    raise ValueError("uint8 frames: H*W*3 must be a multiple of 16 and the tensor 16-byte aligned")
-                job = (src, fb, e.X3[c].data_ptr() + k * B * ob * esz, B, ip, 1)
-                if aug is not None:
-                    t = aug[role][c]
-                    job += (t.get("shift"), t.get("jitter"))
-                jobs.append(job)
-            if aug is None:
-                ops.pack_images_u8_gather_batch(jobs, xd, H, W)
-            else:
-                ops.pack_images_u8_resize_aug_batch(jobs, xd, (Hs, Ws), H, W, aug["pad"][c])
+                if fb != 3 * f.src_hw[c][0] * f.src_hw[c][1]:
+                    raise ValueError(f"uint8 frames: camera {c}'s {role} frames are not of the camera's frame size")
+                t = aug[role][c] if aug is not None else {}
+                jobs.append(ingest.PackJob(src, fb, e.X3[c].data_ptr() + k * slot, B, ip, 1, t.get("shift"), t.get("jitter")))
+            ingest.pack(jobs, f.form, self.img_dtype, f.src_hw[c], f.hw[c], aug["pad"][c] if aug is not None else None)
         e.load_transition(action, reward, done)
         e.set_noise(noise)
 
@@ -247,17 +228,15 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         """The fused transition-replay batch: every image is read by frame id straight out of the resident dataset."""
         rp = batch["replay"]
         B, ids, frames = rp["B"], rp["ids"], rp["frames"]
-        if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == 3 * B):
-            raise ValueError("transition replay batch: ids must be a contiguous device int64 (3, B) table")
         row = {"obs": 0, "next": 1, "goal": 2}  # the id table's rows: [step | step + 1 | goal]
         e = self.engine
         for c in e.enc_cams:
             v = frames.get(c)
             if v is None or not (v.is_cuda and v.is_contiguous() and v.dtype == torch.uint8 and v.dim() == 4):
                 raise ValueError(f"transition replay batch: camera {c} needs a contiguous device uint8 (N,H,W,3) dataset")
-        self._stage_u8(B, {c: tuple(frames[c].shape[1:3]) for c in e.enc_cams},
-                       lambda c, role: (frames[c].data_ptr(), frames[c][0].numel(), ids.data_ptr() + 8 * B * row[role]),
-                       batch.get("aug"), action, reward, done, noise)
+        f = ingest.transition_form({c: frames[c] for c in e.enc_cams}, aug=batch.get("aug"), replay=rp)
+        self._stage_u8(f, lambda c, role: (frames[c].data_ptr(), frames[c][0].numel(), ids.data_ptr() + 8 * B * row[role]),
+                       action, reward, done, noise)
 
     def _stage_gathered_aug(self, obs, goal, nxt, aug, action, reward, done, noise):
         """The gathered uint8 batch with augmentation tables: the same pack, reading image i of each tensor."""
@@ -269,10 +248,9 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
                 t = given[role][c]
                 if t.dtype != torch.uint8 or not (t.is_cuda and t.is_contiguous()):
                     raise ValueError("batch['aug'] needs the dataset's uint8 frames on the device (the augmentation is part of the uint8 pack)")
-        B = action.shape[0]
-        self._stage_u8(B, {c: tuple(given[roles[c][0]][c].shape[-3:-1]) for c in e.enc_cams},
-                       lambda c, role: (given[role][c].data_ptr(), given[role][c][0].numel(), None),
-                       aug, action.to(self.dev), reward.to(self.dev), done.to(self.dev), noise)
+        f = ingest.transition_form({c: given[roles[c][0]][c] for c in e.enc_cams}, aug=aug)
+        self._stage_u8(f, lambda c, role: (given[role][c].data_ptr(), given[role][c][0].numel(), None),
+                       action.to(self.dev), reward.to(self.dev), done.to(self.dev), noise)
 
     def compute_update(self, batch, optimize: bool = True, log_type: str = "train", noise=None):
         obs, action, nxt, reward, done = batch

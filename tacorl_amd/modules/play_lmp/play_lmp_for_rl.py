@@ -206,35 +206,19 @@ def _playlmp_ensure(self, B, T, hw):
 
 def _playlmp_step(self, batch, noise=None, optimize=True, log_type="train", nchw=True):
     """PlayLMP.training_step + the single Adam (reference play_lmp_for_rl.py:200-257,307-317,362-368)."""
+    from ... import image_ingest as ingest
     from ... import ops
-    from ..._lib import BF16, F32, call, ptr
     from ...data.replay import wait_ready
 
     wait_ready(batch)  # a replay batch's small tables travel on the feeder's copy stream
-    rp = batch.get("replay")  # frames by index out of a uint8 dataset (data/replay.py HbmReplay.batch(fused=True))
-    states = rp["frames"] if rp is not None else batch["states"]
+    f = ingest.window_form(batch, nchw)
+    B, T, hw = f.B, f.T, f.hw
     cams, net, pr, ad = self.plan_proposal_obs_modalities, self.net, self.pr, self.ad
     opts = getattr(self, "_optimizers", None)
     if opts and opts[0].lr != self.lr:  # lr edited on the optimiser (scheduler): a launch argument -> new captures
         self.lr, self._graphs = opts[0].lr, {}
-    if rp is not None:
-        B, T, u8, nchw = rp["B"], rp["T"], True, False
-        hw = {c: tuple(v.shape[1:3]) for c, v in states.items()}
-    else:
-        B, T = next(iter(states.values())).shape[:2]
-        u8 = next(iter(states.values())).dtype == torch.uint8  # the dataset's uint8 HWC frames: normalised by the pack
-        if u8:
-            nchw = False
-        hw = {c: (tuple(v.shape[-2:]) if nchw else tuple(v.shape[-3:-1])) for c, v in states.items()}
-    src_hw = dict(hw)  # the frames as stored; an augmentation spec with a Resize stage sets the encoders' geometry
-    rs = (batch.get("aug") or {}).get("resize") or {}
-    if rs:
-        if not u8:
-            raise ValueError("aug['resize'] needs the dataset's uint8 frames (the resize is part of the uint8 pack)")
-        hw = {c: tuple(rs.get(c, hw[c])) for c in hw}
     _playlmp_ensure(self, B, T, hw)
-    R, Ec, A, cd = B * T, 32 * len(cams), pr.A, self.compute
-    xd = BF16 if self.img_dtype == torch.bfloat16 else F32
+    R = B * T
     gs = 1.0 / getattr(self, "world_size", 1)
     for k, buf in self.noise.items():
         if noise is not None:
@@ -249,35 +233,13 @@ def _playlmp_step(self, batch, noise=None, optimize=True, log_type="train", nchw
     if self._pr_train:
         pr.stage_dropout(B, T, noise.get("dropout") if noise is not None else None)
     # ---- eager staging: frames into the fixed NHWC buffers, actions into a fixed buffer
-    for c in cams:
-        H, W = hw[c]
-        v = states[c].to(self.dev)
-        aug = batch.get("aug") if u8 else None
-        Hs, Ws = src_hw[c]
-        if rp is not None:  # window frames by index straight out of the dataset: gather + pack in one pass
-            ids = rp["ids"]
-            job = (v.data_ptr(), 3 * Hs * Ws, self.frames[c].data_ptr(), R, ids.data_ptr(), 1)
-            if aug is None:
-                ops.pack_images_u8_gather_batch([job], xd, H, W)
-            else:
-                st = aug["states"][c]
-                flat = lambda t: None if t is None else t.reshape(R, t.shape[-1]).contiguous()  # noqa: E731
-                ops.pack_images_u8_resize_aug_batch([job + (flat(st.get("shift")), flat(st.get("jitter")))], xd, (Hs, Ws), H, W,
-                                                    aug["pad"][c])
-        elif aug is not None:  # train-time augmentations on the way in, draws as device tables
-            st = aug["states"][c]
-            flat = lambda t: None if t is None else t.reshape(R, t.shape[-1]).contiguous()  # noqa: E731
-            ops.pack_images_u8_resize_aug_batch([(v.data_ptr(), 3 * Hs * Ws, self.frames[c].data_ptr(), R, None, 1,
-                                                  flat(st.get("shift")), flat(st.get("jitter")))], xd, (Hs, Ws), H, W,
-                                                aug["pad"][c])
-        elif u8:
-            if (H * W * 3) % 16 or v.data_ptr() % 16 or not v.is_contiguous():
-                raise ValueError("uint8 frames: contiguous, 16-byte aligned, H*W*3 a multiple of 16")
-            ops.pack_images_u8_batch([(v.data_ptr(), 3 * H * W, self.frames[c].data_ptr(), R)], xd, H, W)
-        elif nchw and (H * W) % 4 == 0 and v.data_ptr() % 16 == 0:
-            ops.pack_images_batch([(v.data_ptr(), 3 * H * W, self.frames[c].data_ptr(), R)], xd, H, W)
-        else:
-            call("tacorl_pack_images", ptr(v), 3 * H * W, int(nchw), ptr(self.frames[c]), xd, R, 3, H, W, ops.stream())
+    for c in cams:  # the job: the window into self.frames[c] (by index straight out of the dataset: gather + pack in one pass)
+        v = f.frames[c].to(self.dev)
+        if not v.is_contiguous():
+            raise ValueError("window frames must be contiguous")
+        job = ingest.PackJob(v.data_ptr(), 3 * f.src_hw[c][0] * f.src_hw[c][1], self.frames[c].data_ptr(), R,
+                             None if f.ids is None else f.ids.data_ptr(), 1, **ingest.window_tables(f.aug, c, "window", T))
+        ingest.pack([job], f.form, self.img_dtype, f.src_hw[c], hw[c], f.aug["pad"][c] if f.aug is not None else None)
     if getattr(self, "_acts", None) is None or self._acts.shape != batch["actions"].shape:
         ops.note_alloc()
         self._acts = torch.zeros(*batch["actions"].shape, device=self.dev)
@@ -370,11 +332,11 @@ def _playlmp_pp_forward(self, B, T, Ec, A, cd):
 def _playlmp_fwd_bwd(self, B, T, hw, acts, gs):
     """Device side of the PlayLMP step up to the gradients (fixed buffers only: hipGraph-capturable)."""
     from ... import ops
-    from ..._lib import BF16, F32, call, ptr
+    from ..._lib import BF16, call, ptr
 
     cams, net, pr, ad = self.plan_proposal_obs_modalities, self.net, self.pr, self.ad
     R, Ec, A, cd = B * T, 32 * len(cams), pr.A, self.compute
-    xd = BF16 if self.img_dtype == torch.bfloat16 else F32
+    xd = stage.image_flag(self.img_dtype)
     ops.mark("start")
     for j, c in enumerate(cams):
         H, W = hw[c]

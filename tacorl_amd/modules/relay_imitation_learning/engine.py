@@ -17,6 +17,7 @@ import torch
 
 from ... import blocks, ops
 from ... import encoder_stage as stage
+from ... import image_ingest as ingest
 from ... import dist as D
 from ..._lib import ACT_NONE, ACT_RELU, ACT_SILU, ACT_TANH, BF16, F32, call, ptr
 
@@ -156,7 +157,7 @@ class RILEngine:
     def load_images(self, cam, imgs, nchw=True):
         """imgs: the four slots' images in SLOTS order, each (B,3,H,W) fp32 [nchw], (B,H,W,3) fp32, or the dataset's
         uint8 (B,H,W,3) frames (ToTensor + Normalize(0.5, 0.5) applied by the pack, as ACEngine.load_images)."""
-        stage.pack_slots(self.X3[cam], range(len(SLOTS)), self.B, self.hw[cam], imgs, nchw, self.img_dtype)
+        ingest.pack_slots(self.X3[cam], range(len(SLOTS)), self.B, self.hw[cam], imgs, nchw, self.img_dtype)
 
     def load_action(self, action):
         self.action.copy_(action.reshape(self.B, self.A_low).float())

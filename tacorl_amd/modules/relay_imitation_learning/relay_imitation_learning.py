@@ -15,6 +15,7 @@ from typing import List
 import torch
 
 from ... import dist as _D
+from ... import image_ingest as ingest
 from ...lightning import LightningModuleBase
 from ..common import GraphMixin, ModuleMixin, broadcast_blocks, register_views, to_plain
 from .engine import SLOTS, RILEngine
@@ -90,13 +91,10 @@ class RelayImitationLearning(GraphMixin, ModuleMixin, LightningModuleBase):
         """The four image roles of every camera of the union and the low-level action; fp32 NCHW tensors, or the
         dataset's uint8 HWC frames (normalised on the GPU, as CQL_Offline._stage)."""
         e = self.engine
-        first = batch[SLOTS[0]][e.cams[0]]
-        if first.dtype == torch.uint8:
-            nchw = False
-        hw = {c: (tuple(batch[SLOTS[0]][c].shape[-2:]) if nchw else tuple(batch[SLOTS[0]][c].shape[-3:-1])) for c in e.cams}
-        e.ensure_batch(first.shape[0], hw)
+        f = ingest.transition_form({c: batch[SLOTS[0]][c] for c in e.cams}, nchw)
+        e.ensure_batch(f.B, f.hw)
         for c in e.cams:
-            e.load_images(c, [batch[s][c].to(self.dev) for s in SLOTS], nchw=nchw)
+            e.load_images(c, [batch[s][c].to(self.dev) for s in SLOTS], nchw=f.form == "f32_nchw")
         e.load_action(batch["low_level_action"].to(self.dev))
 
     def compute_loss(self, batch, stage: str = "train", optimize: bool = True):

@@ -11,8 +11,10 @@ import torch
 import torch.nn as nn
 
 from ... import dist as D
+from ... import image_ingest as ingest
 from ... import ops
-from ..._lib import BF16, F32, call, ptr
+from ..._lib import call, ptr
+from ...encoder_stage import image_flag
 from ..common import register_views
 from ..cql.cql_offline_lightning import CQL_Offline
 
@@ -146,29 +148,12 @@ class TACORL(CQL_Offline):
         from ...data.replay import wait_ready
 
         wait_ready(batch)  # a replay batch's small tables travel on the feeder's copy stream
-        rp = batch.get("replay")  # frames by index out of a uint8 dataset (data/replay.py HbmReplay.batch(fused=True))
-        if rp is not None:
-            u8, nchw, B, T = True, False, rp["B"], rp["T"]
-            states = rp["frames"]
-            hw = {c: tuple(v.shape[1:3]) for c, v in states.items()}
-        else:
-            states = batch["states"]
-            u8 = next(iter(states.values())).dtype == torch.uint8
-            if u8:
-                nchw = False
-            B, T = next(iter(states.values())).shape[:2]
-            hw = {c: (tuple(v.shape[-2:]) if nchw else tuple(v.shape[-3:-1])) for c, v in states.items()}
-        src_hw = dict(hw)  # the frames as stored; an augmentation spec with a Resize stage sets the encoders' geometry
-        rs = (batch.get("aug") or {}).get("resize") or {}
-        if rs:
-            if not u8:
-                raise ValueError("aug['resize'] needs the dataset's uint8 frames (the resize is part of the uint8 pack)")
-            hw = {c: tuple(rs.get(c, hw[c])) for c in hw}
+        f = ingest.window_form(batch, nchw)
+        B, T, hw, aug = f.B, f.T, f.hw, f.aug
         self.engine.extra_normal = {"eps_pr": (B, self.action_dim)}  # drawn with the engine's noise (one launch)
         self.engine.ensure_batch(B, {c: hw[c] for c in self.engine.cams})
         self.eps_pr = self.engine.extra_noise["eps_pr"]
         self._ensure_seq(B, T, hw)
-        xd = BF16 if self.img_dtype == torch.bfloat16 else F32
         e = self.engine
         if self.ad is not None and (getattr(self, "acts", None) is None or self.acts.shape[:2] != (B, T)):
             ops.note_alloc()
@@ -182,86 +167,31 @@ class TACORL(CQL_Offline):
         side.wait_stream(main)  # the previous step's graph read these buffers
         with torch.cuda.stream(side):
             self._stage_small(batch, noise, B, T)
-        # get_rl_batch (tacorl.py:142-179) as strided views: s = states[:,0], s' = states[:,-1]
+        u8, Job, ip = f.form in ingest.U8_FORMS, ingest.PackJob, None if f.ids is None else f.ids.data_ptr()
         for c in sorted(set(self.all_modalities) | set(e.cams)):
-            H, W = hw[c]
-            v = states[c]
-            sz = 1 if u8 else 4  # bytes per source element
+            v = f.frames[c]
             assert v.is_cuda and v.is_contiguous() and v.dtype == (torch.uint8 if u8 else torch.float32)
-            if rp is not None:
-                # image i of a job = dataset frame ids[i * stride]: the window (stride 1), obs = ids[b T], goal = the table's
-                # tail, next = ids[b T + T - 1] - gather and pack in one pass over the dataset
-                Hs, Ws = src_hw[c]
-                ids, fb = rp["ids"], 3 * Hs * Ws
-                assert ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == B * T + B
-                ip = ids.data_ptr()
-                jobs = [(v.data_ptr(), fb, self.frames[c].data_ptr(), B * T, ip, 1)] if c in self.all_modalities else []
-                if c in e.cams:
-                    esz, x3, ob = e.X3[c].element_size(), e.X3[c].data_ptr(), 3 * H * W  # (ob: elements per packed image)
-                    jobs += [(v.data_ptr(), fb, x3, B, ip, T), (v.data_ptr(), fb, x3 + B * ob * esz, B, ip + 8 * B * T, 1),
-                             (v.data_ptr(), fb, x3 + 2 * B * ob * esz, B, ip + 8 * (T - 1), T)]
-                if fb % 16 or v.data_ptr() % 16:
-                    raise ValueError("uint8 dataset: H*W*3 must be a multiple of 16 and the tensor 16-byte aligned")
-                aug = batch.get("aug")
-                if aug is None:
-                    ops.pack_images_u8_gather_batch(jobs, xd, H, W)
-                else:
-                    st, gl = aug["states"][c], aug["goal"][c]
-                    sh, ji = st.get("shift"), st.get("jitter")
-                    row = lambda t, k: None if t is None else t[:, k].contiguous()  # noqa: E731
-                    flat = lambda t: None if t is None else t.reshape(B * T, t.shape[-1]).contiguous()  # noqa: E731
-                    tabs = [(flat(sh), flat(ji))] if c in self.all_modalities else []
-                    if c in e.cams:
-                        tabs += [(row(sh, 0), row(ji, 0)), (gl.get("shift"), gl.get("jitter")), (row(sh, T - 1), row(ji, T - 1))]
-                    ops.pack_images_u8_resize_aug_batch([j + t for j, t in zip(jobs, tabs)], xd, (Hs, Ws), H, W, aug["pad"][c])
-                continue
-            Hs, Ws = src_hw[c]
-            simg = 3 * Hs * Ws  # elements of a source frame
-            jobs = [(v.data_ptr(), simg, self.frames[c].data_ptr(), B * T)] if c in self.all_modalities else []
-            if c in e.cams:
-                g = batch["goal"][c]
-                assert g.is_cuda and g.is_contiguous() and g.dtype == v.dtype
-                esz, img = e.X3[c].element_size(), H * W * 3
-                x3 = e.X3[c].data_ptr()
-                jobs += [(v.data_ptr(), T * simg, x3, B), (g.data_ptr(), simg, x3 + B * img * esz, B),
-                         (v.data_ptr() + sz * (T - 1) * simg, T * simg, x3 + 2 * B * img * esz, B)]
-            aug = batch.get("aug") if u8 else None
-            if aug is not None:
-                # train-time augmentations on the way in: the draws arrive as device tables; the obs / next
-                # frames of the transition take the draws of window frames 0 / T-1, as in the reference, where the
-                # transform ran once per window in the dataset
-                st, gl = aug["states"][c], aug["goal"][c]
-                sh, ji = st.get("shift"), st.get("jitter")
-                row = lambda t, k: None if t is None else t[:, k].contiguous()  # noqa: E731
-                flat = lambda t: None if t is None else t.reshape(B * T, t.shape[-1]).contiguous()  # noqa: E731
-                tabs = [(flat(sh), flat(ji))] if c in self.all_modalities else []
-                if c in e.cams:
-                    tabs += [(row(sh, 0), row(ji, 0)), (gl.get("shift"), gl.get("jitter")), (row(sh, T - 1), row(ji, T - 1))]
-                ops.pack_images_u8_resize_aug_batch([j + (None, 1) + t for j, t in zip(jobs, tabs)], xd, (Hs, Ws), H, W,
-                                                    aug["pad"][c])
-            elif u8:
-                if (H * W * 3) % 16 or any(j[0] % 16 for j in jobs):
-                    raise ValueError("uint8 frames: H*W*3 must be a multiple of 16 and the tensors 16-byte aligned")
-                ops.pack_images_u8_batch(jobs, xd, H, W)  # pitches are in bytes = elements
-            elif nchw and (H * W) % 4 == 0:  # one launch for the window frames and the obs / goal / next images
-                import ctypes as C
-                if c in self.all_modalities and c in e.cams and len(jobs) == 4 and T >= 2:
-                    # obs = window frame 0 and next = window frame T - 1 (get_rl_batch): written from the one read of the
-                    # window; the goal image stays a job of its own
-                    win, _, goal, _ = jobs
-                    x3, img_b = e.X3[c].data_ptr(), H * W * 3 * e.X3[c].element_size()
-                    js = [win, goal]
-                    call("tacorl_pack_images_window_batch", 2, (C.c_void_p * 2)(*[j[0] for j in js]),
-                         (C.c_long * 2)(*[j[1] for j in js]), (C.c_void_p * 2)(*[j[2] for j in js]),
-                         ops.int_array([j[3] for j in js]), (C.c_void_p * 2)(x3, None), (C.c_void_p * 2)(x3 + 2 * B * img_b, None),
-                         ops.int_array([T, 0]), xd, H, W, ops.stream())
-                    continue
-                call("tacorl_pack_images_batch", len(jobs), (C.c_void_p * len(jobs))(*[j[0] for j in jobs]),
-                     (C.c_long * len(jobs))(*[j[1] for j in jobs]), (C.c_void_p * len(jobs))(*[j[2] for j in jobs]),
-                     ops.int_array([j[3] for j in jobs]), xd, H, W, ops.stream())
+            src, simg = v.data_ptr(), 3 * f.src_hw[c][0] * f.src_hw[c][1]  # (simg: elements of a source frame)
+            jobs, roles = [], []
+            if c in self.all_modalities:  # a camera's jobs: the window into self.frames ...
+                jobs, roles = [Job(src, simg, self.frames[c].data_ptr(), B * T, ip, 1)], ["window"]
+            if c in e.cams:  # ... and s = states[:,0], the goal, s' = states[:,-1] (get_rl_batch, tacorl.py:142-179) into X3's slots
+                x3, slot = e.X3[c].data_ptr(), B * 3 * hw[c][0] * hw[c][1] * e.X3[c].element_size()
+                if ip is not None:  # by index (ids[i * stride]): obs = ids[b T], goal = the table's tail, next = ids[b T + T - 1]
+                    jobs += [Job(src, simg, x3, B, ip, T), Job(src, simg, x3 + slot, B, ip + 8 * B * T, 1),
+                             Job(src, simg, x3 + 2 * slot, B, ip + 8 * (T - 1), T)]
+                else:  # strided views of the window
+                    g = batch["goal"][c]
+                    assert g.is_cuda and g.is_contiguous() and g.dtype == v.dtype
+                    jobs += [Job(src, T * simg, x3, B), Job(g.data_ptr(), simg, x3 + slot, B),
+                             Job(src + v.element_size() * (T - 1) * simg, T * simg, x3 + 2 * slot, B)]
+                roles += ["obs", "goal", "next"]
+            if aug is not None:  # train-time augmentations on the way in: the draws arrive as device tables
+                jobs = [j._replace(**ingest.window_tables(aug, c, r, T)) for j, r in zip(jobs, roles)]
+            if len(jobs) == 4 and T >= 2 and ingest.vector_ok(jobs, f.form, hw[c]):
+                ingest.pack_window(jobs, T, self.img_dtype, hw[c])  # one read of the window for its frames, obs and next
             else:
-                for src, pitch, dst, n in jobs:
-                    call("tacorl_pack_images", src, pitch, int(nchw), dst, xd, n, 3, H, W, ops.stream())
+                ingest.pack(jobs, f.form, self.img_dtype, f.src_hw[c], hw[c], aug["pad"][c] if aug is not None else None)
         main.wait_stream(side)
         return B, T, hw
 
@@ -386,7 +316,7 @@ class TACORL(CQL_Offline):
     def get_pr_latent_plan(self, batch, noise=None, nchw=True):
         """reference tacorl.py:235-252 (no_grad / eval): returns the sampled latent plan (device tensor)."""
         B, T, hw = self._stage_frames(batch, noise, nchw)
-        xd = BF16 if self.img_dtype == torch.bfloat16 else F32
+        xd = image_flag(self.img_dtype)
         for c in self.all_modalities:
             H, W = hw[c]
             call("tacorl_encoder_fwd", 1, ops.ptr_array([self.frames[c]]), ops.ptr_array([self.lmp_net.enc(c)]),

@@ -239,56 +239,53 @@ def pack_images(src, img_pitch, src_nchw, dst, n, Cc, H, W, src_offset=0):
          n, Cc, H, W, stream())
 
 
+# A pack job is (src, pitch, dst, n, index, stride, shift, jitter) - image_ingest.PackJob, which is built from this list and
+# documents the fields - or a plain tuple of the leading fields.
+JOB_FIELDS = ("src", "pitch", "dst", "n", "index", "stride", "shift", "jitter")
+_JOB_ARRAY = {"src": C.c_void_p, "dst": C.c_void_p, "index": C.c_void_p, "pitch": C.c_long, "n": C.c_int, "stride": C.c_int}
+
+
+def job_arrays(jobs, *fields):
+    """One ctypes array per named field of the pack jobs: addresses, pitches and counts as they stand, the augmentation
+    tables `shift` / `jitter` (device tensors or None) as their addresses."""
+    col, k = dict(zip(JOB_FIELDS, zip(*jobs))), len(jobs)
+    return [(_JOB_ARRAY[f] * k)(*col[f]) if f in _JOB_ARRAY else ptr_array(col[f]) for f in fields]
+
+
 def pack_images_batch(jobs, dst_dtype_flag, H, W):
-    """jobs: [(src_ptr, image_pitch_elems, dst_ptr, n_images)], NCHW fp32 (C = 3) -> NHWC, one launch
-    (H*W % 4 == 0, 16-byte aligned pointers, pitches % 4 == 0)."""
-    k = len(jobs)
-    call("tacorl_pack_images_batch", k, (C.c_void_p * k)(*[j[0] for j in jobs]), (C.c_long * k)(*[j[1] for j in jobs]),
-         (C.c_void_p * k)(*[j[2] for j in jobs]), int_array([j[3] for j in jobs]), dst_dtype_flag, H, W, stream())
+    """NCHW fp32 (C = 3) -> NHWC, one launch (H*W % 4 == 0, 16-byte aligned pointers, pitches % 4 == 0)."""
+    call("tacorl_pack_images_batch", len(jobs), *job_arrays(jobs, "src", "pitch", "dst", "n"), dst_dtype_flag, H, W, stream())
 
 
 def pack_images_u8_batch(jobs, dst_dtype_flag, H, W):
-    """jobs: [(src_ptr, image_pitch_bytes, dst_ptr, n_images)], uint8 HWC frames -> normalised NHWC, one launch."""
-    k = len(jobs)
-    call("tacorl_pack_images_u8_batch", k, (C.c_void_p * k)(*[j[0] for j in jobs]), (C.c_long * k)(*[j[1] for j in jobs]),
-         (C.c_void_p * k)(*[j[2] for j in jobs]), int_array([j[3] for j in jobs]), dst_dtype_flag, H, W, stream())
+    """uint8 HWC frames -> normalised NHWC, one launch."""
+    call("tacorl_pack_images_u8_batch", len(jobs), *job_arrays(jobs, "src", "pitch", "dst", "n"), dst_dtype_flag, H, W, stream())
 
 
 def pack_images_u8_aug_batch(jobs, dst_dtype_flag, H, W, pad):
-    """jobs: [(src_ptr, image_pitch_bytes, dst_ptr, n_images, shift int32 (n,2) or None, jitter f32 (n,8) or None)]:
-    uint8 HWC frames -> RandomShiftsAug -> /255 -> ColorJitter -> Normalize -> NHWC, one launch."""
-    k = len(jobs)
+    """jobs: [(src, image_pitch_bytes, dst, n_images, shift int32 (n,2) or None, jitter f32 (n,8) or None)] - this entry point
+    has no index: uint8 HWC frames -> RandomShiftsAug -> /255 -> ColorJitter -> Normalize -> NHWC, one launch."""
     for j in jobs:
         for t, dt in ((j[4], torch.int32), (j[5], torch.float32)):
             assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.shape[0] == j[3])
-    call("tacorl_pack_images_u8_aug_batch", k, (C.c_void_p * k)(*[j[0] for j in jobs]), (C.c_long * k)(*[j[1] for j in jobs]),
-         (C.c_void_p * k)(*[j[2] for j in jobs]), ptr_array([j[4] for j in jobs]), ptr_array([j[5] for j in jobs]),
-         int_array([j[3] for j in jobs]), dst_dtype_flag, H, W, int(pad), stream())
+    call("tacorl_pack_images_u8_aug_batch", len(jobs), *job_arrays([tuple(j[:4]) + (None, 1) + tuple(j[4:]) for j in jobs],
+                                                                   "src", "pitch", "dst", "shift", "jitter", "n"),
+         dst_dtype_flag, H, W, int(pad), stream())
 
 
 def pack_images_u8_resize_aug_batch(jobs, dst_dtype_flag, src_hw, H, W, pad):
-    """jobs: [(src_ptr, source_frame_bytes, dst_ptr, n_images, index_ptr or None, index_stride, shift or None, jitter or
-    None)]: uint8 HWC source frames of size src_hw -> Resize(H, W) -> RandomShiftsAug(pad) -> /255 -> ColorJitter ->
-    Normalize -> NHWC (the whole train pipeline of rl_train.yaml), one launch."""
-    k = len(jobs)
-    call("tacorl_pack_images_u8_resize_aug_gather_batch", k, (C.c_void_p * k)(*[j[0] for j in jobs]),
-         (C.c_long * k)(*[j[1] for j in jobs]), (C.c_void_p * k)(*[j[4] for j in jobs]), int_array([j[5] for j in jobs]),
-         (C.c_void_p * k)(*[j[2] for j in jobs]), ptr_array([j[6] for j in jobs]), ptr_array([j[7] for j in jobs]),
-         int_array([j[3] for j in jobs]), dst_dtype_flag, int(src_hw[0]), int(src_hw[1]), H, W, int(pad), stream())
+    """uint8 HWC source frames of size src_hw, read in place or by index -> Resize(H, W) -> RandomShiftsAug(pad) -> /255 ->
+    ColorJitter -> Normalize -> NHWC (the whole train pipeline of rl_train.yaml), one launch."""
+    call("tacorl_pack_images_u8_resize_aug_gather_batch", len(jobs),
+         *job_arrays(jobs, "src", "pitch", "index", "stride", "dst", "shift", "jitter", "n"), dst_dtype_flag, int(src_hw[0]),
+         int(src_hw[1]), H, W, int(pad), stream())
 
 
-def pack_images_u8_gather_batch(jobs, dst_dtype_flag, H, W, pad=None):
-    """jobs: [(dataset_ptr, frame_bytes, dst_ptr, n_images, index_ptr (device int64) or None, index_stride[, shift, jitter])]:
-    image i = dataset frame index[i * stride], normalised (pad given: augmented, with the per-image tables) on the way
-    into the NHWC image buffers - the replay gather and the pack in one pass."""
-    k = len(jobs)
-    base = [k, (C.c_void_p * k)(*[j[0] for j in jobs]), (C.c_long * k)(*[j[1] for j in jobs]),
-            (C.c_void_p * k)(*[j[4] for j in jobs]), int_array([j[5] for j in jobs]), (C.c_void_p * k)(*[j[2] for j in jobs])]
-    if pad is None:
-        call("tacorl_pack_images_u8_gather_batch", *base, int_array([j[3] for j in jobs]), dst_dtype_flag, H, W, stream())
-    else:
-        call("tacorl_pack_images_u8_aug_gather_batch", *base, ptr_array([j[6] for j in jobs]), ptr_array([j[7] for j in jobs]),
-             int_array([j[3] for j in jobs]), dst_dtype_flag, H, W, int(pad), stream())
+def pack_images_u8_gather_batch(jobs, dst_dtype_flag, H, W):
+    """image i = dataset frame index[i * stride], normalised on the way into the NHWC image buffers - the replay gather and
+    the pack in one pass."""
+    call("tacorl_pack_images_u8_gather_batch", len(jobs), *job_arrays(jobs, "src", "pitch", "index", "stride", "dst", "n"),
+         dst_dtype_flag, H, W, stream())
 
 
 def gather_frames_u8(frames, index, out):
