@@ -478,10 +478,14 @@ __global__ __launch_bounds__(256) void softargmax_fwd_kernel(SaArgs a, int OH, i
   shm[w][c] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(shm[0][c], shm[1][c]), fmaxf(shm[2][c], shm[3][c]));
+  // positions are summed relative to the centre of the map (exact in fp32: half-integers): the rounding of the ~P / 4
+  // sequential additions per wave scales with the magnitude of the running sums, i.e. with the distance from the origin of
+  // the coordinates - at 15 x 21 pixels sums from the corner were 2.1e-5 px off fp64 (tests/test_encoder_fp64_gpu.py)
+  const float x0 = 0.5f * (float)(OW - 1), y0 = 0.5f * (float)(OH - 1);
   float se = 0.f, sx = 0.f, sy = 0.f;
   for (int i = w; i < P; i += 4) {
     const float e = expf(q[i * 64] / t - mx);
-    se += e; sx += e * (float)(i % OW); sy += e * (float)(i / OW);
+    se += e; sx += e * ((float)(i % OW) - x0); sy += e * ((float)(i / OW) - y0);
   }
   shs[w][c] = se; shx[w][c] = sx; shy[w][c] = sy;
   __syncthreads();
@@ -489,7 +493,7 @@ __global__ __launch_bounds__(256) void softargmax_fwd_kernel(SaArgs a, int OH, i
     se = ((shs[0][c] + shs[1][c]) + shs[2][c]) + shs[3][c];
     sx = ((shx[0][c] + shx[1][c]) + shx[2][c]) + shx[3][c];
     sy = ((shy[0][c] + shy[1][c]) + shy[2][c]) + shy[3][c];
-    f32x2 r = {sx / se, sy / se};
+    f32x2 r = {x0 + sx / se, y0 + sy / se};
     *reinterpret_cast<f32x2*>(a.out[p] + (long)img * 128 + 2 * c) = r;
   }
 }
@@ -967,6 +971,10 @@ extern "C" int tacorl_encoder_bwd_fused_conv_parts(int nprob, const void* const*
   if (!enc_bwd_plan(nprob, n_img, H, W, pl)) FAIL(TACORL_EINVAL, "encoder_bwd_fused_conv: geometry %dx%d / nprob %d", H, W, nprob);
   if (ws_bytes < pl.total) FAIL(TACORL_ENOMEM, "encoder_bwd_fused_conv: workspace too small");
   if (pl.d.c3.OH * pl.d.c3.OW > 4 * SAB_MAXI_HUGE) FAIL(TACORL_EINVAL, "encoder_bwd_fused: conv3 output too large");
+  // (a partial call must not re-pack the W^T fragments behind a dgrad that is reading them: prepacked or EBW_ALL.  Refused
+  // here, before the soft-argmax backward of a call like parts = 1 | 2 has been launched)
+  if ((parts & EBW_ALL) && (parts & EBW_ALL) != EBW_ALL && !prepacked)
+    FAIL(TACORL_EINVAL, "encoder_bwd_fused_conv_parts: partial calls need prepacked fragments");
   EbwProblem pr[EBW_MAXP];
   enc_bwd_conv_problems(nprob, img, params, act, grads, n_img, pl, ws, pr);
   SabArgs sb{};
@@ -995,8 +1003,6 @@ extern "C" int tacorl_encoder_bwd_fused_conv_parts(int nprob, const void* const*
     hipLaunchKernelGGL(sum_to_scalar_batch_kernel, dim3(nprob), dim3(256), 0, st, sb, accumulate);
   }
   if (!(parts & EBW_ALL)) return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
-  // (a partial call must not re-pack the W^T fragments behind a dgrad that is reading them: prepacked or EBW_ALL)
-  if ((parts & EBW_ALL) != EBW_ALL && !prepacked) FAIL(TACORL_EINVAL, "encoder_bwd_fused_conv_parts: partial calls need prepacked fragments");
   const int rc = ebw_conv_backward(nprob, pr, H, W, accumulate, (unsigned char*)ws + pl.conv_off, pl.total - pl.conv_off, st, prepacked ? 2 : 0,
                                    (parts & EBW_ALL) | (fused3 ? EBW_FUSED3 : 0));
   if (rc != TACORL_OK) FAIL(rc, "encoder_bwd_fused_conv: conv backward launch failed (%d)", rc);
