@@ -459,6 +459,20 @@ int tacorl_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, int r
 int tacorl_copy_cols_batch(int n, const float* const* src, const int* ld_src, float* const* dst,
                            const int* ld_dst, const int* rows, const int* cols,
                            const int* src_row_mod, const int* accumulate, tacorl_stream_t stream);
+/* Vector observations (reference modules/cql/cql_offline_lightning_d4rl.py, modules/tacorl/tacorl_d4rl.py:68-89): the input
+ * rows of the step's policy and Q chains in ONE launch, straight from the batch.  obs (B,T,S), goal (B,G), acts_main
+ * ((3n+1) B, A) = [data action | uniform | n x pi(obs) | n x pi(next)], act_pi / act_next (B,A).  out[0..4] (any may be NULL):
+ *   0: [B][lds] = [obs[b][0] | goal[b]]        1: [B][lds] = [obs[b][T-1] | goal[b]]
+ *   2: [(3n+1) B][ldq] = [obs[r % B][0] | goal[r % B] | acts_main[r]]   (sample-major rows k B + b)
+ *   3: [B][ldq] = [obs[b][0] | goal[b] | act_pi[b]]        4: [B][ldq] = [obs[b][T-1] | goal[b] | act_next[b]]
+ * columns up to the leading dimension are written as zero.  out_bf16 (NULL, or five pointers of which any may be NULL):
+ * bf16 mirrors of the same blocks at the same leading dimensions (round to nearest even).  lds >= S + G, ldq >= S + G + A,
+ * both multiples of 4; fp32 outputs 16-byte, mirrors 8-byte aligned; a Q block needs its action pointer.  Grid-stride over
+ * at most tacorl_vec_rows_max_blocks() workgroups of 256 threads (one thread per row and four columns). */
+int tacorl_vec_rows_max_blocks(void);
+int tacorl_vec_rows(const float* obs, const float* goal, const float* acts_main, const float* act_pi,
+                    const float* act_next, float* const* out, void* const* out_bf16, int B, int T, int S, int G, int A,
+                    int n, int lds, int ldq, tacorl_stream_t stream);
 /* out[b][c] = sum_{j<reps} in[j*B+b][c] : gradient of that broadcast. */
 int tacorl_reduce_rows_mod(const float* in, int ld_in, float* out, int ld_out, int B, int cols,
                            int reps, tacorl_stream_t stream);
@@ -587,6 +601,19 @@ int tacorl_logistic_mixture_finish(const void* ws, size_t ws_bytes, int B, int T
  * caller's U(0,1) draws in the heads' row order; out [R][Da+1] = [actions | gripper -1/+1]. */
 int tacorl_logistic_mixture_sample(const float* heads, int ldh, const float* rand_a, const float* rand_b,
                                    float* out, int R, int Da, int K, tacorl_stream_t stream);
+
+/* The same three without the gripper head (discrete_gripper: False, :52,134-138,265-266 - the D4RL decoder): every action
+ * dimension is a mixture dimension.  heads[(t*B+b)] = [means Da*K | log_scales Da*K | logit_probs Da*K], ldh >= 3*Da*K;
+ * actions batch-major [B][T][Da]; no cross-entropy term; loss_out: two device floats {loss, 0}; the sample writes
+ * out [R][Da].  ws: tacorl_logistic_mixture_ws_bytes(B, Tm, Da).  Always the 16-lane kernel (TACORL_LM_SCALAR is not read),
+ * so a lazy loss (loss_out NULL) is finished by tacorl_logistic_mixture_nogrip_finish, not by the gripper variant's. */
+int tacorl_logistic_mixture_nogrip_loss(const float* heads, int ldh, const float* actions, float* d_heads,
+                                        float* loss_out, int B, int T, int Tm, int Da, int K, int num_classes,
+                                        float grad_scale, void* ws, size_t ws_bytes, tacorl_stream_t stream);
+int tacorl_logistic_mixture_nogrip_finish(const void* ws, size_t ws_bytes, int B, int Tm, int Da, float* loss_out,
+                                          tacorl_stream_t stream);
+int tacorl_logistic_mixture_nogrip_sample(const float* heads, int ldh, const float* rand_a, const float* rand_b,
+                                          float* out, int R, int Da, int K, tacorl_stream_t stream);
 
 /* ---- backward glue: ReLU-RNN BPTT, transformer, seq-VAE KL ---------------------------------- */
 int tacorl_relu_mask_mul(const float* dy, const float* add, const float* h, float* out, long n,

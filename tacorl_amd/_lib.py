@@ -87,6 +87,9 @@ _SIGS = {
     "tacorl_logistic_mixture_loss": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _sz, _p]),
     "tacorl_logistic_mixture_finish": (_i, [_p, _sz, _i, _i, _i, _p, _p]),
     "tacorl_logistic_mixture_sample": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _p]),
+    "tacorl_logistic_mixture_nogrip_loss": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _sz, _p]),
+    "tacorl_logistic_mixture_nogrip_finish": (_i, [_p, _sz, _i, _i, _i, _p, _p]),
+    "tacorl_logistic_mixture_nogrip_sample": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _p]),
     "tacorl_linear_dgrad": (_i, [_i, _p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
     "tacorl_linear_dgrad_ws_bytes": (_sz, [_i, _p, _i, _i]),
     "tacorl_linear_dgrad_splitk": (_i, [_i, _p, _i, _p, _p, _i, _p, _i, _i, _p, _i, _p, _i, _i, _i, _p, _sz, _p]),
@@ -138,6 +141,8 @@ _SIGS = {
     "tacorl_sample_transitions": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p]),
     "tacorl_copy_cols": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "tacorl_copy_cols_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "tacorl_vec_rows_max_blocks": (_i, []),
+    "tacorl_vec_rows": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "tacorl_reduce_rows_mod": (_i, [_p, _i, _p, _i, _i, _i, _i, _p]),
     "tacorl_reduce_rows_mod_batch": (_i, [_i, _p, _i, _p, _i, _i, _i, _i, _p]),
     "tacorl_uniform_actions": (_i, [_p, _p, _i, _i, _i, _i, _p]),

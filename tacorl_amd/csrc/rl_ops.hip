@@ -307,6 +307,79 @@ extern "C" int tacorl_copy_cols_batch(int n, const float* const* src, const int*
   return LAUNCH_OK();
 }
 
+// ===================================================================== vec_rows
+// Vector observations (D4RL AntMaze: state 29, goal 2): every input row of the step's policy and Q chains in one launch,
+// straight from the batch - there is no encoder stage between the batch and the MLPs.  Five row blocks, any of which
+// may be absent (NULL):
+//   s_obs  [B][lds]   = [obs[b][0]   | goal[b] | 0..]
+//   s_next [B][lds]   = [obs[b][T-1] | goal[b] | 0..]
+//   xq     [R][ldq]   = [obs[r % B][0]   | goal[r % B] | acts_main[r] | 0..],  R = (3 n + 1) B rows, sample-major (k B + b)
+//   xqpi   [B][ldq]   = [obs[b][0]   | goal[b] | act_pi[b]   | 0..]
+//   xt     [B][ldq]   = [obs[b][T-1] | goal[b] | act_next[b] | 0..]
+// each with an optional bf16 mirror of the same leading dimension (round to nearest even).  One thread per (row, four
+// columns): four scalar reads (a 29-float state row is not 16-byte aligned), one 16-byte store (8 for the mirror);
+// pad columns are written as zero.  Grid-stride: VEC_ROWS_MAXB workgroups cover any row count.
+#define VEC_ROWS_MAXB 1024
+struct VecRowsArgs {
+  const float* obs; const float* goal; const float* acts[3];  // acts: acts_main, act_pi, act_next
+  float* out[5]; __bf16* out_bf16[5];
+  long first[6];  // virtual row range of each block: [first[i], first[i + 1])
+  int B, T, S, G, A, lds, ldq, W4;
+};
+__global__ __launch_bounds__(256) void vec_rows_kernel(VecRowsArgs a) {
+  const long total = a.first[5] * a.W4;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long v = i / a.W4;
+    const int c0 = (int)(i - v * a.W4) * 4;
+    int blk = 0;
+#pragma unroll
+    for (int j = 1; j < 5; j++) blk += v >= a.first[j];
+    const int ld = blk < 2 ? a.lds : a.ldq;
+    if (c0 >= ld) continue;
+    const long r = v - a.first[blk];
+    const int b = (int)(r % a.B);
+    const float* st = a.obs + ((long)b * a.T + ((blk == 1 || blk == 4) ? a.T - 1 : 0)) * a.S;
+    const float* ac = blk < 2 ? nullptr : a.acts[blk - 2] + r * a.A;
+    const int SG = a.S + a.G, SGA = blk < 2 ? SG : SG + a.A;
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int c = c0 + j;
+      o[j] = c < a.S ? st[c] : (c < SG ? a.goal[(long)b * a.G + (c - a.S)] : (c < SGA ? ac[c - SG] : 0.f));
+    }
+    if (a.out[blk]) *reinterpret_cast<f32x4*>(a.out[blk] + r * ld + c0) = o;
+    if (a.out_bf16[blk])
+      *reinterpret_cast<bf16x4*>(a.out_bf16[blk] + r * ld + c0) = bf16x4{(__bf16)o[0], (__bf16)o[1], (__bf16)o[2], (__bf16)o[3]};
+  }
+}
+extern "C" int tacorl_vec_rows_max_blocks(void) { return VEC_ROWS_MAXB; }
+extern "C" int tacorl_vec_rows(const float* obs, const float* goal, const float* acts_main, const float* act_pi,
+                               const float* act_next, float* const* out, void* const* out_bf16, int B, int T, int S, int G,
+                               int A, int n, int lds, int ldq, tacorl_stream_t stream) {
+  if (B < 1 || T < 1 || S < 1 || G < 0 || A < 0 || n < 0 || !obs || (G > 0 && !goal) || !out) return TACORL_EINVAL;
+  if (lds < S + G || ldq < S + G + A || lds % 4 || ldq % 4) return TACORL_EINVAL;
+  VecRowsArgs a{};
+  a.obs = obs; a.goal = goal; a.acts[0] = acts_main; a.acts[1] = act_pi; a.acts[2] = act_next;
+  a.B = B; a.T = T; a.S = S; a.G = G; a.A = A; a.lds = lds; a.ldq = ldq; a.W4 = (lds > ldq ? lds : ldq) / 4;
+  const long R = (3L * n + 1) * B;
+  long rows = 0;
+  for (int i = 0; i < 5; i++) {
+    a.out[i] = out[i];
+    a.out_bf16[i] = out_bf16 ? (__bf16*)out_bf16[i] : nullptr;
+    if (((uintptr_t)a.out[i] & 15) || ((uintptr_t)a.out_bf16[i] & 7)) return TACORL_EINVAL;
+    a.first[i] = rows;
+    if (a.out[i] || a.out_bf16[i]) {
+      if (i >= 2 && A > 0 && !a.acts[i - 2]) return TACORL_EINVAL;  // a Q block needs its actions
+      rows += i == 2 ? R : B;
+    }
+  }
+  a.first[5] = rows;
+  if (rows == 0) return TACORL_OK;
+  const long total = rows * a.W4, nb = (total + 255) / 256;
+  hipLaunchKernelGGL(vec_rows_kernel, dim3((int)(nb > VEC_ROWS_MAXB ? VEC_ROWS_MAXB : nb)), dim3(256), 0, (hipStream_t)stream, a);
+  return LAUNCH_OK();
+}
+
 // out[b][c] = sum_j in[(j*B + b)][c], j < reps   (gradient of a broadcast over samples).
 // A workgroup owns 64 consecutive output elements; its four waves split the repetitions (wave w: j = w, w + 4, ...,
 // eight loads in flight each) and meet in LDS, summed in wave order: fixed order, run-to-run identical.  (One thread

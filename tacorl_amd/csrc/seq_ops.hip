@@ -438,6 +438,9 @@ __device__ __forceinline__ float grp16_sum(float v) {
   for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
   return v;
 }
+// GRIP = false (tacorl_logistic_mixture_nogrip_*, discrete_gripper: False of action_decoder_logistic.py:52,134-138): every action
+// dimension is a mixture dimension - heads rows are 3 Da K wide, actions [B][T][Da], no cross-entropy term.
+template <bool GRIP>
 __global__ __launch_bounds__(256) void logistic_mixture_k16_kernel(const float* __restrict__ heads, int ldh,
                                                                    const float* __restrict__ actions, float* __restrict__ d_heads,
                                                                    float* __restrict__ partial, int B, int T, int Tm, int Da,
@@ -449,12 +452,13 @@ __global__ __launch_bounds__(256) void logistic_mixture_k16_kernel(const float* 
   float loss = 0.f, hits = 0.f;
   const float gR = grad_scale / (float)R;
   const bool on = k < K;
+  const int AS = GRIP ? Da + 1 : Da;  // floats of one action row
   for (long i = (long)blockIdx.x * 16 + (threadIdx.x >> 4); i < total; i += (long)gridDim.x * 16) {
     const int a = (int)(i % Da);
     const long r = i / Da;
     const int b = (int)(r % B), t = (int)(r / B);
     const float* h = heads + r * ldh;
-    const float x = actions[((long)b * T + t) * (Da + 1) + a];
+    const float x = actions[((long)b * T + t) * AS + a];
     const float pl = on ? h[2 * Da * K + a * K + k] : -INFINITY;
     const float mxl = grp16_max(pl);
     const float lse_l = mxl + logf(grp16_sum(on ? expf(pl - mxl) : 0.f));
@@ -494,7 +498,7 @@ __global__ __launch_bounds__(256) void logistic_mixture_k16_kernel(const float* 
       d[Da * K + a * K + k] = -gR * w * ds;
       d[2 * Da * K + a * K + k] = -gR * (w - p);
     }
-    if (a == 0 && k == 0) {  // gripper cross-entropy for this row (nn.CrossEntropyLoss, mean over rows)
+    if (GRIP && a == 0 && k == 0) {  // gripper cross-entropy for this row (nn.CrossEntropyLoss, mean over rows)
       const float g0 = h[3 * Da * K], g1 = h[3 * Da * K + 1], mg = fmaxf(g0, g1);
       const float lz = mg + logf(expf(g0 - mg) + expf(g1 - mg));
       const int y = actions[((long)b * T + t) * (Da + 1) + Da] == -1.0f ? 0 : (int)actions[((long)b * T + t) * (Da + 1) + Da];
@@ -552,7 +556,7 @@ extern "C" int tacorl_logistic_mixture_loss(const float* heads, int ldh, const f
                        d_heads, (float*)ws, B, T, Tm, Da, K, 1.0f / (float)(num_classes - 1),
                        logf((float)(num_classes - 1) / 2.f), gripper_alpha, grad_scale);
   else
-    hipLaunchKernelGGL(logistic_mixture_k16_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, heads, ldh, actions,
+    hipLaunchKernelGGL(logistic_mixture_k16_kernel<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, heads, ldh, actions,
                        d_heads, (float*)ws, B, T, Tm, Da, K, 1.0f / (float)(num_classes - 1),
                        logf((float)(num_classes - 1) / 2.f), gripper_alpha, grad_scale);
   // loss_out == NULL: the per-block partials stay in ws and tacorl_logistic_mixture_finish sums them when the scalar is read
@@ -577,10 +581,41 @@ extern "C" int tacorl_logistic_mixture_finish(const void* ws, size_t ws_bytes, i
   return LAUNCH_OK();
 }
 
+// The mixture term alone (discrete_gripper: False): always the 16-lane kernel, so the block count - and with it the layout of
+// the partial sums in ws - does not depend on TACORL_LM_SCALAR.
+static long lm_nogrip_blocks(int B, int Tm, int Da) {
+  const long blocks = ((long)B * Tm * Da + 15) / 16;
+  return blocks > 1024 ? 1024 : blocks;
+}
+extern "C" int tacorl_logistic_mixture_nogrip_loss(const float* heads, int ldh, const float* actions, float* d_heads,
+                                                   float* loss_out, int B, int T, int Tm, int Da, int K, int num_classes,
+                                                   float grad_scale, void* ws, size_t ws_bytes, tacorl_stream_t stream) {
+  if (K < 1 || K > LM_MAXK || Da < 1 || B < 1 || Tm < 1 || Tm > T || num_classes < 2 || ldh < 3 * Da * K) return TACORL_EINVAL;
+  if (!heads || !actions || !ws) return TACORL_EINVAL;
+  if (ws_bytes < tacorl_logistic_mixture_ws_bytes(B, Tm, Da)) return TACORL_ENOMEM;
+  const long blocks = lm_nogrip_blocks(B, Tm, Da);
+  hipLaunchKernelGGL(logistic_mixture_k16_kernel<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, heads, ldh, actions,
+                     d_heads, (float*)ws, B, T, Tm, Da, K, 1.0f / (float)(num_classes - 1), logf((float)(num_classes - 1) / 2.f),
+                     0.f, grad_scale);
+  if (loss_out)  // (loss_out == NULL: the partials stay in ws for tacorl_logistic_mixture_nogrip_finish)
+    hipLaunchKernelGGL(scaled_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws, (int)blocks,
+                       1.0f / (float)(B * Tm), loss_out);
+  return LAUNCH_OK();
+}
+extern "C" int tacorl_logistic_mixture_nogrip_finish(const void* ws, size_t ws_bytes, int B, int Tm, int Da, float* loss_out,
+                                                     tacorl_stream_t stream) {
+  if (!loss_out || !ws || B < 1 || Tm < 1 || Da < 1) return TACORL_EINVAL;
+  if (ws_bytes < tacorl_logistic_mixture_ws_bytes(B, Tm, Da)) return TACORL_ENOMEM;
+  hipLaunchKernelGGL(scaled_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)ws,
+                     (int)lm_nogrip_blocks(B, Tm, Da), 1.0f / (float)(B * Tm), loss_out);
+  return LAUNCH_OK();
+}
+
 // ActionDecoderLogistic._sample (reference action_decoder_logistic.py:238-266): Gumbel-max choice of the mixture
 // component, inversion sampling of that logistic, argmax gripper class.  One thread per (row, action dim).
 // heads as in logistic_mixture_kernel; rand_a [R][Da][K], rand_b [R][Da] U(0,1) draws in the heads' row order;
-// out [R][Da+1] = [actions | gripper command -1/+1].
+// out [R][Da+1] = [actions | gripper command -1/+1]; GRIP = false: out [R][Da], the actions alone (:265-266).
+template <bool GRIP>
 __global__ void logistic_mixture_sample_kernel(const float* __restrict__ heads, int ldh, const float* __restrict__ rand_a,
                                                const float* __restrict__ rand_b, float* __restrict__ out, int R, int Da, int K) {
   const long total = (long)R * Da;
@@ -601,8 +636,8 @@ __global__ void logistic_mixture_sample_kernel(const float* __restrict__ heads, 
     }
     const float ls = fmaxf(lsc[arg], -5.0f);  // LOG_SIG_MIN (:18,292)
     const float u = (r1 - r2) * rand_b[i] + r2;
-    out[r * (Da + 1) + a] = mean[arg] + expf(ls) * (logf(u) - logf(1.0f - u));
-    if (a == 0) out[r * (Da + 1) + Da] = h[3 * Da * K + 1] > h[3 * Da * K] ? 1.0f : -1.0f;
+    out[r * (GRIP ? Da + 1 : Da) + a] = mean[arg] + expf(ls) * (logf(u) - logf(1.0f - u));
+    if (GRIP && a == 0) out[r * (Da + 1) + Da] = h[3 * Da * K + 1] > h[3 * Da * K] ? 1.0f : -1.0f;
   }
 }
 extern "C" int tacorl_logistic_mixture_sample(const float* heads, int ldh, const float* rand_a, const float* rand_b,
@@ -612,8 +647,21 @@ extern "C" int tacorl_logistic_mixture_sample(const float* heads, int ldh, const
   if (total <= 0) return TACORL_OK;
   long blocks = (total + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(logistic_mixture_sample_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, heads, ldh, rand_a,
+  hipLaunchKernelGGL(logistic_mixture_sample_kernel<true>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, heads, ldh, rand_a,
                      rand_b, out, R, Da, K);
+  return LAUNCH_OK();
+}
+
+extern "C" int tacorl_logistic_mixture_nogrip_sample(const float* heads, int ldh, const float* rand_a, const float* rand_b,
+                                                     float* out, int R, int Da, int K, tacorl_stream_t stream) {
+  if (K < 1 || K > LM_MAXK || R < 0 || Da < 1 || ldh < 3 * Da * K) return TACORL_EINVAL;
+  const long total = (long)R * Da;
+  if (total <= 0) return TACORL_OK;
+  if (!heads || !rand_a || !rand_b || !out) return TACORL_EINVAL;
+  long blocks = (total + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(logistic_mixture_sample_kernel<false>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, heads, ldh,
+                     rand_a, rand_b, out, R, Da, K);
   return LAUNCH_OK();
 }
 

@@ -45,13 +45,16 @@ class NetBlock:
         self.head_off = off
         off += blocks.mlp_size(self.head_dims)
         self.size = off
+        self._head_names, self._head_parts = head_names, head_parts
+        self._alloc_block(device)
+
+    def _alloc_block(self, device):
         z = lambda: torch.zeros(self.size, device=device)  # noqa: E731
         self.param, self.grad, self.m, self.v = z(), z(), z(), z()
         # bf16 copy of the MLP part of the block (the fused MLP forward's MFMA operand); refreshed from
         # the fp32 master at the start of every update (ACEngine._refresh_bf16)
         self.param_bf16 = torch.zeros(self.size, device=device, dtype=torch.bfloat16)
         self.step = torch.zeros(1, dtype=torch.int32, device=device)
-        self._head_names, self._head_parts = head_names, head_parts
         self.views, self.grad_views = self._views_of(self.param), self._views_of(self.grad)
 
     def _views_of(self, flat):
@@ -62,11 +65,14 @@ class NetBlock:
                 dst[f"encoder.networks.{c}.{k}"] = v
         gn = [(f"goal_encoder.mlp.{i}.weight", f"goal_encoder.mlp.{i}.bias") for i in (0, 2, 4)]
         dst.update(blocks.mlp_views(flat, self.genc_off, self.genc_dims, gn))
+        dst.update(self._head_views(flat))
+        return dst
+
+    def _head_views(self, flat):
         if self._head_parts is None:
-            dst.update(blocks.mlp_views(flat, self.head_off, self.head_dims, self._head_names))
-        else:
-            dst.update(blocks.mlp_views(flat, self.head_off, self.head_dims[:-1], self._head_names))
-            dst.update(blocks.head_views(flat, self.head_off, self.head_dims, self.head_dims[-2], self._head_parts))
+            return blocks.mlp_views(flat, self.head_off, self.head_dims, self._head_names)
+        dst = blocks.mlp_views(flat, self.head_off, self.head_dims[:-1], self._head_names)
+        dst.update(blocks.head_views(flat, self.head_off, self.head_dims, self.head_dims[-2], self._head_parts))
         return dst
 
     def views_of(self, flat):
@@ -115,39 +121,47 @@ class ACEngine:
                                       "branch is not built)")
         if len(set(cams)) != len(cams) or len(set(goal_cams)) != len(goal_cams):
             raise ValueError(f"a modality is listed twice: obs {list(cams)}, goal {list(goal_cams)}")
-        self.cams, self.hw, self.B, self.n, self.A = list(cams), dict(hw or {}), B, n, action_dim
+        self.cams, self.hw = list(cams), dict(hw or {})
         # Two ordered camera lists (reference visual_actor_wrapper.py:41-62): the state embedding is the cameras of `cams`
         # in list order, the goal encoder's input the cameras of `goal_cams` in list order; every network owns an encoder
         # per camera of the union.  enc_cams: every camera the step encodes (the observation cameras first).
         self.goal_cams = list(goal_cams)
         self.enc_cams = self.cams + [c for c in self.goal_cams if c not in self.cams]
-        self.dev, self.compute, self.img_dtype = device, compute, img_dtype
+        self.img_dtype = img_dtype
+        self.Eo, self.G = 32 * len(self.cams), 32 * len(self.goal_cams)
+        self.E = self.Eo + self.G
+        self.lds = self.E
+        self._init_step(action_dim, B, device, n, dict(
+            discount=discount, tau=tau, actor_lr=actor_lr, critic_lr=critic_lr, deterministic_backup=deterministic_backup,
+            reward_scale=reward_scale, clip=clip_grad_val, cons_w=conservative_weight, gap=lagrange_thresh, temp=temp,
+            target_entropy=target_entropy), with_lagrange, discrete_gripper, policy_layers, q_layers, hidden, compute, world_size)
+
+    def _init_step(self, action_dim, B, device, n, hp, with_lagrange, discrete_gripper, policy_layers, q_layers, hidden, compute,
+                   world_size):
+        """Everything of the constructor that does not depend on where the state rows come from (self.E, self.lds are set):
+        hyper-parameters, the five networks, the two temperatures, the gradient arena, the first batch's buffers."""
+        self.B, self.n, self.A = B, n, action_dim
+        self.dev, self.compute = device, compute
         self.dg = bool(discrete_gripper)
         self.Ac = action_dim - 1 if self.dg else action_dim
         self.HD = 2 * self.Ac + (2 if self.dg else 0)
-        self.hp = dict(discount=discount, tau=tau, actor_lr=actor_lr, critic_lr=critic_lr,
-                       deterministic_backup=deterministic_backup, reward_scale=reward_scale,
-                       clip=clip_grad_val, cons_w=conservative_weight, gap=lagrange_thresh, temp=temp,
-                       target_entropy=target_entropy)
+        self.hp = hp
         self.with_lagrange = with_lagrange
         self.world = world_size
         self.hidden = hidden
-        self.Eo, self.G = 32 * len(self.cams), 32 * len(self.goal_cams)
-        self.E = self.Eo + self.G
         self.ldq = _al4(self.E + action_dim)
-        self.lds = self.E
         pol_dims = [self.E] + [hidden] * policy_layers + [self.HD]
         q_dims = [self.E + action_dim] + [hidden] * q_layers + [1]
         silu_p, silu_q = [ACT_SILU] * policy_layers + [ACT_NONE], [ACT_SILU] * q_layers + [ACT_NONE]
-        pn = [(f"actor.policy.fc_layers.{i}.weight", f"actor.policy.fc_layers.{i}.bias") for i in range(policy_layers)]
-        parts = [("actor.policy.fc_mean", self.Ac), ("actor.policy.fc_log_std", self.Ac)]
+        ap, qp = self.name_prefix
+        pn = [(f"{ap}policy.fc_layers.{i}.weight", f"{ap}policy.fc_layers.{i}.bias") for i in range(policy_layers)]
+        parts = [(f"{ap}policy.fc_mean", self.Ac), (f"{ap}policy.fc_log_std", self.Ac)]
         if self.dg:
-            parts.append(("actor.policy.gripper_action", 2))
-        qn = [(f"critic.Q.fc_layers.{i}.weight", f"critic.Q.fc_layers.{i}.bias") for i in range(q_layers)]
-        qn.append(("critic.Q.out.weight", "critic.Q.out.bias"))
-        self.actor = NetBlock(cams, goal_cams, pol_dims, silu_p, pn, device, head_parts=parts, hidden=hidden)
-        mk = lambda: NetBlock(cams, goal_cams, q_dims, silu_q, qn, device, hidden=hidden)  # noqa: E731
-        self.q1, self.q2, self.tq1, self.tq2 = mk(), mk(), mk(), mk()
+            parts.append((f"{ap}policy.gripper_action", 2))
+        qn = [(f"{qp}Q.fc_layers.{i}.weight", f"{qp}Q.fc_layers.{i}.bias") for i in range(q_layers)]
+        qn.append((f"{qp}Q.out.weight", f"{qp}Q.out.bias"))
+        self.actor = self._net_block(pol_dims, silu_p, pn, parts)
+        self.q1, self.q2, self.tq1, self.tq2 = (self._net_block(q_dims, silu_q, qn, None) for _ in range(4))
         self.log_alpha, self.log_alpha_prime = Scalar(device), Scalar(device)
         # one gradient arena [actor | q1 | q2 | log_alpha'] -> ONE all-reduce per step for the update
         # (plus the scalar one for log_alpha, which must be stepped before the actor loss)
@@ -157,6 +171,13 @@ class ACEngine:
         self.B = None
         if B:
             self.ensure_batch(B)
+
+    # reference names of the policy / Q tensors inside a network's block (the visual wrappers' sub-module names)
+    name_prefix = ("actor.", "critic.")
+
+    def _net_block(self, head_dims, head_acts, head_names, head_parts):
+        return NetBlock(self.cams, self.goal_cams, head_dims, head_acts, head_names, self.dev, head_parts=head_parts,
+                        hidden=self.hidden)
 
     def _bind_arena(self):
         """[actor | q1 | q2 | log_alpha' | extra blocks...]: every gradient the step's second collective reduces, one
@@ -193,8 +214,14 @@ class ACEngine:
             self._alloc()
 
     def _alloc(self):
-        B, n, dev = self.B, self.n, self.dev
         ops.note_alloc()
+        self._alloc_encoder_stage()
+        self._alloc_chains()
+
+    def _alloc_encoder_stage(self):
+        """The stage in front of the chains: image slots, encoder outputs / activations, the goal encoders' buffers, and the
+        rows it hands to the chains - the state rows S, the Q input rows XQ / XQpi / XT - with the gradients that come back."""
+        B, dev = self.B, self.dev
         f = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
         # Image slots of a camera, in units of B images: [obs | goal | next] for a camera in both roles, [obs | next] for an
         # observation-only camera, [goal] for a goal-only one (images that no role uses are neither packed nor encoded).
@@ -232,6 +259,19 @@ class ACEngine:
         self.gact = {k: f(ops.mlp_act_layout(B, net.genc_dims, net.genc_acts)[2]) for k, net in nets}
         self.g_yoff = ops.mlp_act_layout(B, self.actor.genc_dims, self.actor.genc_acts)[1][-1]
         self.S = {k: f(B, self.lds) for k in ("a", "a_nx", "q1", "q2", "tq1", "tq2")}
+        self.dS = {k: f(B, self.lds) for k in ("a", "q1", "q2")}
+        self.dgin = {k: f(B, self.G) for k in ("a", "q1", "q2")}
+        R = (3 * self.n + 1) * B
+        self.XQ = {k: f(R, self.ldq) for k in ("q1", "q2")}
+        self.XQpi = {k: f(B, self.ldq) for k in ("q1", "q2")}
+        self.XT = {k: f(B, self.ldq) for k in ("tq1", "tq2")}
+        self.dXQ = {k: f(R, self.ldq) for k in ("q1", "q2")}
+
+    def _alloc_chains(self):
+        """Buffers of the policy and Q chains, the sampled actions, the losses and the step's noise: what the step needs
+        whatever produced its state rows self.S / Q input rows self.XQ, self.XQpi, self.XT."""
+        B, n, dev = self.B, self.n, self.dev
+        f = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
         pd, pa = self.actor.head_dims, self.actor.head_acts
         self.pact = {k: f(ops.mlp_act_layout(B, pd, pa)[2]) for k in ("a", "a_nx")}
         self.p_yoff = ops.mlp_act_layout(B, pd, pa)[1][-1]
@@ -242,9 +282,6 @@ class ACEngine:
         self.logp_cur, self.logp_nxt = f(n * B), f(n * B)
         self.grip_pi = torch.zeros(B, dtype=torch.int32, device=dev)
         qd, qa = self.q1.head_dims, self.q1.head_acts
-        self.XQ = {k: f(R, self.ldq) for k in ("q1", "q2")}
-        self.XQpi = {k: f(B, self.ldq) for k in ("q1", "q2")}
-        self.XT = {k: f(B, self.ldq) for k in ("tq1", "tq2")}
         self.qact = {k: f(ops.mlp_act_layout(R, qd, qa)[2]) for k in ("q1", "q2")}
         self.qact_pi = {k: f(ops.mlp_act_layout(B, qd, qa)[2]) for k in ("q1", "q2")}
         self.qact_t = {k: f(ops.mlp_act_layout(B, qd, qa)[2]) for k in ("tq1", "tq2")}
@@ -252,11 +289,8 @@ class ACEngine:
         self.q_yoff_B = ops.mlp_act_layout(B, qd, qa)[1][-1]
         self.dq = {k: f(R) for k in ("q1", "q2")}
         self.dq_pi = {k: f(B) for k in ("q1", "q2")}
-        self.dXQ = {k: f(R, self.ldq) for k in ("q1", "q2")}
         self.dXQpi = {k: f(B, self.ldq) for k in ("q1", "q2")}
         self.d_head = f(B, self.HD)
-        self.dS = {k: f(B, self.lds) for k in ("a", "q1", "q2")}
-        self.dgin = {k: f(B, self.G) for k in ("a", "q1", "q2")}
         self.reward, self.done = f(B), f(B)
         # the data action IS rows [0, B) of the Q networks' action column block (no copy in front of the Q forward):
         # load_transition / TACORL's plan-recognition sample write it in place
@@ -598,34 +632,7 @@ class ACEngine:
             torch.cuda.current_stream().wait_event(self.action_ready)
             self.action_ready = None
         ops.mark("b:start")
-        qd, qa = self.q1.head_dims, self.q1.head_acts
-        ps = [self.q1.head(), self.q2.head(), self.q1.head(), self.q2.head(), self.tq1.head(), self.tq2.head()]
-        ac = [self.qact["q1"], self.qact["q2"], self.qact_pi["q1"], self.qact_pi["q2"], self.qact_t["tq1"],
-              self.qact_t["tq2"]]
-        pb = [self.q1.head_bf16(), self.q2.head_bf16(), self.q1.head_bf16(), self.q2.head_bf16(), self.tq1.head_bf16(),
-              self.tq2.head_bf16()]
-        if self._gather_ok("q"):
-            # Q inputs [enc(obs) | goal_enc | action] read in place: the state rows repeat every B rows (expand_obs on
-            # embeddings), the actions are acts_main = [data | uniform | n x pi(obs) | n x pi(next)]; only the two
-            # problems with weight gradients (q1 / q2 over all R rows) also write their assembled rows
-            E = self.E
-            seg = lambda k, mod, a_t: self._emb_segs(*self._OBS_SRC[k], mod) + [(a_t, 0, A, E, 0)]  # noqa: E731
-            segs = [seg("q1", B, self.acts_main), seg("q2", B, self.acts_main), seg("q1", 0, self.act_pi), seg("q2", 0, self.act_pi),
-                    seg("tq1", 0, self.act_next), seg("tq2", 0, self.act_next)]
-            ops.mlp_fwd_gather(segs, [self.XQ["q1"], self.XQ["q2"], None, None, None, None], self.ldq, ps, pb, ac,
-                               [self.R, self.R, B, B, B, B], qd, qa, lean=self._lean("q"))
-        else:
-            with ops.copy_batch():  # one launch
-                for k in ("q1", "q2"):
-                    ops.copy_cols(self.S[k], 0, self.lds, self.XQ[k], 0, self.ldq, self.R, self.E, src_row_mod=B)
-                    ops.copy_cols(self.acts_main, 0, A, self.XQ[k], self.E, self.ldq, self.R, A)
-                    ops.copy_cols(self.S[k], 0, self.lds, self.XQpi[k], 0, self.ldq, B, self.E)
-                    ops.copy_cols(self.act_pi, 0, A, self.XQpi[k], self.E, self.ldq, B, A)
-                for k in ("tq1", "tq2"):
-                    ops.copy_cols(self.S[k], 0, self.lds, self.XT[k], 0, self.ldq, B, self.E)
-                    ops.copy_cols(self.act_next, 0, A, self.XT[k], self.E, self.ldq, B, A)
-            xs = [self.XQ["q1"], self.XQ["q2"], self.XQpi["q1"], self.XQpi["q2"], self.XT["tq1"], self.XT["tq2"]]
-            ops.mlp_fwd(xs, self.ldq, ps, ac, [self.R, self.R, B, B, B, B], qd, qa, self.compute, params_bf16=pb, lean=self._lean("q"))
+        self._q_forward()
         qout = lambda buf, off, rows: buf[off: off + rows]  # noqa: E731
         q1m, q2m = qout(self.qact["q1"], self.q_yoff_R, self.R), qout(self.qact["q2"], self.q_yoff_R, self.R)
         q1p, q2p = qout(self.qact_pi["q1"], self.q_yoff_B, B), qout(self.qact_pi["q2"], self.q_yoff_B, B)
@@ -652,18 +659,64 @@ class ACEngine:
             with torch.cuda.stream(self._bwd_stream):
                 self._actor_backward(bc_phase, head_cur, q1p, q2p, gs)
                 ops.mark("b:actor_bwd")
-            # ---- critic backward through the Q MLPs; sum the broadcast embedding gradient over samples
-            self._mlp_backward("q", [self.XQ["q1"], self.XQ["q2"]], self.ldq, [self.q1.head(), self.q2.head()],
-                               [self.qact["q1"], self.qact["q2"]], [self.dq["q1"], self.dq["q2"]], 1,
-                               [self.q1.head(self.q1.grad), self.q2.head(self.q2.grad)], [self.dXQ["q1"], self.dXQ["q2"]],
-                               self.ldq, [self.R, self.R], qd, qa)
-            call("tacorl_reduce_rows_mod_batch", 2, ops.ptr_array([self.dXQ["q1"], self.dXQ["q2"]]), self.ldq,
-                 ops.ptr_array([self.dS["q1"], self.dS["q2"]]), self.lds, B, self.E, 3 * n + 1, ops.stream())
+            self._critic_backward()
             ops.mark("b:critic_bwd")
             main_stream.wait_stream(self._bwd_stream)
             self._encoders_backward()
             ops.mark("b:enc_bwd")
         ops.mark("b:end")
+
+    def _q_forward(self):
+        """The six Q forwards of the step (q1 / q2 over all R rows and over pi(obs), the targets over pi(next)), with the
+        assembly of their input rows [S | action]."""
+        B, A = self.B, self.A
+        qd, qa = self.q1.head_dims, self.q1.head_acts
+        ps = [self.q1.head(), self.q2.head(), self.q1.head(), self.q2.head(), self.tq1.head(), self.tq2.head()]
+        ac = [self.qact["q1"], self.qact["q2"], self.qact_pi["q1"], self.qact_pi["q2"], self.qact_t["tq1"],
+              self.qact_t["tq2"]]
+        pb = [self.q1.head_bf16(), self.q2.head_bf16(), self.q1.head_bf16(), self.q2.head_bf16(), self.tq1.head_bf16(),
+              self.tq2.head_bf16()]
+        if self._gather_ok("q"):
+            # Q inputs [enc(obs) | goal_enc | action] read in place: the state rows repeat every B rows (expand_obs on
+            # embeddings), the actions are acts_main = [data | uniform | n x pi(obs) | n x pi(next)]; only the two
+            # problems with weight gradients (q1 / q2 over all R rows) also write their assembled rows
+            E = self.E
+            seg = lambda k, mod, a_t: self._emb_segs(*self._OBS_SRC[k], mod) + [(a_t, 0, A, E, 0)]  # noqa: E731
+            segs = [seg("q1", B, self.acts_main), seg("q2", B, self.acts_main), seg("q1", 0, self.act_pi), seg("q2", 0, self.act_pi),
+                    seg("tq1", 0, self.act_next), seg("tq2", 0, self.act_next)]
+            ops.mlp_fwd_gather(segs, [self.XQ["q1"], self.XQ["q2"], None, None, None, None], self.ldq, ps, pb, ac,
+                               [self.R, self.R, B, B, B, B], qd, qa, lean=self._lean("q"))
+        else:
+            self._assemble_q_rows()
+            xs = [self.XQ["q1"], self.XQ["q2"], self.XQpi["q1"], self.XQpi["q2"], self.XT["tq1"], self.XT["tq2"]]
+            ops.mlp_fwd(xs, self.ldq, ps, ac, [self.R, self.R, B, B, B, B], qd, qa, self.compute, params_bf16=pb, lean=self._lean("q"))
+
+    def _assemble_q_rows(self):
+        """XQ / XQpi / XT = [S | action] for the forwards that do not gather (one launch)."""
+        B, A = self.B, self.A
+        with ops.copy_batch():
+            for k in ("q1", "q2"):
+                ops.copy_cols(self.S[k], 0, self.lds, self.XQ[k], 0, self.ldq, self.R, self.E, src_row_mod=B)
+                ops.copy_cols(self.acts_main, 0, A, self.XQ[k], self.E, self.ldq, self.R, A)
+                ops.copy_cols(self.S[k], 0, self.lds, self.XQpi[k], 0, self.ldq, B, self.E)
+                ops.copy_cols(self.act_pi, 0, A, self.XQpi[k], self.E, self.ldq, B, A)
+            for k in ("tq1", "tq2"):
+                ops.copy_cols(self.S[k], 0, self.lds, self.XT[k], 0, self.ldq, B, self.E)
+                ops.copy_cols(self.act_next, 0, A, self.XT[k], self.E, self.ldq, B, A)
+
+    def _critic_backward(self):
+        """Critic backward through the Q MLPs; sum the broadcast embedding gradient over samples."""
+        qd, qa = self.q1.head_dims, self.q1.head_acts
+        self._mlp_backward("q", [self.XQ["q1"], self.XQ["q2"]], self.ldq, [self.q1.head(), self.q2.head()],
+                           [self.qact["q1"], self.qact["q2"]], [self.dq["q1"], self.dq["q2"]], 1,
+                           [self.q1.head(self.q1.grad), self.q2.head(self.q2.grad)], [self.dXQ["q1"], self.dXQ["q2"]],
+                           self.ldq, [self.R, self.R], qd, qa)
+        self._state_grads_from_q()
+
+    def _state_grads_from_q(self):
+        B, n = self.B, self.n
+        call("tacorl_reduce_rows_mod_batch", 2, ops.ptr_array([self.dXQ["q1"], self.dXQ["q2"]]), self.ldq,
+             ops.ptr_array([self.dS["q1"], self.dS["q2"]]), self.lds, B, self.E, 3 * n + 1, ops.stream())
 
     lean_mlp_acts = True  # hidden-layer outputs of the fused MLPs are recomputed by the weight-gradient launch, not saved
 

@@ -87,7 +87,7 @@ def check_plan_recognition(cfg, what):
 
 def check_action_decoder(cfg, what):
     """config/networks/action_decoder/logistic.yaml (reference action_decoder_logistic.py:21-71); the value checks
-    (relu rnn_decoder, discrete gripper, +-1 bounds, no dropout) are ActionDecoderLogistic.__init__'s."""
+    (relu rnn_decoder, +-1 bounds, no dropout; the gripper head discrete or absent) are ActionDecoderLogistic.__init__'s."""
     return _require(cfg, what, "ActionDecoderLogistic", {},
                     free=("n_mixtures", "num_layers", "hidden_size", "out_features", "act_max_bound", "act_min_bound",
                           "policy_rnn_dropout_p", "num_classes", "latent_plan_dim", "rnn_model", "include_goal",

@@ -1,0 +1,250 @@
+"""PlayLMP on vector observations - drop-in for reference modules/play_lmp/play_lmp_d4rl.py:17-241 (D4RL AntMaze): the seq-VAE
+of play_lmp_for_rl without a perceptual encoder and without a goal encoder.  The plan recognition reads the observation window
+(B,T,29) as it stands, the plan proposal reads [observations[:,0] | observations[:,-1,:2]], the action decoder (no discrete
+gripper: all 8 action dimensions are mixture dimensions) reads [plan | observations[:,t]].  `state_dict()` keys:
+`plan_recognition.*`, `plan_proposal.policy.*`, `action_decoder.*`.  The batch: `observations` (B,T,state_dim), `actions`
+(B,T,action_dim).  Nothing imports gym or d4rl (modules/d4rl_env.py).
+Select with `module._target_=tacorl_amd.modules.play_lmp.play_lmp_d4rl.PlayLMP`.
+"""
+import torch
+
+from ... import dist as _D
+from ... import ops
+from ..._lib import ACT_NONE, ACT_SILU, BF16, call, ptr
+from ...engine import _al4
+from ...init import init_views_
+from ...lightning import LightningModuleBase
+from ...networks.action_decoder import ActionDecoderLogistic
+from ...networks.plan_recognition import PlanRecognition
+from ...vec_engine import HeadBlock
+from .. import cfgcheck
+from ..common import GraphMixin, ModuleMixin, broadcast_blocks, register_views, to_plain
+from ..d4rl_env import GOAL_DIM, env_dims
+
+LOG_NAMES = ["kl_loss", "kl_loss_scaled", "action_loss", None, "random_plan_action_loss"]  # slots of self.logs
+
+
+class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
+    def __init__(self, actor={}, plan_proposal={}, plan_recognition={}, action_decoder={}, transform_manager={}, dataloader={},
+                 kl_beta: float = 1e-3, kl_balancing: bool = True, add_random_plan_loss: bool = False, kl_alpha: float = 0.8,
+                 lr: float = 1e-4, d4rl_env: str = "antmaze-large-diverse-v0", *args, state_dim=None, action_dim=None,
+                 device=None, compute_dtype="f32", world_size=1, **kwargs):
+        super().__init__()
+        self._init_runtime(device, compute_dtype, "f32", world_size)
+        self.automatic_optimization = False  # forward, backward and the fused Adam are one kernel sequence in training_step
+        self.save_hyperparameters()  # reference :53
+        self.d4rl_env, self.env, self.transform_manager, self.dataloader = d4rl_env, None, transform_manager, dataloader
+        self.state_dim, self.env_action_dim, self.act_bound = env_dims(d4rl_env, state_dim, action_dim)
+        self.goal_dim = GOAL_DIM
+        self.add_random_plan_loss = add_random_plan_loss
+        self.lr, self.kl_beta, self.kl_balancing, self.kl_alpha = lr, kl_beta, kl_balancing, kl_alpha
+        self.pp_cfg, self.pr_cfg, self.ad_cfg = to_plain(plan_proposal), to_plain(plan_recognition), to_plain(action_decoder)
+        self.build_networks()
+        if _D.collectives_on(self.world_size):
+            self.sync_from_rank0()
+
+    def build_networks(self):
+        """reference :55-82."""
+        pol = cfgcheck.check_actor(self.pp_cfg, "plan_proposal")
+        if self.pp_cfg.get("discrete_gripper", False):
+            raise NotImplementedError("plan_proposal: a latent plan has no discrete gripper")
+        self.policy_layers, self.hidden = pol.get("num_layers", 2), pol.get("hidden_dim", 256)
+        pr_kind, prc = cfgcheck.check_plan_recognition(self.pr_cfg, "plan_recognition")
+        if pr_kind != "transformer":
+            raise NotImplementedError("plan_recognition: the D4RL module is configured with the transformer posterior")
+        prc["state_dim"] = self.state_dim
+        self.pr = PlanRecognition(device=self.dev, **prc)
+        A = self.pr.latent_plan_dim
+        E = self.state_dim + self.goal_dim
+        pdims = [E] + [self.hidden] * self.policy_layers + [2 * A]
+        pn = [(f"policy.fc_layers.{i}.weight", f"policy.fc_layers.{i}.bias") for i in range(self.policy_layers)]
+        self.pp = HeadBlock(pdims, [ACT_SILU] * self.policy_layers + [ACT_NONE], pn, self.dev,
+                            head_parts=[("policy.fc_mean", A), ("policy.fc_log_std", A)])
+        adc = cfgcheck.check_action_decoder(self.ad_cfg, "action_decoder")
+        # out_features and the bounds come from the environment's action space (:58-60)
+        adc.update(state_dim=self.state_dim, out_features=self.env_action_dim,
+                   act_max_bound=[self.act_bound] * self.env_action_dim, act_min_bound=[-self.act_bound] * self.env_action_dim)
+        self.ad = ActionDecoderLogistic(device=self.dev, **adc)
+        init_views_(self.pr.blk.views)
+        init_views_(self.pp.views)
+        init_views_(self.ad.blk.views, rnn_hidden=self.ad.hidden)
+        self._pv = {"pr": register_views(self, "plan_recognition.", self.pr.blk.views),
+                    "pp": register_views(self, "plan_proposal.", self.pp.views),
+                    "ad": register_views(self, "action_decoder.", self.ad.blk.views)}
+        for k, v in self.ad.buffers.items():
+            self.action_decoder.register_buffer(k, v)
+        self.plan_proposal.action_dim, self.plan_proposal.state_dim, self.plan_proposal.goal_dim = A, self.state_dim, self.goal_dim
+        self.action_decoder.clear_hidden_state = self.ad.clear_hidden_state
+        self.action_decoder.act = lambda latent_plan, perceptual_emb, latent_goal=None, noise=None: self.ad.act(
+            latent_plan, perceptual_emb, latent_goal, noise=noise, compute=self.compute)
+
+    def _blocks(self):
+        return [self.pp, self.pr.blk, self.ad.blk]
+
+    def sync_from_rank0(self):
+        broadcast_blocks(self._blocks())
+        ops.touched(*[b.param for b in self._blocks()])
+
+    def set_kl_beta(self, kl_beta):
+        """reference :190-192."""
+        self.kl_beta = kl_beta
+
+    def named_gradients(self):
+        out = {f"plan_proposal.{k}": v for k, v in self.pp.grad_views.items()}
+        out.update({f"plan_recognition.{k}": v for k, v in self.pr.blk.grad_views.items()})
+        out.update({f"action_decoder.{k}": v for k, v in self.ad.blk.grad_views.items()})
+        return out
+
+    # --------------------------------------------------------------------------- training step
+    def _ensure(self, B, T):
+        if getattr(self, "_shape", None) == (B, T):
+            return
+        ops.note_alloc()
+        f = lambda *s: torch.zeros(*s, device=self.dev)  # noqa: E731
+        A, pp = self.pr.A, self.pp
+        self.lds = _al4(self.state_dim + self.goal_dim)
+        self.obs, self.goal, self.acts = f(B, T, self.state_dim), f(B, self.goal_dim), f(B, T, self.env_action_dim)
+        self.S = f(B, self.lds)
+        self.pact = f(ops.mlp_act_layout(B, pp.head_dims, pp.head_acts)[2])
+        self.p_yoff = ops.mlp_act_layout(B, pp.head_dims, pp.head_acts)[1][-1]
+        self.d_head_pp, self.d_head_pr = f(B, 2 * A), f(B, 2 * A)
+        self.plan, self.rplan, self.d_plan = f(B, A), f(B, A), f(B, A)
+        self.d_obs = f(B * T, self.state_dim)  # the decoder's gradient w.r.t. the observations: written, read by nothing
+        self.noise = dict(eps_plan=f(B, A), u_plan=f(B, A))
+        self.logs = f(16)  # 0 kl, 1 kl_scaled, 2 action_loss, 4 random-plan action_loss (3, 5: the decoder's second output)
+        self._shape = (B, T)
+
+    def _grad_arena(self):
+        """The three blocks' gradients as slices of one allocation (made on first use, i.e. only with several ranks)."""
+        a = self.__dict__.get("_grad_arena_t")
+        if a is None:
+            ops.note_alloc()
+            a = torch.zeros(sum(b.size for b in self._blocks()), device=self.dev)
+            o = 0
+            for b in self._blocks():
+                b.rebind_grad(a[o: o + b.size])
+                o += b.size
+            self.__dict__["_grad_arena_t"] = a
+        return a
+
+    def _fwd_bwd(self, B, T, gs):
+        """Device side of the step up to the gradients (fixed buffers only: hipGraph-capturable).  reference :108-144."""
+        pr, pp, ad, cd = self.pr, self.pp, self.ad, self.compute
+        A, Sd, emb = pr.A, self.state_dim, self.obs  # the "embeddings" are the observations: rows [B*T][state_dim]
+        if getattr(self, "_branch", None) is None:
+            self._branch = torch.cuda.Stream(device=self.dev)
+        main, s_rand = torch.cuda.current_stream(), self._branch
+        # logging-only decoder pass with a uniform random plan (:133-140) beside the proposal / recognition forward; the
+        # decoder's buffers are shared with the real pass, which waits for this branch
+        s_rand.wait_stream(main)
+        with torch.cuda.stream(s_rand):
+            call("tacorl_uniform_actions", ptr(self.noise["u_plan"]), ptr(self.rplan), A, B, A, 0, ops.stream())
+            ad.forward(self.rplan, emb, Sd, B, T, T - 1, cd)
+            ad.loss(self.acts, ops._at(self.logs, 4), B, T, T - 1, want_grad=False)
+        # plan proposal on [observations[:,0] | observations[:,-1,:2]] (:110-112): one row-assembly launch, one MLP
+        call("tacorl_vec_rows", ptr(emb), ptr(self.goal), None, None, None, ops.ptr_array([self.S, None, None, None, None]), None,
+             B, T, Sd, self.goal_dim, 0, 0, self.lds, self.lds, ops.stream())
+        pb = None
+        if cd == BF16:
+            import ctypes as C
+
+            call("tacorl_to_bf16_batch", 1, ops.ptr_array([pp.param]), ops.ptr_array([pp.param_bf16]), (C.c_long * 1)(pp.size),
+                 ops.stream())
+            pb = [pp.head_bf16()]
+        ops.mlp_fwd([self.S], self.lds, [pp.head()], [self.pact], [B], pp.head_dims, pp.head_acts, cd, params_bf16=pb)
+        head_pp = self.pact[self.p_yoff: self.p_yoff + B * 2 * A]
+        head_pr = pr.forward(emb, Sd, B, T, cd, train=self._pr_train)
+        call("tacorl_gauss_kl_balanced", ptr(head_pr), ptr(head_pp), ptr(self.d_head_pr), ptr(self.d_head_pp), B, A,
+             float(self.kl_alpha), float(self.kl_beta), float(pr.min_std), int(self.kl_balancing), gs, ptr(self.logs),
+             ops.stream())
+        # the plan proposal's backward stops at its head: nothing in front of it has parameters
+        ops.mlp_backward(("plmp_d4rl_pp", "plmp_d4rl_ppf"), [self.S], self.lds, [pp.head()], [self.pact], [self.d_head_pp], 2 * A,
+                         [pp.head(pp.grad)], [None], self.lds, [B], pp.head_dims, pp.head_acts, cd)
+        call("tacorl_pr_sample", ptr(head_pr), ptr(self.noise["eps_plan"]), ptr(self.plan), None, None, B, A, float(pr.min_std),
+             ops.stream())
+        main.wait_stream(s_rand)
+        ad.forward(self.plan, emb, Sd, B, T, T - 1, cd)
+        ad.loss(self.acts, ops._at(self.logs, 2), B, T, T - 1, want_grad=True, grad_scale=gs)
+        if self.add_random_plan_loss:
+            raise NotImplementedError("add_random_plan_loss=True is not used by any in-scope config")
+        ad.backward(B, T - 1, cd, need_input_grad=True)
+        # of the decoder's input gradient only the plan's share goes on (the observations are data)
+        call("tacorl_ad_input_bwd", ptr(ad.dx_seq), ptr(self.d_plan), ptr(self.d_obs), Sd, B, T, T - 1, ad.P, ad.E, 0, ops.stream())
+        call("tacorl_pr_sample_bwd", ptr(head_pr), ptr(self.noise["eps_plan"]), ptr(self.d_plan), ptr(self.d_head_pr), B, A,
+             float(pr.min_std), ops.stream())
+        pr.backward(self.d_head_pr, B, T, cd)
+
+    def _step(self, batch, noise=None, optimize=True, log_type="train"):
+        obs = batch["observations"]
+        B, T = obs.shape[:2]
+        pr = self.pr
+        opts = getattr(self, "_optimizers", None)
+        if opts and opts[0].lr != self.lr:  # lr edited on the optimiser (scheduler): a launch argument -> new captures
+            self.lr, self._graphs = opts[0].lr, {}
+        self._ensure(B, T)
+        gs = 1.0 / self.world_size
+        # the step's draws, in the reference's order: dropout masks, rsample, one uniform_(-1, 1) random plan (:114,130,133)
+        for k, buf in self.noise.items():
+            if noise is not None:
+                buf.copy_(noise[k].reshape(buf.shape))
+            elif k.startswith("eps"):
+                buf.normal_()
+            else:
+                buf.uniform_()
+        self._pr_train = bool(self.training and pr.dropout_p > 0)
+        if self._pr_train:
+            pr.stage_dropout(B, T, noise.get("dropout") if noise is not None else None)
+        self.obs.copy_(obs)
+        self.goal.copy_(obs[:, -1, :self.goal_dim])  # pp_goal = observations[:, -1, :2] (:111)
+        self.acts.copy_(batch["actions"])
+        reduce_on = optimize and _D.collectives_on(self.world_size)
+        if reduce_on:
+            self._grad_arena()  # (before anything is captured: the backward kernels write into the arena's slices)
+
+        def opt():
+            if optimize:
+                ops.adam_step_batch([(blk.param, blk.grad, blk.m, blk.v, self.lr, 0.0, blk.step, None, 0.0) for blk in self._blocks()])
+
+        def reduce_grads():
+            if reduce_on:
+                _D.all_reduce_sum_(self._grad_arena())  # ONE collective: [plan proposal | plan recognition | action decoder]
+
+        self._stepped_blocks = (lambda: [b.param for b in self._blocks()]) if optimize else None
+        self._run_segments(("playlmp_d4rl", B, T, optimize, self._pr_train), [lambda: self._fwd_bwd(B, T, gs), opt], [reduce_grads])
+        self._step_count += 1
+        if (optimize and self.log_every_n_steps > 1 and self._step_count % self.log_every_n_steps
+                and self.__dict__.get("_last_total") is not None):
+            return self.__dict__["_last_total"]
+        logs, div = _D.reduce_logs_(self.logs, self.world_size)
+        lg = [x / div for x in logs.cpu().tolist()]
+        for k, v in zip(LOG_NAMES, lg):
+            if k is not None:
+                self.log(f"{log_type}/{k}", v, on_step=True, on_epoch=True, sync_dist=True)
+        total = lg[1] + lg[2]
+        self.log(f"{log_type}/total_loss", total, on_step=True, on_epoch=True, sync_dist=True)
+        self.__dict__["_last_total"] = total
+        return total
+
+    def training_step(self, batch, batch_idx=0, noise=None):
+        """reference :194-204 (returns the total loss; the optimiser step has already run - manual optimisation)."""
+        out = self._step(batch, noise, True, "train")
+        self._tick_optimizers()
+        return out
+
+    def validation_step(self, batch, batch_idx=0, noise=None):
+        return self._step(batch, noise, False, "validation")
+
+    def configure_optimizers(self):
+        """reference :235-241: ONE Adam over every parameter.  A BlockAdam spanning the three flat blocks."""
+        ent = [(blk, self._pv[k], blk.views_of(blk.m), blk.views_of(blk.v))
+               for k, blk in (("pr", self.pr.blk), ("pp", self.pp), ("ad", self.ad.blk))]
+        self._optimizers = [self._make_adam("adam", ent, self.lr)]
+        return self._optimizers[0]
+
+
+def load_play_lmp(play_lmp_dir, epoch=-1, overwrite_cfg=None, device=None, compute_dtype="f32", unsafe_pickle=False):
+    """load_pl_module_from_checkpoint (reference utils/networks.py:90-117) for this class: the image module's loader."""
+    from .play_lmp_for_rl import load_play_lmp as _load
+
+    return _load(play_lmp_dir, epoch, overwrite_cfg, device=device, compute_dtype=compute_dtype, unsafe_pickle=unsafe_pickle,
+                 module_cls=PlayLMP)

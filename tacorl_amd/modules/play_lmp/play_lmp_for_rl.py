@@ -130,7 +130,7 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
 
 
 def load_play_lmp(play_lmp_dir, epoch=-1, overwrite_cfg=None, device=None, compute_dtype="f32", image_dtype="f32",
-                  unsafe_pickle=False):
+                  unsafe_pickle=False, module_cls=None):
     """utils/networks.py:90-117 load_pl_module_from_checkpoint: the run directory's first `*config.yaml` (loaded as
     a whole and resolved, so `${latent_plan_dim}`-style interpolations arrive as values) + `last.ckpt` or the
     checkpoint of epoch N.  The checkpoint is read with weights_only=True (a state_dict needs nothing else);
@@ -154,8 +154,11 @@ def load_play_lmp(play_lmp_dir, epoch=-1, overwrite_cfg=None, device=None, compu
     cfg = load_resolved_yaml(cfgs[0])["module"]
     cfg = {k: v for k, v in cfg.items() if k not in ("_target_", "_recursive_")}
     cfg.update(overwrite_cfg or {})
-    cfg.setdefault("real_world", True)
-    mod = PlayLMP(device=device, compute_dtype=compute_dtype, image_dtype=image_dtype, **cfg)
+    if module_cls is None:
+        cfg.setdefault("real_world", True)
+        mod = PlayLMP(device=device, compute_dtype=compute_dtype, image_dtype=image_dtype, **cfg)
+    else:  # another PlayLMP class of this package (play_lmp_d4rl.PlayLMP: vector observations, no image options)
+        mod = module_cls(device=device, compute_dtype=compute_dtype, **cfg)
     import os
 
     unsafe_pickle = unsafe_pickle or os.environ.get("TACORL_UNSAFE_PICKLE", "") not in ("", "0")

@@ -1,7 +1,8 @@
 """ActionDecoderLogistic on HIP kernels (reference
 networks/action_decoders/action_decoder_logistic.py:21-300, rnn_models.py:5-16):
 2-layer ReLU RNN (hidden 2048) over [plan | perceptual emb] -> mixture heads -> discretised
-logistic-mixture NLL + gripper cross-entropy.
+logistic-mixture NLL + gripper cross-entropy.  discrete_gripper=False (the D4RL decoder, :52,134-138,265-266): every action
+dimension is a mixture dimension - three heads, no gripper_fc / gripper_bounds, no cross-entropy term.
 
 Internals are time-major ([t][b] rows) so every per-step slice and every BPTT operand pair is a
 contiguous row range; the four heads (mean_fc | log_scale_fc | prob_fc | gripper_fc) are stored
@@ -24,30 +25,35 @@ class ActionDecoderLogistic:
                  act_max_bound=(1.0,) * 7, act_min_bound=(-1.0,) * 7, gripper_alpha=1.0, policy_rnn_dropout_p=0.0,
                  num_layers=2, rnn_model="rnn_decoder", discrete_gripper=True, include_goal=False, num_classes=10,
                  n_mixtures=10, **unused):
-        if rnn_model != "rnn_decoder" or not discrete_gripper or include_goal or policy_rnn_dropout_p != 0.0:
-            raise NotImplementedError("only the configured decoder (relu nn.RNN, discrete gripper, no goal) is in scope")
+        if rnn_model != "rnn_decoder" or include_goal or policy_rnn_dropout_p != 0.0:
+            raise NotImplementedError("only the configured decoder (relu nn.RNN, no goal, no dropout) is in scope")
+        dg = self.discrete_gripper = bool(discrete_gripper)
+        if not dg and (len(act_max_bound) != out_features or len(act_min_bound) != out_features):
+            raise ValueError(f"action bounds need out_features = {out_features} entries (reference :167-168)")
         if any(abs(b - 1.0) > 0 for b in act_max_bound) or any(abs(b + 1.0) > 0 for b in act_min_bound):
             raise NotImplementedError("action bounds other than +-1 (config/networks/action_decoder/logistic.yaml)")
         self.dev, self.P, self.E, self.hidden, self.L = device, latent_plan_dim, state_dim, hidden_size, num_layers
-        self.Da, self.K, self.num_classes, self.gripper_alpha = out_features - 1, n_mixtures, num_classes, gripper_alpha
+        self.Da, self.K, self.num_classes, self.gripper_alpha = out_features - int(dg), n_mixtures, num_classes, gripper_alpha
+        self.AW = out_features  # floats of an action row: [Da mixture dimensions | gripper command (discrete gripper)]
         self.include_goal = include_goal
-        H, In, DK = hidden_size, state_dim + latent_plan_dim, (out_features - 1) * n_mixtures
+        H, In, DK = hidden_size, state_dim + latent_plan_dim, self.Da * n_mixtures
         spec = []
         for l in range(num_layers):
             spec += [(f"rnn.weight_ih_l{l}", (H, In if l == 0 else H)), (f"rnn.weight_hh_l{l}", (H, H)),
                      (f"rnn.bias_ih_l{l}", (H,)), (f"rnn.bias_hh_l{l}", (H,))]
+        grip = lambda shape: [("gripper_fc." + shape[0], shape[1])] if dg else []  # noqa: E731
         spec += [("mean_fc.weight", (DK, H)), ("log_scale_fc.weight", (DK, H)), ("prob_fc.weight", (DK, H)),
-                 ("gripper_fc.weight", (2, H)), ("mean_fc.bias", (DK,)), ("log_scale_fc.bias", (DK,)),
-                 ("prob_fc.bias", (DK,)), ("gripper_fc.bias", (2,))]
+                 *grip(("weight", (2, H))), ("mean_fc.bias", (DK,)), ("log_scale_fc.bias", (DK,)),
+                 ("prob_fc.bias", (DK,)), *grip(("bias", (2,)))]
         self.blk = TensorBlock(spec, device)
-        self.NH = 3 * DK + 2
+        self.NH = 3 * DK + (2 if dg else 0)
         assert DK % 4 == 0, "head packing needs Da*K % 4 == 0"
         t = lambda v: torch.tensor(v, device=device, dtype=torch.float32)  # noqa: E731
-        mx, mn = t(list(act_max_bound)[:-1]), t(list(act_min_bound)[:-1])
+        mx, mn = t(list(act_max_bound)[:self.Da]), t(list(act_min_bound)[:self.Da])
         self.buffers = {  # register_buffer'ed by the reference (state-dict interchange)
             "one_hot_embedding_eye": torch.eye(n_mixtures, device=device),
             "ones": torch.ones(1, 1, n_mixtures, device=device),
-            "gripper_bounds": t([act_min_bound[-1], act_max_bound[-1]]),
+            **({"gripper_bounds": t([act_min_bound[-1], act_max_bound[-1]])} if dg else {}),
             "action_max_bound": mx.view(1, 1, -1, 1) * torch.ones(1, 1, 1, n_mixtures, device=device),
             "action_min_bound": mn.view(1, 1, -1, 1) * torch.ones(1, 1, 1, n_mixtures, device=device),
         }
@@ -61,7 +67,7 @@ class ActionDecoderLogistic:
     def act(self, latent_plan, perceptual_emb, latent_goal=None, noise=None, compute=None):
         """ActionDecoderLogistic.act (reference :87-97): ONE decoder step per call with the RNN's hidden state carried
         between calls (rollout: evaluation/rollout_manager.py:375-386).  latent_plan (B,P); perceptual_emb (B,1,E);
-        returns the sampled action (B,1,7).  noise = (rand_a (B,1,6,K), rand_b (B,1,6)) injects the two U(0,1) draws
+        returns the sampled action (B,1,7) - (B,1,Da) without the discrete gripper.  noise = (rand_a (B,1,6,K), rand_b (B,1,6)) injects the two U(0,1) draws
         of `_sample` (:247,258)."""
         if latent_goal is not None:
             raise NotImplementedError("include_goal=False is the configured decoder")
@@ -73,7 +79,7 @@ class ActionDecoderLogistic:
             ops.note_alloc()
             self._act_x, self._act_xin = f(B, self.P + self.E), f(B, H)
             self._act_h = [[f(B, H) for _ in range(L)] for _ in range(2)]  # ping-pong: previous / new hidden state
-            self._act_heads, self._act_out = f(B, (self.NH + 31) // 32 * 32), f(B, self.Da + 1)
+            self._act_heads, self._act_out = f(B, (self.NH + 31) // 32 * 32), f(B, self.AW)
             self._act_ra, self._act_rb = f(B, self.Da, self.K), f(B, self.Da)
             nb = ops.L.lib().tacorl_linear_add_fwd_ws_bytes(1, ops.int_array([B]), H, H)
             self._act_ws = torch.empty(max(256, nb), dtype=torch.uint8, device=self.dev)
@@ -103,11 +109,12 @@ class ActionDecoderLogistic:
         else:
             self._act_ra.uniform_()
             self._act_rb.uniform_()
-        call("tacorl_logistic_mixture_sample", ptr(self._act_heads), self._act_heads.shape[1], ptr(self._act_ra),
-             ptr(self._act_rb), ptr(self._act_out), B, self.Da, self.K, ops.stream())
+        call("tacorl_logistic_mixture_sample" if self.discrete_gripper else "tacorl_logistic_mixture_nogrip_sample",
+             ptr(self._act_heads), self._act_heads.shape[1], ptr(self._act_ra), ptr(self._act_rb), ptr(self._act_out), B, self.Da,
+             self.K, ops.stream())
         self._act_flip ^= 1
         self.hidden_state = torch.stack(new)  # (num_layers, B, H) as nn.RNN's h_n
-        return self._act_out.view(B, 1, self.Da + 1).clone()
+        return self._act_out.view(B, 1, self.AW).clone()
 
     def _ensure(self, B, Tm):
         if self._shape == (B, Tm):
@@ -196,7 +203,7 @@ class ActionDecoderLogistic:
         self._mirror_ring, self._mirror_shape = self._ring_proj(), (B, Tm)
         if self._mirror_ring:
             call("tacorl_pad_to_bf16", blk.p("rnn.weight_ih_l0"), self.P + self.E, ptr(self.wih0_b), 128, H, self.P + self.E, ops.stream())
-        ob = blk.off["mean_fc.bias"][0]  # the four heads' biases sit back to back
+        ob = blk.off["mean_fc.bias"][0]  # the heads' biases sit back to back
         self.headb[: self.NH].copy_(blk.param[ob: ob + self.NH])
 
     def prepare_backward(self, B, Tm, compute):
@@ -372,14 +379,18 @@ class ActionDecoderLogistic:
                       ldy=self.NHP)
 
     def loss(self, actions, loss_out, B, T, Tm, want_grad, grad_scale=1.0, twin=None, lazy=False):
-        """actions: device [B][T][Da+1]; writes the scalar loss to loss_out (device float) and, if
+        """actions: device [B][T][AW]; writes the scalar loss to loss_out (device float) and, if
         want_grad, dL/dheads into self.d_heads.  twin: the loss of that twin pass's heads instead (no gradient).
         lazy: the scalar is only logged - leave the per-block partial sums in the workspace; finish_loss() (the module calls it
         before it reads the logs) sums them into loss_out.  One launch fewer at the end of the step's decoder branch."""
         heads, ws = (self.heads, self.ws) if twin is None else (twin.heads, twin.ws)
-        call("tacorl_logistic_mixture_loss", ptr(heads), self.NHP, ptr(actions), ptr(self.d_heads) if want_grad and twin is None else None,
-             None if lazy else loss_out, B, T, Tm, self.Da, self.K, self.num_classes, float(self.gripper_alpha), float(grad_scale),
-             ptr(ws), ws.numel(), ops.stream())
+        d_heads = ptr(self.d_heads) if want_grad and twin is None else None
+        if self.discrete_gripper:
+            call("tacorl_logistic_mixture_loss", ptr(heads), self.NHP, ptr(actions), d_heads, None if lazy else loss_out, B, T, Tm,
+                 self.Da, self.K, self.num_classes, float(self.gripper_alpha), float(grad_scale), ptr(ws), ws.numel(), ops.stream())
+        else:
+            call("tacorl_logistic_mixture_nogrip_loss", ptr(heads), self.NHP, ptr(actions), d_heads, None if lazy else loss_out, B, T,
+                 Tm, self.Da, self.K, self.num_classes, float(grad_scale), ptr(ws), ws.numel(), ops.stream())
         self._lazy_loss = (ws, B, Tm, loss_out) if lazy else None
 
     def finish_loss(self):
@@ -387,17 +398,21 @@ class ActionDecoderLogistic:
         pend = getattr(self, "_lazy_loss", None)
         if pend is not None:
             ws, B, Tm, loss_out = pend
-            call("tacorl_logistic_mixture_finish", ptr(ws), ws.numel(), B, Tm, self.Da, loss_out, ops.stream())
+            call("tacorl_logistic_mixture_finish" if self.discrete_gripper else "tacorl_logistic_mixture_nogrip_finish", ptr(ws),
+                 ws.numel(), B, Tm, self.Da, loss_out, ops.stream())
 
     def loss_step(self, module, actions, plan, B, T, optimize, frozen=False, defer_update=False, mirrors_current=False,
-                  prepared=False):
+                  prepared=False, emb=None):
         """TACORL.compute_action_decoder_update (reference tacorl.py:206-233): loss on emb[:, :-1],
-        actions[:, :-1]; logged always, Adam step when fine-tuning."""
+        actions[:, :-1]; logged always, Adam step when fine-tuning.  emb = (rows [B*T][ld], ld): the decoder's per-frame
+        input as the caller has it (vector observations); default: the module's camera embeddings."""
         from .._lib import LOG_SLOTS
 
         acts = actions
-        cams = module.action_decoder_modalities
-        if len(cams) == 1:  # one camera: the frame embeddings as the encoder wrote them
+        cams = module.action_decoder_modalities if emb is None else None
+        if emb is not None:
+            emb, ld = emb
+        elif len(cams) == 1:  # one camera: the frame embeddings as the encoder wrote them
             emb, ld = module.f_out[cams[0]], 32
         elif cams == module.plan_recognition_modalities:  # already concatenated for the plan recognition
             emb, ld = module.pr_in, module.pr_in.shape[1]

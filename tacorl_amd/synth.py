@@ -109,3 +109,25 @@ def tensor_stats(t, k=16):
     n = f.numel()
     idx = (np.arange(k, dtype=np.int64) * 2654435761 + 12345) % max(n, 1)
     return np.concatenate([[f.norm().item(), f.sum().item()], f[torch.from_numpy(idx)].numpy()])
+
+
+def make_d4rl_window_batch(seed, B, T, state_dim=29, action_dim=8, goal_dim=2):
+    """The reference's D4RL window batch (datamodule/dataset/d4rl_dataset.py: `observations` (B,T,S), `actions` (B,T,A) in
+    [-1, 1], `goal` (B,G), `goal_reached` (B,)).  Some actions sit on and just inside the bounds +-1 - the two edge branches of
+    the decoder's discretised-logistic likelihood - and both values of goal_reached appear from B = 2 on."""
+    rs = _rs(seed, "d4rl_window")
+    obs = rs.uniform(-1.0, 1.0, size=(B, T, state_dim)).astype(np.float32)
+    act = rs.uniform(-1.0, 1.0, size=(B, T, action_dim)).astype(np.float32)
+    edge = rs.uniform(size=(B, T, action_dim))
+    act[edge < 0.06] = -1.0
+    act[(edge >= 0.06) & (edge < 0.09)] = -0.9995
+    act[(edge >= 0.09) & (edge < 0.12)] = 0.9995
+    act[edge >= 0.94] = 1.0
+    for t, v in enumerate((-1.0, -0.9995, 0.9995, 1.0)):  # (each of them at least once among the steps the decoder scores)
+        act[0, t % max(T - 1, 1), t % action_dim] = v
+    goal = rs.uniform(-1.0, 1.0, size=(B, goal_dim)).astype(np.float32)
+    reached = rs.uniform(size=B) < 0.3
+    if B >= 2:
+        reached[0], reached[1] = True, False
+    return {"observations": torch.from_numpy(obs), "actions": torch.from_numpy(act), "goal": torch.from_numpy(goal),
+            "goal_reached": torch.from_numpy(reached), "idx": torch.arange(B)}
