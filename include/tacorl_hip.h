@@ -451,6 +451,27 @@ int tacorl_sample_transitions(const long* possible_steps, long n_possible, const
                               const long* idx, const long* strategy, const long* disp, const double* u_choice,
                               long current_horizon, long n_frames, int B, int A, long* ids, float* action,
                               float* reward, float* done, int* status, tacorl_stream_t stream);
+/* The window sampler of the vector-observation dataset (reference datamodule/dataset/d4rl_play_dataset.py:69-146) over
+ * resident tables, one 64-lane wavefront per window b < B (four windows per block, grid ceil(B / 4)):
+ *   s = episode_lookup[idx[b]], ws = window[b] in [min_window, Tmax];
+ *   obs[b] (Tmax, S) = observations[s : s + ws], then the window's last row repeated; act[b] (Tmax, A) = actions[s : s + ws],
+ *   then zero rows; and with G > 0 (G = 2 for AntMaze; G = 0: no goal, disp is not read):
+ *   end = ep_end[k] of the last episode with ep_start[k] <= s (binary search), goal_step = min(end, s + (ws - 1) * disp[b])
+ *   decided without forming a product that could overflow, goal[b] = observations[goal_step][0:G],
+ *   reached[b] = done[b] = (sqrtf(dx*dx + dy*dy) < threshold ? 1 : 0) in fp32 with (dx, dy) = goal[b][0:2] -
+ *   observations[s + ws - 1][0:2].  window_size (B) int64 = ws; ids (2, B) int64 = [s | goal_step] (goal_step = s when G = 0).
+ * goal, reached, done, window_size and ids may each be NULL (not written).  The tables are validated by the host
+ * (tacorl_amd/data/d4rl_replay.py D4RLWindowIndex) and every id they can produce lies in [0, n_frames); idx, window, disp
+ * (>= 1), s and goal_step are nevertheless clamped into range before any table access, and *status is set to 1 (it is never
+ * cleared here) when a clamp changed a value.  All pointers are device pointers, 8-byte (int64) or 4-byte (float / int)
+ * aligned.  Nothing is allocated; a non-positive size, G == 1 or G > S, min_window outside [1, Tmax], n_frames < Tmax or a
+ * NULL required / misaligned pointer is refused with TACORL_EINVAL before anything is launched. */
+int tacorl_sample_d4rl_windows(const long* episode_lookup, long n_items, const long* ep_start, const long* ep_end,
+                               int n_episodes, const float* observations, const float* actions, long n_frames,
+                               const long* idx, const long* window, const long* disp, int B, int Tmax, int S, int A,
+                               int G, int min_window, float threshold, float* obs, float* act, float* goal,
+                               float* reached, float* done, long* window_size, long* ids, int* status,
+                               tacorl_stream_t stream);
 /* dst[r][0:cols] (+)= src[r % src_row_mod][0:cols]  (src_row_mod <= 0: r).  expand_obs on
  * embeddings instead of images (reference utils/misc.py:132-153) and torch.cat plumbing. */
 int tacorl_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, int rows, int cols,

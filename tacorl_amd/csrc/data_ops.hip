@@ -249,7 +249,106 @@ __global__ __launch_bounds__(256) void sample_transitions_kernel(TransTbl t, int
   if (bad) *t.status = 1;
 }
 
+// Window sampling of the vector-observation dataset (reference datamodule/dataset/d4rl_play_dataset.py:69-146) over resident
+// tables: one 64-lane wavefront per window, four windows per block.  The index arithmetic is uniform over the wavefront (the
+// window id is made a scalar, so the table reads are scalar loads); the lanes then copy the window's rows - one contiguous span
+// of ws * S floats in the table and in the batch - as coalesced dwords (S = 29: a span is 4-byte aligned only) and write the
+// padding rows.  Validated on the host (tacorl_amd/data/d4rl_replay.py D4RLWindowIndex); the clamps stand in front of every
+// table access all the same, and a clamp that changed a value raises the status word (plain store: every writer stores 1).
+struct D4rlTbl {
+  const long* lookup; long n_items;             // episode_lookup: item -> first frame of its window
+  const long* ep_start; const long* ep_end; int n_ep;
+  const float* observations; const float* actions; long n_frames;  // (n_frames, S), (n_frames, A)
+  const long* idx; const long* window; const long* disp;
+  float* obs; float* act; float* goal; float* reached; float* done; long* window_size; long* ids; int* status;
+};
+
+__global__ __launch_bounds__(256) void sample_d4rl_windows_kernel(D4rlTbl t, int B, int Tmax, int S, int A, int G, int min_window,
+                                                                  float threshold) {
+  const int b = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  bool bad = false;
+  long pos = t.idx[b];
+  if (pos < 0 || pos >= t.n_items) { bad = true; pos = pos < 0 ? 0 : t.n_items - 1; }
+  long wl = t.window[b];
+  if (wl < min_window || wl > Tmax) { bad = true; wl = wl < min_window ? min_window : Tmax; }
+  const int ws = (int)wl;
+  long s = t.lookup[pos];
+  if (s < 0 || s > t.n_frames - ws) { bad = true; s = s < 0 ? 0 : t.n_frames - ws; }  // rows s .. s + ws - 1 exist
+  long goal_step = s;
+  if (G > 0) {
+    // episode end: the last episode whose start is <= s (binary search over the sorted starts)
+    int lo = 0, hi = t.n_ep;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (t.ep_start[mid] <= s) lo = mid + 1; else hi = mid;
+    }
+    const long end = t.ep_end[lo > 0 ? lo - 1 : 0];
+    long d = t.disp[b];
+    if (d < 1) { bad = true; d = 1; }
+    // min(end, s + (ws - 1) * disp) without the overflow of a huge draw: the product is formed only where it stays <= end
+    const long stride = ws - 1;
+    goal_step = (stride == 0 || end < s || d > (end - s) / stride) ? (stride == 0 ? s : end) : s + stride * d;
+    if (goal_step < 0 || goal_step > t.n_frames - 1) { bad = true; goal_step = goal_step < 0 ? 0 : t.n_frames - 1; }
+  }
+  {
+    const float* __restrict__ src = t.observations + s * S;
+    float* __restrict__ dst = t.obs + (long)b * Tmax * S;
+    const int n = ws * S, last = n - S, pad = (Tmax - ws) * S;
+    for (int i = lane; i < n; i += 64) dst[i] = src[i];
+    for (int i = lane; i < pad; i += 64) dst[n + i] = src[last + i % S];  // pad_with_repetition: the window's last row
+  }
+  {
+    const float* __restrict__ src = t.actions + s * A;
+    float* __restrict__ dst = t.act + (long)b * Tmax * A;
+    const int n = ws * A, pad = (Tmax - ws) * A;
+    for (int i = lane; i < n; i += 64) dst[i] = src[i];
+    for (int i = lane; i < pad; i += 64) dst[n + i] = 0.f;  // pad_with_zeros
+  }
+  if (lane != 0) return;
+  if (G > 0) {
+    const float* __restrict__ g = t.observations + goal_step * S;
+    const float* __restrict__ e = t.observations + (s + ws - 1) * S;
+    if (t.goal)
+      for (int k = 0; k < G; k++) t.goal[(long)b * G + k] = g[k];
+    // ||goal - observations[s + ws - 1][:2]|| < goal_threshold in fp32, the products and the sum rounded one by one
+    const float dx = g[0] - e[0], dy = g[1] - e[1];
+    const float r = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy))) < threshold ? 1.f : 0.f;
+    if (t.reached) t.reached[b] = r;
+    if (t.done) t.done[b] = r;
+  }
+  if (t.window_size) t.window_size[b] = ws;
+  if (t.ids) { t.ids[b] = s; t.ids[(long)B + b] = goal_step; }
+  if (bad) *t.status = 1;
+}
+
 }  // namespace
+
+extern "C" int tacorl_sample_d4rl_windows(const long* episode_lookup, long n_items, const long* ep_start, const long* ep_end,
+                                          int n_episodes, const float* observations, const float* actions, long n_frames,
+                                          const long* idx, const long* window, const long* disp, int B, int Tmax, int S, int A,
+                                          int G, int min_window, float threshold, float* obs, float* act, float* goal,
+                                          float* reached, float* done, long* window_size, long* ids, int* status,
+                                          tacorl_stream_t stream) {
+  if (B <= 0 || Tmax <= 0 || S <= 0 || A <= 0 || n_items <= 0 || n_episodes <= 0) return TACORL_EINVAL;
+  if (G < 0 || G == 1 || G > S || min_window < 1 || min_window > Tmax || n_frames < Tmax) return TACORL_EINVAL;
+  if ((long)Tmax * S > 0x7fffffffL || (long)Tmax * A > 0x7fffffffL || (long)B + 3 > 0x7fffffffL) return TACORL_EINVAL;
+  const void* p8[] = {episode_lookup, ep_start, ep_end, idx, window, disp};
+  const void* p4[] = {observations, actions, obs, act, status};
+  for (const void* p : p8)
+    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
+  for (const void* p : p4)
+    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
+  if (((uintptr_t)goal & 3) || ((uintptr_t)reached & 3) || ((uintptr_t)done & 3) || ((uintptr_t)window_size & 7) ||
+      ((uintptr_t)ids & 7))
+    return TACORL_EINVAL;
+  const D4rlTbl t{episode_lookup, n_items, ep_start, ep_end, n_episodes, observations, actions, n_frames, idx, window, disp,
+                  obs, act, goal, reached, done, window_size, ids, status};
+  hipLaunchKernelGGL(sample_d4rl_windows_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, t, B, Tmax, S, A, G,
+                     min_window, threshold);
+  return LAUNCH_OK();
+}
 
 extern "C" int tacorl_sample_transitions(const long* possible_steps, long n_possible, const long* ep_start,
                                          const long* ep_end, int n_episodes, const long* nn_ptr, long n_nn,

@@ -1,2 +1,3 @@
 """Replay data path: play-window / goal sampling, the uint8 dataset resident in HBM (or in pinned
-host memory behind a copy stream), GPU augmentations."""
+host memory behind a copy stream), GPU augmentations; the vector-observation (D4RL) window replay and its datamodule
+(d4rl_replay.py)."""

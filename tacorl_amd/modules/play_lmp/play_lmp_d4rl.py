@@ -3,7 +3,8 @@ of play_lmp_for_rl without a perceptual encoder and without a goal encoder.  The
 (B,T,29) as it stands, the plan proposal reads [observations[:,0] | observations[:,-1,:2]], the action decoder (no discrete
 gripper: all 8 action dimensions are mixture dimensions) reads [plan | observations[:,t]].  `state_dict()` keys:
 `plan_recognition.*`, `plan_proposal.policy.*`, `action_decoder.*`.  The batch: `observations` (B,T,state_dim), `actions`
-(B,T,action_dim).  Nothing imports gym or d4rl (modules/d4rl_env.py).
+(B,T,action_dim), or a fused replay batch `{"replay": ...}` (data/d4rl_replay.py).  Nothing imports gym or d4rl
+(modules/d4rl_env.py).
 Select with `module._target_=tacorl_amd.modules.play_lmp.play_lmp_d4rl.PlayLMP`.
 """
 import torch
@@ -175,8 +176,16 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         pr.backward(self.d_head_pr, B, T, cd)
 
     def _step(self, batch, noise=None, optimize=True, log_type="train"):
-        obs = batch["observations"]
-        B, T = obs.shape[:2]
+        rb = batch.get("replay")  # a fused replay batch (data/d4rl_replay.py): the sampler writes self.obs / self.acts itself
+        if rb is not None:
+            rp = rb["replay"]
+            if rb.get("kind") != "d4rl_window" or rp.S != self.state_dim or rp.A != self.env_action_dim:
+                raise ValueError(f"the replay batch ({rb.get('kind')}: S {rp.S}, A {rp.A}) does not fit this module "
+                                 f"({self.state_dim}, {self.env_action_dim})")
+            obs, (B, T) = None, (rb["B"], rb["T"])
+        else:
+            obs = batch["observations"]
+            B, T = obs.shape[:2]
         pr = self.pr
         opts = getattr(self, "_optimizers", None)
         if opts and opts[0].lr != self.lr:  # lr edited on the optimiser (scheduler): a launch argument -> new captures
@@ -194,9 +203,13 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self._pr_train = bool(self.training and pr.dropout_p > 0)
         if self._pr_train:
             pr.stage_dropout(B, T, noise.get("dropout") if noise is not None else None)
-        self.obs.copy_(obs)
-        self.goal.copy_(obs[:, -1, :self.goal_dim])  # pp_goal = observations[:, -1, :2] (:111)
-        self.acts.copy_(batch["actions"])
+        if rb is not None:
+            rb["replay"].sample_into(rb["draws"], obs=self.obs, actions=self.acts)
+            self.goal.copy_(self.obs[:, -1, :self.goal_dim])
+        else:
+            self.obs.copy_(obs)
+            self.goal.copy_(obs[:, -1, :self.goal_dim])  # pp_goal = observations[:, -1, :2] (:111)
+            self.acts.copy_(batch["actions"])
         reduce_on = optimize and _D.collectives_on(self.world_size)
         if reduce_on:
             self._grad_arena()  # (before anything is captured: the backward kernels write into the arena's slices)

@@ -4,7 +4,8 @@
 "action") -> action-decoder loss on observations[:, :-1] / actions[:, :-1] (an Adam step when fine-tuning) -> CQL update on
 (s, s', g) = ([observations[:,0] | goal], [observations[:,-1] | goal]), r = d = goal_reached, target entropy -action_dim of the
 ENVIRONMENT (-8) although the RL action is the 16-d plan.  The actor is the LMP's plan proposal; the critics are fresh and
-mirror its layers and hidden size.  The batch: `observations` (B,T,29), `actions` (B,T,8), `goal` (B,2), `goal_reached` (B,).
+mirror its layers and hidden size.  The batch: `observations` (B,T,29), `actions` (B,T,8), `goal` (B,2), `goal_reached` (B,) -
+or a fused replay batch `{"replay": ...}` (data/d4rl_replay.py), whose sampler launch writes the step's buffers itself.
 Select with `module._target_=tacorl_amd.modules.tacorl.tacorl_d4rl.TACORL`.
 """
 from pathlib import Path
@@ -75,7 +76,27 @@ class TACORL(CQL_Offline):
         return out
 
     # ---------------------------------------------------------------------- stepping
+    def _stage_replay(self, rb, noise):
+        """A fused replay batch (data/d4rl_replay.py HbmD4RLReplay.batch(fused=True)): ONE sampler launch writes the window
+        into the step's own buffers - observations, actions, goal, reward = done = goal_reached - in place of the five copies."""
+        B, T, rp = rb["B"], rb["T"], rb["replay"]
+        if rb.get("kind") != "d4rl_window" or rp.S != self.state_dim or rp.A != self.env_action_dim or rp.G != self.goal_dim:
+            raise ValueError(f"the replay batch ({rb.get('kind')}: S {rp.S}, A {rp.A}, G {rp.G}) does not fit this module "
+                             f"({self.state_dim}, {self.env_action_dim}, {self.goal_dim})")
+        e = self.engine
+        e.extra_normal = {"eps_pr": (B, self.action_dim)}
+        e.ensure_batch(B, T)
+        self.eps_pr = e.extra_noise["eps_pr"]
+        if self._acts is None or self._acts.shape[:2] != (B, T):
+            ops.note_alloc()
+            self._acts = torch.zeros(B, T, self.env_action_dim, device=self.dev)
+        rp.sample_into(rb["draws"], obs=e.obs, actions=self._acts, goal=e.goal, reached=e.reward, done=e.done)
+        e.set_noise(noise)
+        return B, T
+
     def _stage(self, batch, noise):
+        if "replay" in batch:
+            return self._stage_replay(batch["replay"], noise)
         obs = batch["observations"]
         B, T = obs.shape[:2]
         e = self.engine

@@ -317,6 +317,31 @@ def sample_transitions(tables, draws, current_horizon, ids, action, reward, done
          int(tables["n_frames"]), B, A, ptr(ids), ptr(action), ptr(reward), ptr(done), ptr(status), stream())
 
 
+def sample_d4rl_windows(tables, draws, Tmax, G, min_window, threshold, obs, act, status, goal=None, reached=None, done=None,
+                        window_size=None, ids=None):
+    """The D4RL window sampler over resident tables (data/d4rl_replay.py HbmD4RLReplay): tables = device tensors `lookup`,
+    `ep_start`, `ep_end` (int64), `observations` (N, S), `actions` (N, A) f32 and the int `n_frames`; draws = device `idx`,
+    `window`, `disp` (int64), B each.  Writes obs (B, Tmax, S), act (B, Tmax, A) and, where given, goal (B, G), reached (B),
+    done (B) f32, window_size (B) and ids (2, B) int64 = [start | goal_step]; raises the int32 `status` word on a clamp."""
+    B = draws["idx"].numel()
+    S, A = tables["observations"].shape[1], tables["actions"].shape[1]
+    i64 = [tables[k] for k in ("lookup", "ep_start", "ep_end")] + [draws[k] for k in ("idx", "window", "disp")]
+    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64)
+    assert all(draws[k].numel() == B for k in ("idx", "window", "disp"))
+    assert tables["observations"].shape[0] >= tables["n_frames"] and tables["actions"].shape[0] >= tables["n_frames"]
+    _f32(tables["observations"]), _f32(tables["actions"])
+    for t, n in ((obs, B * Tmax * S), (act, B * Tmax * A), (goal, B * G), (reached, B), (done, B)):
+        assert t is None or _f32(t).numel() == n, (None if t is None else tuple(t.shape), n)
+    for t, n in ((window_size, B), (ids, 2 * B)):
+        assert t is None or (t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.numel() == n)
+    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+    call("tacorl_sample_d4rl_windows", ptr(tables["lookup"]), tables["lookup"].numel(), ptr(tables["ep_start"]),
+         ptr(tables["ep_end"]), tables["ep_start"].numel(), ptr(tables["observations"]), ptr(tables["actions"]),
+         int(tables["n_frames"]), ptr(draws["idx"]), ptr(draws["window"]), ptr(draws["disp"]), B, int(Tmax), S, A, int(G),
+         int(min_window), float(threshold), ptr(obs), ptr(act), ptr(goal), ptr(reached), ptr(done), ptr(window_size), ptr(ids),
+         ptr(status), stream())
+
+
 def _at(t, off):
     return C.c_void_p(t.data_ptr() + 4 * off)
 
