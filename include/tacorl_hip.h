@@ -451,6 +451,27 @@ int tacorl_sample_transitions(const long* possible_steps, long n_possible, const
                               const long* idx, const long* strategy, const long* disp, const double* u_choice,
                               long current_horizon, long n_frames, int B, int A, long* ids, float* action,
                               float* reward, float* done, int* status, tacorl_stream_t stream);
+/* The sampler of RelayImitationLearning's dataset (reference datamodule/dataset/relay_imitation_learning_dataset.py:73-113)
+ * over resident tables, one thread per sample b < B (256 threads per block), with Lw = max_low_level_window and
+ * Hw = max_high_level_window:
+ *   step = episode_lookup[idx[b]], end = ep_end[k] of the last episode with ep_start[k] <= step (binary search),
+ *   sub  = min(end, step + Lw)                      (the subgoal frame, `high_level_action`)
+ *   low  = step + 1 + floor(u_low[b] * (sub - step - 1))   where sub - step - 1 > 0, else sub
+ *   hmax = min(end, step + Hw)
+ *   high = sub + floor(u_high[b] * (hmax - sub))           where hmax - sub > 0, else hmax   (hmax < sub when Hw < Lw)
+ *   with u in [0, 1), the floors kept inside their ranges, and the two minima formed without the overflow of a huge window.
+ *   ids: int64 (4, B) = [step | low | high | sub] - obs, low_level_goal, high_level_goal, high_level_action, the id tables
+ *   of the four image packs (stride 1 at offsets 0, B, 2B, 3B); action[b] = actions[step] (A floats).
+ * The tables are validated by the host (tacorl_amd/data/relay_replay.py RelayIndex) and every id they can produce lies in
+ * [0, n_frames); idx[b] is nevertheless clamped into [0, n_items) before the lookup is read, step and end into the dataset
+ * before they are used, and each id into [0, n_frames) before it is written; *status is set to 1 (it is never cleared here)
+ * when a clamp changed a value.  All pointers are device pointers, 8-byte (int64 / double) or 4-byte (float / int) aligned.
+ * Nothing is allocated; a non-positive B, A, n_items, n_episodes, n_frames or window, or a NULL / misaligned pointer, is
+ * refused with TACORL_EINVAL before anything is launched. */
+int tacorl_sample_relay(const long* episode_lookup, long n_items, const long* ep_start, const long* ep_end, int n_episodes,
+                        const float* actions, long n_frames, const long* idx, const double* u_low, const double* u_high,
+                        long max_low_level_window, long max_high_level_window, int B, int A, long* ids, float* action,
+                        int* status, tacorl_stream_t stream);
 /* The window sampler of the vector-observation dataset (reference datamodule/dataset/d4rl_play_dataset.py:69-146) over
  * resident tables, one 64-lane wavefront per window b < B (four windows per block, grid ceil(B / 4)):
  *   s = episode_lookup[idx[b]], ws = window[b] in [min_window, Tmax];

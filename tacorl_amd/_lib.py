@@ -139,6 +139,7 @@ _SIGS = {
     "tacorl_pack_images_u8_aug_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "tacorl_stage_transition": (_i, [_p, _i, _p, _p, _i, _p, _p, _l, _p]),
     "tacorl_sample_transitions": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "tacorl_sample_relay": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p]),
     "tacorl_sample_d4rl_windows": (_i, [_p, _l, _p, _p, _i, _p, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p,
                                         _p, _p, _p]),
     "tacorl_copy_cols": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),

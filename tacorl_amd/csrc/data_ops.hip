@@ -249,6 +249,55 @@ __global__ __launch_bounds__(256) void sample_transitions_kernel(TransTbl t, int
   if (bad) *t.status = 1;
 }
 
+// Relay sampling (reference datamodule/dataset/relay_imitation_learning_dataset.py:73-113) as index arithmetic: one thread per
+// sample, in the form of sample_transitions_kernel.  Validated on the host (tacorl_amd/data/relay_replay.py RelayIndex); the
+// clamps stand in front of every table access all the same - idx before the lookup read, every id before the action read and
+// the frame gathers behind this kernel - and a clamp that changed a value raises the status word (plain store).
+struct RelayTbl {
+  const long* lookup; long n_items;             // episode_lookup: item -> step
+  const long* ep_start; const long* ep_end; int n_ep;
+  const float* actions; long n_frames;          // (n_frames, A)
+  const long* idx; const double* u_low; const double* u_high;
+  long low_window, high_window;
+  long* ids; float* action; int* status;
+};
+
+__global__ __launch_bounds__(256) void sample_relay_kernel(RelayTbl t, int B, int A) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  bool bad = false;
+  long pos = t.idx[b];
+  if (pos < 0 || pos >= t.n_items) { bad = true; pos = pos < 0 ? 0 : t.n_items - 1; }
+  const long top = t.n_frames - 1;
+  long step = t.lookup[pos];
+  if (step < 0 || step > top) { bad = true; step = step < 0 ? 0 : top; }
+  // episode end: the last episode whose start is <= step (binary search over the sorted starts)
+  int lo = 0, hi = t.n_ep;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (t.ep_start[mid] <= step) lo = mid + 1; else hi = mid;
+  }
+  long end = t.ep_end[lo > 0 ? lo - 1 : 0];
+  if (end < step || end > top) { bad = true; end = end < step ? step : top; }
+  // min(end, step + window) without the overflow of a huge window
+  const long sub = t.low_window >= end - step ? end : step + t.low_window;    // the subgoal frame (high_level_action)
+  const long hmax = t.high_window >= end - step ? end : step + t.high_window;
+  // sample_goal_step(start, stop): uniform over [start, stop) where that is not empty, else stop
+  const long nl = sub - step - 1, nh = hmax - sub;
+  const long low = nl > 0 ? step + 1 + pick_of(t.u_low[b], nl) : sub;
+  const long high = nh > 0 ? sub + pick_of(t.u_high[b], nh) : hmax;
+  const long id[4] = {step, low, high, sub};  // obs | low_level_goal | high_level_goal | high_level_action
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const long c = id[k] < 0 ? 0 : (id[k] > top ? top : id[k]);
+    bad |= c != id[k];
+    t.ids[(long)k * B + b] = c;
+  }
+  const float* __restrict__ a = t.actions + step * A;
+  for (int k = 0; k < A; k++) t.action[(long)b * A + k] = a[k];
+  if (bad) *t.status = 1;
+}
+
 // Window sampling of the vector-observation dataset (reference datamodule/dataset/d4rl_play_dataset.py:69-146) over resident
 // tables: one 64-lane wavefront per window, four windows per block.  The index arithmetic is uniform over the wavefront (the
 // window id is made a scalar, so the table reads are scalar loads); the lanes then copy the window's rows - one contiguous span
@@ -367,6 +416,25 @@ extern "C" int tacorl_sample_transitions(const long* possible_steps, long n_poss
   const TransTbl t{possible_steps, n_possible, ep_start, ep_end, n_episodes, nn_ptr, n_nn, nn_val, actions, idx, strategy,
                    disp, u_choice, current_horizon, n_frames, ids, action, reward, done, status};
   hipLaunchKernelGGL(sample_transitions_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, B, A);
+  return LAUNCH_OK();
+}
+
+extern "C" int tacorl_sample_relay(const long* episode_lookup, long n_items, const long* ep_start, const long* ep_end,
+                                   int n_episodes, const float* actions, long n_frames, const long* idx, const double* u_low,
+                                   const double* u_high, long max_low_level_window, long max_high_level_window, int B, int A,
+                                   long* ids, float* action, int* status, tacorl_stream_t stream) {
+  if (B <= 0 || A <= 0 || n_items <= 0 || n_episodes <= 0 || n_frames <= 0 || max_low_level_window <= 0 ||
+      max_high_level_window <= 0)
+    return TACORL_EINVAL;
+  const void* p8[] = {episode_lookup, ep_start, ep_end, idx, u_low, u_high, ids};
+  const void* p4[] = {actions, action, status};
+  for (const void* p : p8)
+    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
+  for (const void* p : p4)
+    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
+  const RelayTbl t{episode_lookup, n_items, ep_start, ep_end, n_episodes, actions, n_frames, idx, u_low, u_high,
+                   max_low_level_window, max_high_level_window, ids, action, status};
+  hipLaunchKernelGGL(sample_relay_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, B, A);
   return LAUNCH_OK();
 }
 

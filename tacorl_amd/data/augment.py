@@ -58,3 +58,21 @@ def draw_transition_batch_augmentation(specs, B, device, generator=None):
             aug[role][cam] = {"shift": s, "jitter": j}
         aug["pad"][cam] = sp.pad
     return aug
+
+
+RIL_ROLES = ("obs", "low_level_goal", "high_level_goal", "high_level_action")  # the RIL engine's image slots, in order
+
+
+def draw_ril_batch_augmentation(specs, B, device, generator=None):
+    """batch["aug"] for a relay-imitation-learning batch: per camera four independent draws, one per frame of the item - the
+    reference's dataset calls its transform manager once per frame (relay_imitation_learning_dataset.py:85-98,121-127)."""
+    aug = {role: {} for role in RIL_ROLES}
+    aug.update(pad={}, resize={})
+    for cam, sp in specs.items():
+        if sp.resize is not None:
+            aug["resize"][cam] = sp.resize
+        for role in RIL_ROLES:
+            s, j = sp.draw(B, device, generator)
+            aug[role][cam] = {"shift": s, "jitter": j}
+        aug["pad"][cam] = sp.pad
+    return aug

@@ -58,14 +58,16 @@ def window_form(batch, nchw=True):
     return _form(first, nchw, *first.shape[:2], batch["states"], batch.get("aug"))
 
 
-def transition_form(images, nchw=True, aug=None, replay=None):
+def transition_form(images, nchw=True, aug=None, replay=None, rows=3):
     """A transition batch (CQL_Offline, RelayImitationLearning).  images: per camera one of its (B,3,H,W) [nchw] or
     (B,H,W,3) tensors - the first camera's decides the form - or, with `replay` (data/replay.py HbmTransitionReplay
-    .batch(fused=True)), the camera's dataset; the id table is then (3, B): [step | step + 1 | goal]."""
+    .batch(fused=True)), the camera's dataset; the id table is then (3, B): [step | step + 1 | goal] - or, with rows=4
+    (data/relay_replay.py HbmRelayReplay), (4, B): [obs | low_level_goal | high_level_goal | high_level_action]."""
     if replay is not None:
         B, ids = replay["B"], replay["ids"]
-        if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == 3 * B):
-            raise ValueError("transition replay batch: ids must be a contiguous device int64 (3, B) table")
+        if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == rows * B):
+            raise ValueError("transition replay batch: ids must be a contiguous device int64 (3, B) table" if rows == 3 else
+                             f"replay batch: ids must be a contiguous device int64 ({rows}, B) table")
         return _form(None, False, B, None, images, aug, ids)
     first = next(iter(images.values()))
     return _form(first, nchw, first.shape[0], None, images, aug)
@@ -123,6 +125,45 @@ def pack(jobs, form, img_dtype, src_hw, hw, aug_pad=None):
     else:
         for j in jobs:
             call("tacorl_pack_images", j.src, j.pitch, int(form == "f32_nchw"), j.dst, xd, j.n, 3, H, W, ops.stream())
+
+
+def pack_u8_roles(f, cams, X3, slots_of, source_of, img_dtype):
+    """uint8 frames into the image slots of every camera in `cams` by the gathering / augmenting pack, one launch per camera
+    (CQL_Offline: obs / goal / next; RelayImitationLearning: its four roles).  f: the batch form (f.aug None: the plain
+    normalising pack, else f.aug[role][cam] = {"shift", "jitter"} and f.aug["pad"][cam]); slots_of(cam) -> {role: slot of
+    X3[cam]} (slot k = image rows [k*B, (k+1)*B)); source_of(cam, role) -> (source address, bytes per source frame, index
+    address or None): the dataset and a row of an id table, or a gathered (B,H,W,3) tensor."""
+    B, aug = f.B, f.aug
+    for c in cams:
+        slot = B * 3 * f.hw[c][0] * f.hw[c][1] * X3[c].element_size()  # bytes of one role's packed images
+        jobs = []
+        for role, k in slots_of(c).items():
+            src, fb, ip = source_of(c, role)
+            if fb != 3 * f.src_hw[c][0] * f.src_hw[c][1]:
+                raise ValueError(f"uint8 frames: camera {c}'s {role} frames are not of the camera's frame size")
+            t = aug[role][c] if aug is not None else {}
+            jobs.append(PackJob(src, fb, X3[c].data_ptr() + k * slot, B, ip, 1, t.get("shift"), t.get("jitter")))
+        pack(jobs, f.form, img_dtype, f.src_hw[c], f.hw[c], aug["pad"][c] if aug is not None else None)
+
+
+def replay_source(rp, cams, row, what):
+    """source_of for a fused replay batch `rp` ({"frames", "ids", "B"}): role -> row of the (rows, B) id table."""
+    B, ids, frames = rp["B"], rp["ids"], rp["frames"]
+    for c in cams:
+        v = frames.get(c)
+        if v is None or not (v.is_cuda and v.is_contiguous() and v.dtype == torch.uint8 and v.dim() == 4):
+            raise ValueError(f"{what}: camera {c} needs a contiguous device uint8 (N,H,W,3) dataset")
+    return lambda c, role: (frames[c].data_ptr(), frames[c][0].numel(), ids.data_ptr() + 8 * B * row[role])
+
+
+def gathered_source(given, roles):
+    """source_of for gathered uint8 tensors given[role][cam] (B,H,W,3): image i of each tensor; roles: {cam: its roles}."""
+    for c, rs in roles.items():
+        for role in rs:
+            t = given[role][c]
+            if t.dtype != torch.uint8 or not (t.is_cuda and t.is_contiguous()):
+                raise ValueError("batch['aug'] needs the dataset's uint8 frames on the device (the augmentation is part of the uint8 pack)")
+    return lambda c, role: (given[role][c].data_ptr(), given[role][c][0].numel(), None)
 
 
 def pack_window(jobs, T, img_dtype, hw):

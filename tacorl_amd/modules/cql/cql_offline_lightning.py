@@ -204,53 +204,33 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         e.load_transition(action.to(self.dev), reward.to(self.dev), done.to(self.dev))
         e.set_noise(noise)
 
-    def _stage_u8(self, f, jobs_of, action, reward, done, noise):
-        """uint8 frames into the engine's image slots engine.slot[cam] by the gathering / augmenting pack: obs and next for the
-        cameras of obs_modalities only, goal for those of goal_modalities only.  f: the batch form (f.aug None: the plain
-        normalising pack); jobs_of(cam, role) -> (source address, bytes per source frame, index address or None): the dataset
-        and an id table (the fused replay batch), or a gathered (B,H,W,3) tensor."""
-        e, B, aug = self.engine, f.B, f.aug
-        e.ensure_batch(B, f.hw)
-        for c in e.enc_cams:
-            slot = B * 3 * f.hw[c][0] * f.hw[c][1] * e.X3[c].element_size()  # bytes of one role's packed images
-            jobs = []
-            for role, k in e.slot[c].items():  # obs / goal / next, as far as the camera has the role
-                src, fb, ip = jobs_of(c, role)
-                if fb != 3 * f.src_hw[c][0] * f.src_hw[c][1]:
-                    raise ValueError(f"uint8 frames: camera {c}'s {role} frames are not of the camera's frame size")
-                t = aug[role][c] if aug is not None else {}
-                jobs.append(ingest.PackJob(src, fb, e.X3[c].data_ptr() + k * slot, B, ip, 1, t.get("shift"), t.get("jitter")))
-            ingest.pack(jobs, f.form, self.img_dtype, f.src_hw[c], f.hw[c], aug["pad"][c] if aug is not None else None)
+    def _stage_u8(self, f, source_of, action, reward, done, noise):
+        """uint8 frames into the engine's image slots engine.slot[cam] by the gathering / augmenting pack
+        (image_ingest.pack_u8_roles): obs and next for the cameras of obs_modalities only, goal for those of goal_modalities
+        only.  f: the batch form; source_of(cam, role): the dataset and an id table (the fused replay batch), or a gathered
+        (B,H,W,3) tensor."""
+        e = self.engine
+        e.ensure_batch(f.B, f.hw)
+        ingest.pack_u8_roles(f, e.enc_cams, e.X3, lambda c: e.slot[c], source_of, self.img_dtype)
         e.load_transition(action, reward, done)
         e.set_noise(noise)
 
     def _stage_replay(self, batch, action, reward, done, noise):
         """The fused transition-replay batch: every image is read by frame id straight out of the resident dataset."""
-        rp = batch["replay"]
-        B, ids, frames = rp["B"], rp["ids"], rp["frames"]
+        rp, e = batch["replay"], self.engine
         row = {"obs": 0, "next": 1, "goal": 2}  # the id table's rows: [step | step + 1 | goal]
-        e = self.engine
-        for c in e.enc_cams:
-            v = frames.get(c)
-            if v is None or not (v.is_cuda and v.is_contiguous() and v.dtype == torch.uint8 and v.dim() == 4):
-                raise ValueError(f"transition replay batch: camera {c} needs a contiguous device uint8 (N,H,W,3) dataset")
-        f = ingest.transition_form({c: frames[c] for c in e.enc_cams}, aug=batch.get("aug"), replay=rp)
-        self._stage_u8(f, lambda c, role: (frames[c].data_ptr(), frames[c][0].numel(), ids.data_ptr() + 8 * B * row[role]),
-                       action, reward, done, noise)
+        source = ingest.replay_source(rp, e.enc_cams, row, "transition replay batch")
+        f = ingest.transition_form({c: rp["frames"][c] for c in e.enc_cams}, aug=batch.get("aug"), replay=rp)
+        self._stage_u8(f, source, action, reward, done, noise)
 
     def _stage_gathered_aug(self, obs, goal, nxt, aug, action, reward, done, noise):
         """The gathered uint8 batch with augmentation tables: the same pack, reading image i of each tensor."""
         e = self.engine
         given = {"obs": obs, "goal": goal, "next": nxt}
         roles = {c: (["obs", "next"] if c in e.cams else []) + (["goal"] if c in e.goal_cams else []) for c in e.enc_cams}
-        for c in e.enc_cams:
-            for role in roles[c]:
-                t = given[role][c]
-                if t.dtype != torch.uint8 or not (t.is_cuda and t.is_contiguous()):
-                    raise ValueError("batch['aug'] needs the dataset's uint8 frames on the device (the augmentation is part of the uint8 pack)")
+        source = ingest.gathered_source(given, roles)
         f = ingest.transition_form({c: given[roles[c][0]][c] for c in e.enc_cams}, aug=aug)
-        self._stage_u8(f, lambda c, role: (given[role][c].data_ptr(), given[role][c][0].numel(), None),
-                       action.to(self.dev), reward.to(self.dev), done.to(self.dev), noise)
+        self._stage_u8(f, source, action.to(self.dev), reward.to(self.dev), done.to(self.dev), noise)
 
     def compute_update(self, batch, optimize: bool = True, log_type: str = "train", noise=None):
         obs, action, nxt, reward, done = batch

@@ -89,8 +89,30 @@ class RelayImitationLearning(GraphMixin, ModuleMixin, LightningModuleBase):
     # ---------------------------------------------------------------------- stepping
     def _stage(self, batch, nchw=True):
         """The four image roles of every camera of the union and the low-level action; fp32 NCHW tensors, or the
-        dataset's uint8 HWC frames (normalised on the GPU, as CQL_Offline._stage)."""
+        dataset's uint8 HWC frames (normalised on the GPU, as CQL_Offline._stage).  Two more forms come from
+        data/relay_replay.py: `batch["replay"]` (HbmRelayReplay.batch(fused=True): every image is read by frame id straight
+        out of the resident dataset, row k of the (4, B) id table into slot k) and the gathered uint8 batch with
+        `batch["aug"]`; both go through the pack CQL_Offline._stage_u8 uses, one launch of four jobs per camera."""
         e = self.engine
+        rp, aug = batch.get("replay"), batch.get("aug")
+        if rp is not None or aug is not None:
+            slots = {s: k for k, s in enumerate(SLOTS)}
+            if rp is not None:
+                if rp.get("kind") != "relay":
+                    raise ValueError("RelayImitationLearning takes the relay replay (HbmRelayReplay), not kind "
+                                     f"{rp.get('kind')!r}")
+                from ...data.replay import wait_ready
+
+                wait_ready(batch)
+                source = ingest.replay_source(rp, e.cams, slots, "relay replay batch")
+                f = ingest.transition_form({c: rp["frames"][c] for c in e.cams}, aug=aug, replay=rp, rows=len(SLOTS))
+            else:
+                source = ingest.gathered_source(batch, {c: SLOTS for c in e.cams})
+                f = ingest.transition_form({c: batch[SLOTS[0]][c] for c in e.cams}, aug=aug)
+            e.ensure_batch(f.B, f.hw)
+            ingest.pack_u8_roles(f, e.cams, e.X3, lambda c: slots, source, self.img_dtype)
+            e.load_action(batch["low_level_action"].to(self.dev))
+            return
         f = ingest.transition_form({c: batch[SLOTS[0]][c] for c in e.cams}, nchw)
         e.ensure_batch(f.B, f.hw)
         for c in e.cams:

@@ -317,6 +317,25 @@ def sample_transitions(tables, draws, current_horizon, ids, action, reward, done
          int(tables["n_frames"]), B, A, ptr(ids), ptr(action), ptr(reward), ptr(done), ptr(status), stream())
 
 
+def sample_relay(tables, draws, low_window, high_window, ids, action, status):
+    """The relay sampler over resident tables (data/relay_replay.py HbmRelayReplay): tables = device tensors `lookup`,
+    `ep_start`, `ep_end` (int64), `actions` (N, A) f32 and the int `n_frames`; draws = device `idx` (int64), `u_low`,
+    `u_high` (f64), B each.  Writes ids (4, B) int64 [obs | low_level_goal | high_level_goal | high_level_action] and
+    action (B, A) f32, and raises the int32 `status` word on a clamped id."""
+    B, A = ids.shape[1], tables["actions"].shape[1]
+    i64 = [tables[k] for k in ("lookup", "ep_start", "ep_end")] + [draws["idx"]]
+    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64 + [ids])
+    assert all(draws[k].numel() == B for k in ("idx", "u_low", "u_high")) and ids.shape == (4, B)
+    assert all(draws[k].dtype == torch.float64 and draws[k].is_cuda and draws[k].is_contiguous() for k in ("u_low", "u_high"))
+    assert tables["actions"].shape[0] >= tables["n_frames"] and tables["ep_start"].numel() == tables["ep_end"].numel()
+    for t, n in ((_f32(tables["actions"]), None), (_f32(action), B * A)):
+        assert n is None or t.numel() == n
+    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+    call("tacorl_sample_relay", ptr(tables["lookup"]), tables["lookup"].numel(), ptr(tables["ep_start"]), ptr(tables["ep_end"]),
+         tables["ep_start"].numel(), ptr(tables["actions"]), int(tables["n_frames"]), ptr(draws["idx"]), ptr(draws["u_low"]),
+         ptr(draws["u_high"]), int(low_window), int(high_window), B, A, ptr(ids), ptr(action), ptr(status), stream())
+
+
 def sample_d4rl_windows(tables, draws, Tmax, G, min_window, threshold, obs, act, status, goal=None, reached=None, done=None,
                         window_size=None, ids=None):
     """The D4RL window sampler over resident tables (data/d4rl_replay.py HbmD4RLReplay): tables = device tensors `lookup`,
