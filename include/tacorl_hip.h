@@ -777,6 +777,38 @@ int tacorl_cem_refine(int R, int nnet, const float* const* s, const float* const
                       int discrete_gripper, int compute_dtype, float* t_pop, float* t_q, int* t_elite, float* t_mean,
                       float* t_std, void* ws, size_t ws_bytes, tacorl_stream_t stream);
 
+/* ---- neighbour table of the similar_robot_obs goal strategy (knn_ops.hip) ----
+ * The exact brute-force L2 k-NN the reference builds with faiss.IndexFlatL2 (set_nn_steps_from_step,
+ * datamodule/dataset/play_dataset.py:183-234, goal_cond_replay_buffer_dataset.py:76-130), stated so that it can be
+ * reproduced bit for bit:
+ *   points: (n_points, D) fp32 at a row pitch of ld floats (ld >= D: a column slice of a wider table is fine);
+ *   d(q, p) in fp32, sequentially over j = 0 .. D-1: acc = acc + (q_j - p_j) * (q_j - p_j), every subtract, multiply and add
+ *   rounded once (the direct form, no contraction; the expanded |q|^2 + |p|^2 - 2 q.p cancels on near-duplicate frames);
+ *   the neighbours of query row q are the min(k, n_points) rows with the smallest (d, row), ascending - ties go to the lower
+ *   row, the query's own row takes part and a duplicate at a lower row precedes it; absent entries (n_points < k) are row -1
+ *   at distance +inf.
+ * Queries are the rows [q0, q0 + n_queries) of the same table: a slice equals the same rows of the full run.
+ *   nbr_row (n_queries, k) int32, nbr_dist (n_queries, k) fp32 or NULL; every element is written.
+ * One thread per query, tacorl_knn_l2_query_block(k) queries per workgroup; the table streams through LDS in tiles of
+ * tacorl_knn_l2_tile() rows; nothing of size n_points x n_points exists.  Deterministic.
+ * Supported: 1 <= D <= 32, 1 <= k <= 64, n_points <= 2^31 - 1.  Device pointers, 4-byte aligned; nothing is allocated;
+ * a NULL (but for nbr_dist) or misaligned pointer, ld < D, a query range outside the table, k or D out of range or a
+ * non-positive size is refused with TACORL_EINVAL before anything is launched. */
+int tacorl_knn_l2_supported(int D, int k);
+int tacorl_knn_l2_tile(void);
+int tacorl_knn_l2_query_block(int k); /* 0: k not supported */
+int tacorl_knn_l2(const float* points, long n_points, int D, long ld, long q0, long n_queries, int k, int* nbr_row,
+                  float* nbr_dist, tacorl_stream_t stream);
+/* The reference's temporal filter, applied after the top-k as it does: with t = step_of_row[q0 + q] and s = step_of_row[r] for
+ * each neighbour row r of query q in list order (rows outside [0, n_points), the absent entries, are skipped), s is dropped
+ * iff s + margin > t > s - margin, i.e. |t - s| < margin (|t - s| == margin is kept; pure id arithmetic, it crosses episode
+ * boundaries).  nn_steps (n_queries, k) int64: the surviving steps packed left in list order, -1 after; count (n_queries)
+ * int32.  Every element of both is written.  step_of_row: (n_points) int64.  One thread per query.  A NULL or misaligned
+ * pointer (8 bytes for the int64 tables), k outside 1..64, a query range outside the table, a negative margin or a
+ * non-positive size is refused with TACORL_EINVAL before anything is launched. */
+int tacorl_nn_margin_filter(const int* nbr_row, long n_queries, int k, long q0, const long* step_of_row, long n_points,
+                            long margin, long* nn_steps, int* count, tacorl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

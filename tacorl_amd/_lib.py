@@ -167,6 +167,11 @@ _SIGS = {
     "tacorl_cem_ws_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "tacorl_cem_refine": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p,
                                _p, _sz, _p]),
+    "tacorl_knn_l2_supported": (_i, [_i, _i]),
+    "tacorl_knn_l2_tile": (_i, []),
+    "tacorl_knn_l2_query_block": (_i, [_i]),
+    "tacorl_knn_l2": (_i, [_p, _l, _i, _l, _l, _l, _i, _p, _p, _p]),
+    "tacorl_nn_margin_filter": (_i, [_p, _l, _i, _l, _p, _l, _l, _p, _p, _p]),
 }
 
 _lib = None

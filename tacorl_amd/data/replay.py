@@ -19,6 +19,11 @@ from .. import ops
 GEOMETRIC, SIMILAR = 0, 1
 
 
+def _is_table(nn_steps_from_step):
+    """A neighbours.NeighbourTable (the CSR itself) rather than the reference's dict {step: [steps]}."""
+    return hasattr(nn_steps_from_step, "index_csr")
+
+
 class PlayIndex:
     def __init__(self, ep_start_end_ids, min_window_size=16, max_window_size=16, goal_sampling_prob=0.3,
                  goal_strategy_prob=None, goal_augmentation=False, nn_steps_from_step=None, train=True):
@@ -32,15 +37,21 @@ class PlayIndex:
             raise ValueError("Goal strategy probability must sum to 1")  # :93-96
         self.p_strategy = np.array([gs.get("geometric", 0.0), gs.get("similar_robot_obs", 0.0)])
         self.goal_augmentation = bool(goal_augmentation)
-        self.nn = {int(k): np.asarray(v, dtype=np.int64) for k, v in (nn_steps_from_step or {}).items()}
         # the ragged neighbour lists as one CSR table indexed by frame id (a python loop over half the batch was the
         # sampler's hot spot: 180 us per 256-sample batch, a fifth of the device step)
-        top = (max(self.nn) + 1) if self.nn else 0
-        cnt = np.zeros(top, dtype=np.int64)
-        for k, v in self.nn.items():
-            cnt[k] = len(v)
-        self._nn_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-        self._nn_val = (np.concatenate([self.nn[k] for k in sorted(self.nn)]) if self.nn else np.zeros(0, np.int64))
+        self.nn_table = nn_steps_from_step if _is_table(nn_steps_from_step) else None
+        if self.nn_table is not None:
+            # a NeighbourTable (data/neighbours.py) is that CSR already: adopted as it stands, no loop over its keys
+            self.nn = None
+            self._nn_ptr, self._nn_val = self.nn_table.index_csr()
+        else:
+            self.nn = {int(k): np.asarray(v, dtype=np.int64) for k, v in (nn_steps_from_step or {}).items()}
+            top = (max(self.nn) + 1) if self.nn else 0
+            cnt = np.zeros(top, dtype=np.int64)
+            for k, v in self.nn.items():
+                cnt[k] = len(v)
+            self._nn_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+            self._nn_val = (np.concatenate([self.nn[k] for k in sorted(self.nn)]) if self.nn else np.zeros(0, np.int64))
         # load_file_indices (:452-473): every start frame that leaves room for a max-size window
         look = []
         for s, e in self.ep:
@@ -440,16 +451,26 @@ class TransitionIndex:
         self.possible_steps = np.concatenate([np.arange(s, e) for s, e in self.ep])
         if len(self.possible_steps) < 2:
             raise ValueError("fewer than two possible steps: the `random` strategy has nothing to choose from")
-        self.nn = {int(k): np.asarray(v, dtype=np.int64).reshape(-1) for k, v in (nn_steps_from_step or {}).items()}
-        for k, v in self.nn.items():
-            if not 0 <= k < self.n_frames or (len(v) and (v.min() < 0 or v.max() >= self.n_frames)):
-                raise ValueError(f"nn_steps_from_step[{k}]: a step outside [0, {self.n_frames})")
-        top = (max(self.nn) + 1) if self.nn else 0
-        cnt = np.zeros(top, dtype=np.int64)
-        for k, v in self.nn.items():
-            cnt[k] = len(v)
-        self._nn_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-        self._nn_val = np.concatenate([self.nn[k] for k in sorted(self.nn)] + [np.zeros(0, np.int64)]).astype(np.int64)
+        self.nn_table = nn_steps_from_step if _is_table(nn_steps_from_step) else None
+        if self.nn_table is not None:
+            # a NeighbourTable (data/neighbours.py): its CSR is adopted as it stands and validated as arrays
+            self.nn = None
+            self._nn_ptr, self._nn_val = self.nn_table.index_csr()
+            keys = self.nn_table.host()[2]
+            if (len(keys) and (keys.min() < 0 or keys.max() >= self.n_frames)) or \
+                    (len(self._nn_val) and (self._nn_val.min() < 0 or self._nn_val.max() >= self.n_frames)):
+                raise ValueError(f"nn_steps_from_step: a step outside [0, {self.n_frames})")
+        else:
+            self.nn = {int(k): np.asarray(v, dtype=np.int64).reshape(-1) for k, v in (nn_steps_from_step or {}).items()}
+            for k, v in self.nn.items():
+                if not 0 <= k < self.n_frames or (len(v) and (v.min() < 0 or v.max() >= self.n_frames)):
+                    raise ValueError(f"nn_steps_from_step[{k}]: a step outside [0, {self.n_frames})")
+            top = (max(self.nn) + 1) if self.nn else 0
+            cnt = np.zeros(top, dtype=np.int64)
+            for k, v in self.nn.items():
+                cnt[k] = len(v)
+            self._nn_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+            self._nn_val = np.concatenate([self.nn[k] for k in sorted(self.nn)] + [np.zeros(0, np.int64)]).astype(np.int64)
 
     def __len__(self):
         return len(self.possible_steps)
@@ -538,8 +559,14 @@ class HbmTransitionReplay:
         if short or acts.dim() != 2 or acts.shape[0] < index.n_frames:
             raise ValueError(f"frames (uint8 (N,H,W,3)) and actions (N,A) must cover the index's {index.n_frames} frames")
         i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)  # noqa: E731
+        tab = getattr(index, "nn_table", None)
+        if tab is not None and tab.val.numel() and tab.device == torch.empty(0, device=self.dev).device:
+            # a NeighbourTable built on this device: its tensors are the sampler's tables (ptr cut as the index keeps it)
+            nn_ptr, nn_val = tab.ptr[: len(index._nn_ptr)], tab.val
+        else:
+            nn_ptr, nn_val = i64(index._nn_ptr), i64(index._nn_val if len(index._nn_val) else [0])
         self.tables = {"steps": i64(index.possible_steps), "ep_start": i64(index.ep[:, 0]), "ep_end": i64(index.ep[:, 1]),
-                       "nn_ptr": i64(index._nn_ptr), "nn_val": i64(index._nn_val if len(index._nn_val) else [0]),
+                       "nn_ptr": nn_ptr, "nn_val": nn_val,
                        "actions": acts, "n_nn": len(index._nn_ptr) - 1, "n_frames": index.n_frames}
         self.A = int(acts.shape[1])
         self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)

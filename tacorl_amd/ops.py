@@ -361,6 +361,56 @@ def sample_d4rl_windows(tables, draws, Tmax, G, min_window, threshold, obs, act,
          ptr(status), stream())
 
 
+# The blocking of the k-NN search kernel (knn_ops.hip; tacorl_knn_l2_tile / tacorl_knn_l2_query_block answer the same, which
+# tests/test_nn_table_cpu.py checks): database rows per LDS tile, queries per workgroup for k <= 32 and for k <= 64.
+KNN_TILE, KNN_QUERY_BLOCK, KNN_QUERY_BLOCK_K64 = 128, 256, 128
+KNN_MAX_D, KNN_MAX_K = 32, 64
+
+
+def knn_l2_supported(D, k):
+    return bool(L.lib().tacorl_knn_l2_supported(int(D), int(k)))
+
+
+def knn_l2(points, k, q0=0, n_queries=None, nbr_row=None, nbr_dist=None, want_dist=True):
+    """Exact L2 k-NN of the rows [q0, q0 + n_queries) of `points` against all its rows, by the definition of
+    include/tacorl_hip.h tacorl_knn_l2 (fp32 direct form, (distance, row) order).  points: (N, D) fp32 device tensor whose
+    rows are dense (stride(1) == 1; a column slice of a wider table is fine).  Returns nbr_row (n_queries, k) int32 and
+    nbr_dist (n_queries, k) fp32 (None with want_dist=False)."""
+    assert points.dim() == 2 and points.dtype == torch.float32 and points.is_cuda, (points.dtype, points.device, points.dim())
+    N, D = points.shape
+    assert N >= 1 and (N == 1 or points.stride(0) >= D) and (D == 1 or points.stride(1) == 1), (points.shape, points.stride())
+    ld = int(points.stride(0)) if N > 1 else D
+    n_queries = N - q0 if n_queries is None else int(n_queries)
+    if not knn_l2_supported(D, k):
+        raise L.TacorlHipError(f"knn_l2: D = {D} (1..{KNN_MAX_D}) / k = {k} (1..{KNN_MAX_K}) not supported")
+    if nbr_row is None:
+        nbr_row = torch.empty(n_queries, k, dtype=torch.int32, device=points.device)
+    if nbr_dist is None and want_dist:
+        nbr_dist = torch.empty(n_queries, k, dtype=torch.float32, device=points.device)
+    for t, dt in ((nbr_row, torch.int32), (nbr_dist, torch.float32)):
+        assert t is None or (t.dtype == dt and t.is_cuda and t.is_contiguous() and t.numel() == n_queries * k)
+    call("tacorl_knn_l2", ptr(points), N, D, ld, int(q0), n_queries, int(k), ptr(nbr_row), ptr(nbr_dist), stream())
+    return nbr_row, nbr_dist
+
+
+def nn_margin_filter(nbr_row, step_of_row, margin, q0=0, nn_steps=None, count=None):
+    """The reference's temporal filter behind the top-k (tacorl_nn_margin_filter): nbr_row (n_queries, k) int32 rows of the
+    queries [q0, q0 + n_queries), step_of_row (N) int64.  Returns nn_steps (n_queries, k) int64 - the surviving steps packed
+    left in list order, -1 after - and count (n_queries) int32."""
+    assert nbr_row.dim() == 2 and nbr_row.dtype == torch.int32 and nbr_row.is_cuda and nbr_row.is_contiguous()
+    assert step_of_row.dim() == 1 and step_of_row.dtype == torch.int64 and step_of_row.is_cuda and step_of_row.is_contiguous()
+    nq, k = nbr_row.shape
+    if nn_steps is None:
+        nn_steps = torch.empty(nq, k, dtype=torch.int64, device=nbr_row.device)
+    if count is None:
+        count = torch.empty(nq, dtype=torch.int32, device=nbr_row.device)
+    assert nn_steps.dtype == torch.int64 and nn_steps.is_cuda and nn_steps.is_contiguous() and nn_steps.numel() == nq * k
+    assert count.dtype == torch.int32 and count.is_cuda and count.is_contiguous() and count.numel() == nq
+    call("tacorl_nn_margin_filter", ptr(nbr_row), nq, k, int(q0), ptr(step_of_row), step_of_row.numel(), int(margin),
+         ptr(nn_steps), ptr(count), stream())
+    return nn_steps, count
+
+
 def _at(t, off):
     return C.c_void_p(t.data_ptr() + 4 * off)
 
