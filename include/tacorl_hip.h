@@ -281,7 +281,9 @@ int tacorl_mlp_fwd(int nprob, const float* const* x, int ldx, const float* const
 /* The same forward as ONE launch (bf16 MFMA only; <= 8 problems, <= 4 layers, every layer input width a
  * multiple of 8 and all widths <= 256, ldx % 4 == 0 - query with _supported).  params_bf16[p] is a bf16
  * copy of params[p] at the same element offsets (tacorl_to_bf16_batch); the caller refreshes it
- * whenever the fp32 block changes.  Saved activations are identical in layout to tacorl_mlp_fwd's. */
+ * whenever the fp32 block changes.  Saved activations are identical in layout to tacorl_mlp_fwd's.  An unsupported
+ * shape or a misaligned x / params (16 bytes) / params_bf16 (8 bytes) of ANY problem is refused with TACORL_EINVAL before
+ * anything is launched. */
 int tacorl_mlp_fwd_fused_supported(int nprob, int n_layers, const int* dims, int ldx);
 /* lean != 0: hidden-layer outputs whose pre-activation is saved are not written; the fused weight-gradient launch
  * (same flag) recomputes them.  Only where tacorl_mlp_lean_supported() - forward, input-gradient chain and one-launch

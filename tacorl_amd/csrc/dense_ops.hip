@@ -1100,6 +1100,11 @@ static int mlp_fwd_fused_impl(int nprob, const float* const* x, int ldx, const f
                               const void* const* params_bf16, float* const* act, const int* M, int L,
                               const int* dims, const int* acts, int lean, tacorl_stream_t stream, const MlpXGather* gather) {
   if (!mlp_fused_fwd_ok(nprob, L, dims, ldx)) FAIL(TACORL_EINVAL, "mlp_fwd_fused: shapes not supported");
+  // every problem's pointers before ANY launch: the many-row group below leaves first, and a misaligned pointer in the
+  // few-row group behind it would otherwise be refused with the many-row problems' activations already written
+  for (int p = 0; p < nprob; p++)
+    if (!aligned16(params[p]) || ((uintptr_t)params_bf16[p] & 7) || (!gather && !aligned16(x[p])))
+      FAIL(TACORL_EINVAL, "mlp_fwd_fused: problem %d: misaligned pointer", p);
   long wo[MLP_MAXL], bo[MLP_MAXL];
   tacorl_mlp_param_layout(L, dims, wo, bo);
   // Many-row problems of a lean site (>= 16 384 rows: C5's Q networks) take kernels of their own and save, per hidden
