@@ -495,6 +495,36 @@ int tacorl_sample_d4rl_windows(const long* episode_lookup, long n_items, const l
                                int G, int min_window, float threshold, float* obs, float* act, float* goal,
                                float* reached, float* done, long* window_size, long* ids, int* status,
                                tacorl_stream_t stream);
+/* The play-window sampler (reference datamodule/dataset/play_dataset.py:115-169,258-310; PlayIndex.sample + pad_actions of
+ * tacorl_amd/data/replay.py) over resident tables, one 64-lane wavefront per window b < B (four windows per block, grid
+ * ceil(B / 4)):
+ *   s = episode_lookup[idx[b]], ws = window[b] in [min_window, Tmax], end = ep_end[k] of the last episode with
+ *   ep_start[k] <= s (binary search; -1 where s lies in no episode), rs = episode_lookup[min(floor(u_random_state[b] *
+ *   n_items), n_items - 1)] (the random state);
+ *   strategy[b] == 0 (geometric): goal = min(end, s + (ws - 1) * disp[b] + noise_step[b]) decided without forming a product
+ *     that could overflow (a one-frame window has stride 0 and is not divided by), rs where end < 0; noise_step NULL: 0;
+ *   strategy[b] == 1 (similar_robot_obs): with key = s + ws - 1 and cnt = nn_ptr[key + 1] - nn_ptr[key] (0 where key lies
+ *     outside [0, n_nn)): goal = nn_val[nn_ptr[key] + min(floor(u_choice[b] * cnt), cnt - 1)] where cnt > 0, else rs;
+ *   goal is then clipped into [0, last_end] (last_end = max(ep_end); part of the definition, it raises no status); the
+ *   products u * n are formed in double and truncated, as NumPy does.
+ *   ids: int64 (B * Tmax + B) = the window's frame ids s + min(t, ws - 1), row-major (b, t), then the B goal ids (the id table
+ *   of the window / goal image packs); act (B, Tmax, A) = actions[s : s + ws], then rows that are zero except the last column
+ *   (the gripper action), which repeats the last real step's; disp_out (B) = disp[b] for a geometric goal, else -1;
+ *   window_size (B) = ws.
+ * The tables are validated by the host (tacorl_amd/data/play_replay.py validate_play_tables) and every id they can produce
+ * lies in [0, n_frames); idx, window, strategy (into [0, 1]), disp (>= 1), noise_step (into [-1, 1]), s, rs, the position
+ * read in nn_val and the goal are nevertheless clamped into range before any table access or store, and *status is set to 1
+ * (it is never cleared here) when such a clamp changed a value or an nn_val entry lay outside [0, n_frames).  All pointers are
+ * device pointers, 8-byte (int64 / double) or 4-byte (float / int) aligned; nn_ptr / nn_val may be NULL when n_nn == 0,
+ * noise_step may be NULL (no goal augmentation).  Nothing is allocated; a non-positive B, Tmax, A, n_items, n_episodes or
+ * n_frames, n_nn < 0, min_window outside [1, Tmax], n_frames < Tmax, last_end outside [0, n_frames) or a NULL required /
+ * misaligned pointer is refused with TACORL_EINVAL before anything is launched. */
+int tacorl_sample_play_windows(const long* episode_lookup, long n_items, const long* ep_start, const long* ep_end,
+                               int n_episodes, const long* nn_ptr, long n_nn, const long* nn_val, const float* actions,
+                               long n_frames, long last_end, const long* idx, const long* window, const long* strategy,
+                               const long* disp, const long* noise_step, const double* u_choice,
+                               const double* u_random_state, int B, int Tmax, int A, int min_window, long* ids, float* act,
+                               long* disp_out, long* window_size, int* status, tacorl_stream_t stream);
 /* dst[r][0:cols] (+)= src[r % src_row_mod][0:cols]  (src_row_mod <= 0: r).  expand_obs on
  * embeddings instead of images (reference utils/misc.py:132-153) and torch.cat plumbing. */
 int tacorl_copy_cols(const float* src, int ld_src, float* dst, int ld_dst, int rows, int cols,

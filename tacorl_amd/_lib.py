@@ -142,6 +142,8 @@ _SIGS = {
     "tacorl_sample_relay": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p]),
     "tacorl_sample_d4rl_windows": (_i, [_p, _l, _p, _p, _i, _p, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p,
                                         _p, _p, _p]),
+    "tacorl_sample_play_windows": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i,
+                                        _p, _p, _p, _p, _p, _p]),
     "tacorl_copy_cols": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p]),
     "tacorl_copy_cols_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "tacorl_vec_rows_max_blocks": (_i, []),

@@ -372,7 +372,127 @@ __global__ __launch_bounds__(256) void sample_d4rl_windows_kernel(D4rlTbl t, int
   if (bad) *t.status = 1;
 }
 
+// Play-window sampling (reference datamodule/dataset/play_dataset.py:115-169,258-310; tacorl_amd/data/replay.py
+// PlayIndex.sample + pad_actions) over resident tables, in the form of sample_d4rl_windows_kernel: one 64-lane wavefront per
+// window, four windows per block, the index arithmetic uniform over the wavefront (scalar table reads).  The lanes then write
+// the window's Tmax frame ids and copy its action rows - one contiguous span of ws * A floats in the table and in the batch -
+// as coalesced dwords, and write the padding rows (zero, the gripper column repeated).  Validated on the host
+// (tacorl_amd/data/play_replay.py validate_play_tables); the clamps stand in front of every table access all the same, and a
+// clamp that changed a value raises the status word (plain store: every writer stores 1).
+struct PlayTbl {
+  const long* lookup; long n_items;             // episode_lookup: item -> first frame of its window
+  const long* ep_start; const long* ep_end; int n_ep;
+  const long* nn_ptr; long n_nn; const long* nn_val;  // CSR neighbour lists of frames [0, n_nn)
+  const float* actions; long n_frames, last_end;      // (n_frames, A); the goal's clip bound max(ep_end)
+  const long* idx; const long* window; const long* strategy; const long* disp; const long* noise;
+  const double* u_choice; const double* u_random;
+  long* ids; float* act; long* disp_out; long* window_size; int* status;
+};
+
+__global__ __launch_bounds__(256) void sample_play_windows_kernel(PlayTbl t, int B, int Tmax, int A, int min_window) {
+  const int b = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int lane = threadIdx.x & 63;
+  if (b >= B) return;
+  bool bad = false;
+  const long top = t.n_frames - 1;
+  long pos = t.idx[b];
+  if (pos < 0 || pos >= t.n_items) { bad = true; pos = pos < 0 ? 0 : t.n_items - 1; }
+  long wl = t.window[b];
+  if (wl < min_window || wl > Tmax) { bad = true; wl = wl < min_window ? min_window : Tmax; }
+  const int ws = (int)wl;
+  long s = t.lookup[pos];
+  if (s < 0 || s > t.n_frames - ws) { bad = true; s = s < 0 ? 0 : t.n_frames - ws; }  // frames s .. s + ws - 1 exist
+  long strat = t.strategy[b];
+  if (strat < 0 || strat > 1) { bad = true; strat = strat < 0 ? 0 : 1; }
+  long d = t.disp[b];
+  if (d < 1) { bad = true; d = 1; }
+  // the random state (play_dataset.py:262-264): another item's first frame
+  long rs = t.lookup[pick_of(t.u_random[b], t.n_items)];
+  if (rs < 0 || rs > top) { bad = true; rs = rs < 0 ? 0 : top; }
+  long goal;
+  if (strat == 0) {
+    // find_episode_end: the last episode whose start is <= s (binary search over the sorted starts), -1 where s lies in none
+    int lo = 0, hi = t.n_ep;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (t.ep_start[mid] <= s) lo = mid + 1; else hi = mid;
+    }
+    const long end = lo > 0 ? t.ep_end[lo - 1] : -1;
+    if (end < s) {
+      goal = rs;
+    } else {
+      long nz = t.noise ? t.noise[b] : 0;
+      if (nz < -1 || nz > 1) { bad = true; nz = nz < 0 ? -1 : 1; }
+      // min(end, s + (ws - 1) * disp + noise) without the overflow of a huge draw: the product is formed only where the sum
+      // stays <= end, i.e. (ws - 1) * disp <= lim; a one-frame window has stride 0 and is not divided by
+      const long stride = ws - 1, lim = end - s - nz;
+      if (lim < 0) goal = end;
+      else if (stride == 0) goal = s + nz;
+      else goal = d > lim / stride ? end : s + stride * d + nz;
+    }
+  } else {
+    const long key = s + ws - 1;
+    long first = 0, cnt = 0, total = 0;
+    if (t.n_nn > 0) total = t.nn_ptr[t.n_nn];
+    if (key >= 0 && key < t.n_nn) { first = t.nn_ptr[key]; cnt = t.nn_ptr[key + 1] - first; }
+    if (cnt > 0 && total > 0) {
+      long at = first + pick_of(t.u_choice[b], cnt);
+      if (at < 0 || at > total - 1) { bad = true; at = at < 0 ? 0 : total - 1; }
+      goal = t.nn_val[at];
+      if (goal < 0 || goal > top) bad = true;  // (the clip below brings it inside)
+    } else {
+      goal = rs;  // no neighbour recorded: the reference's fallback
+    }
+  }
+  // the definition's own clip of the goal (PlayIndex.sample): no status
+  goal = goal < 0 ? 0 : (goal > t.last_end ? t.last_end : goal);
+  if (goal > top) { bad = true; goal = top; }
+  {
+    long* __restrict__ dst = t.ids + (long)b * Tmax;
+    for (int i = lane; i < Tmax; i += 64) dst[i] = s + (i < ws ? i : ws - 1);  // pad by repetition of the last frame
+  }
+  {
+    const float* __restrict__ src = t.actions + s * A;
+    float* __restrict__ dst = t.act + (long)b * Tmax * A;
+    const int n = ws * A, pad = (Tmax - ws) * A;
+    const float grip = src[n - 1];  // the last real step's gripper action
+    for (int i = lane; i < n; i += 64) dst[i] = src[i];
+    for (int i = lane; i < pad; i += 64) dst[n + i] = (i % A == A - 1) ? grip : 0.f;
+  }
+  if (lane != 0) return;
+  t.ids[(long)B * Tmax + b] = goal;
+  t.disp_out[b] = strat == 0 ? d : -1;
+  t.window_size[b] = ws;
+  if (bad) *t.status = 1;
+}
+
 }  // namespace
+
+extern "C" int tacorl_sample_play_windows(const long* episode_lookup, long n_items, const long* ep_start, const long* ep_end,
+                                          int n_episodes, const long* nn_ptr, long n_nn, const long* nn_val,
+                                          const float* actions, long n_frames, long last_end, const long* idx,
+                                          const long* window, const long* strategy, const long* disp, const long* noise_step,
+                                          const double* u_choice, const double* u_random_state, int B, int Tmax, int A,
+                                          int min_window, long* ids, float* act, long* disp_out, long* window_size,
+                                          int* status, tacorl_stream_t stream) {
+  if (B <= 0 || Tmax <= 0 || A <= 0 || n_items <= 0 || n_episodes <= 0 || n_frames <= 0 || n_nn < 0) return TACORL_EINVAL;
+  if (min_window < 1 || min_window > Tmax || n_frames < Tmax || last_end < 0 || last_end >= n_frames) return TACORL_EINVAL;
+  if ((long)Tmax * A > 0x7fffffffL || (long)B + 3 > 0x7fffffffL) return TACORL_EINVAL;
+  const void* p8[] = {episode_lookup, ep_start, ep_end, idx, window, strategy, disp, u_choice, u_random_state, ids, disp_out,
+                      window_size};
+  const void* p4[] = {actions, act, status};
+  for (const void* p : p8)
+    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
+  for (const void* p : p4)
+    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
+  if ((uintptr_t)noise_step & 7) return TACORL_EINVAL;
+  if (n_nn > 0 && (!nn_ptr || !nn_val || ((uintptr_t)nn_ptr & 7) || ((uintptr_t)nn_val & 7))) return TACORL_EINVAL;
+  const PlayTbl t{episode_lookup, n_items, ep_start, ep_end, n_episodes, nn_ptr, n_nn, nn_val, actions, n_frames, last_end,
+                  idx, window, strategy, disp, noise_step, u_choice, u_random_state, ids, act, disp_out, window_size, status};
+  hipLaunchKernelGGL(sample_play_windows_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, t, B, Tmax, A,
+                     min_window);
+  return LAUNCH_OK();
+}
 
 extern "C" int tacorl_sample_d4rl_windows(const long* episode_lookup, long n_items, const long* ep_start, const long* ep_end,
                                           int n_episodes, const float* observations, const float* actions, long n_frames,

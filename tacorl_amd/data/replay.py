@@ -71,6 +71,38 @@ class PlayIndex:
                 "disp": rng.geometric(self.p_geom_goal, size=n), "noise_step": rng.integers(0, 3, size=n) - 1,
                 "u_choice": rng.random(n), "u_random_state": rng.random(n)}
 
+    def device_constants(self, n, device):
+        """What is no draw, one tensor per (device, n), shared by the batches and written by nobody: the window of an index
+        with min == max, and the zero noise step of one without goal augmentation."""
+        dev = torch.device(device)
+        const = self.__dict__.setdefault("_dev_constants", {})
+        if (dev, n) not in const:
+            const[dev, n] = (torch.full((n,), self.max_ws, device=dev, dtype=torch.int64), torch.zeros(n, device=dev, dtype=torch.int64))
+        return const[dev, n]
+
+    def draw_device(self, n, device, generator=None):
+        """`draw` made by torch on the device (nothing crosses PCIe), plus the items themselves: int64 idx / window_size /
+        strategy / disp / noise_step, float64 u_choice / u_random_state - what `tacorl_sample_play_windows` reads
+        (data/play_replay.py HbmPlayReplay).  Items are drawn with replacement, as the sibling indices draw theirs
+        (TransitionIndex, RelayIndex, D4RLWindowIndex); the reference's DataLoader(shuffle=True) draws WITHOUT replacement -
+        every item once per epoch, in a random order.  The window when min == max and the noise step without goal
+        augmentation are `device_constants`, not draws.  Every launch here stands on the trainer's stream in front of the
+        step, so each quantity is one generator kernel writing its final dtype (no compare, no cast), and the two uniforms
+        are the rows of one (2, n) draw: four launches for a constant window without goal augmentation."""
+        dev, g = torch.device(device), generator
+        win, noise = self.device_constants(n, dev)
+        i64 = lambda: torch.empty(n, device=dev, dtype=torch.int64)  # noqa: E731
+        idx = torch.randint(0, len(self), (n,), device=dev, generator=g, dtype=torch.int64)
+        if self.min_ws < self.max_ws:
+            win = torch.randint(self.min_ws, self.max_ws + 1, (n,), device=dev, generator=g, dtype=torch.int64)
+        strategy = i64().bernoulli_(1.0 - float(self.p_strategy[0]), generator=g)  # 1 = similar_robot_obs
+        disp = i64().geometric_(self.p_geom_goal, generator=g)
+        if self.goal_augmentation:
+            noise = torch.randint(-1, 2, (n,), device=dev, generator=g, dtype=torch.int64)
+        u = torch.rand(2, n, device=dev, generator=g, dtype=torch.float64)
+        return {"idx": idx, "window_size": win, "strategy": strategy, "disp": disp, "noise_step": noise,
+                "u_choice": u[0], "u_random_state": u[1]}
+
     def episode_end(self, step):
         """find_episode_end (:238-242): end (inclusive) of the first episode with start <= step <= end, -1 if none."""
         step = np.asarray(step)

@@ -361,6 +361,33 @@ def sample_d4rl_windows(tables, draws, Tmax, G, min_window, threshold, obs, act,
          ptr(status), stream())
 
 
+def sample_play_windows(tables, draws, Tmax, min_window, ids, act, disp_out, window_size, status, goal_augmentation=False):
+    """The play-window sampler over resident tables (data/play_replay.py HbmPlayReplay): tables = device tensors `lookup`,
+    `ep_start`, `ep_end`, `nn_ptr`, `nn_val` (int64), `actions` (N, A) f32 and the ints `n_nn`, `n_frames`, `last_end`;
+    draws = device `idx`, `window_size`, `strategy`, `disp`, `noise_step` (int64; read with goal_augmentation only) and
+    `u_choice`, `u_random_state` (f64), B each.  Writes ids (B * Tmax + B) int64 = [window frames (b, t) | goal], act
+    (B, Tmax, A) f32, disp_out (B) and window_size (B) int64; raises the int32 `status` word on a clamp."""
+    B, A = draws["idx"].numel(), tables["actions"].shape[1]
+    ints = ("idx", "window_size", "strategy", "disp") + (("noise_step",) if goal_augmentation else ())
+    i64 = [tables[k] for k in ("lookup", "ep_start", "ep_end", "nn_ptr", "nn_val")] + [draws[k] for k in ints]
+    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64 + [ids, disp_out, window_size])
+    assert all(draws[k].numel() == B for k in ints + ("u_choice", "u_random_state"))
+    assert all(draws[k].dtype == torch.float64 and draws[k].is_cuda and draws[k].is_contiguous() for k in ("u_choice", "u_random_state"))
+    assert ids.numel() == B * Tmax + B and disp_out.numel() == B and window_size.numel() == B
+    assert tables["nn_ptr"].numel() == tables["n_nn"] + 1 and tables["actions"].shape[0] >= tables["n_frames"]
+    assert tables["ep_start"].numel() == tables["ep_end"].numel()
+    _f32(tables["actions"])
+    assert _f32(act).numel() == B * Tmax * A
+    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+    n_nn = int(tables["n_nn"])
+    call("tacorl_sample_play_windows", ptr(tables["lookup"]), tables["lookup"].numel(), ptr(tables["ep_start"]),
+         ptr(tables["ep_end"]), tables["ep_start"].numel(), ptr(tables["nn_ptr"]) if n_nn else None, n_nn,
+         ptr(tables["nn_val"]) if n_nn else None, ptr(tables["actions"]), int(tables["n_frames"]), int(tables["last_end"]),
+         ptr(draws["idx"]), ptr(draws["window_size"]), ptr(draws["strategy"]), ptr(draws["disp"]),
+         ptr(draws["noise_step"]) if goal_augmentation else None, ptr(draws["u_choice"]), ptr(draws["u_random_state"]), B,
+         int(Tmax), A, int(min_window), ptr(ids), ptr(act), ptr(disp_out), ptr(window_size), ptr(status), stream())
+
+
 # The blocking of the k-NN search kernel (knn_ops.hip; tacorl_knn_l2_tile / tacorl_knn_l2_query_block answer the same, which
 # tests/test_nn_table_cpu.py checks): database rows per LDS tile, queries per workgroup for k <= 32 and for k <= 64.
 KNN_TILE, KNN_QUERY_BLOCK, KNN_QUERY_BLOCK_K64 = 128, 256, 128
