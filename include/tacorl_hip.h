@@ -841,6 +841,25 @@ int tacorl_knn_l2(const float* points, long n_points, int D, long ld, long q0, l
 int tacorl_nn_margin_filter(const int* nbr_row, long n_queries, int k, long q0, const long* step_of_row, long n_points,
                             long margin, long* nn_steps, int* count, tacorl_stream_t stream);
 
+/* ---- rollout (rollout_ops.hip) ------------------------------------------------------ */
+/* A linear layer with two inputs for a handful of rows, read from torch's row-major (N, K) fp32 masters as they lie:
+ *   y[r][n] = act(b1[n] + b2[n] + sum_k w1[n][k] x1[r][k] + sum_k w2[n][k] x2[r][k]),   r < R, n < N.
+ * One call is a ReLU-RNN cell of the action decoder's one-step rollout (reference action_decoder_logistic.py:87-97 through
+ * nn.RNN: x1 the layer's input, x2 = h_{t-1}, act = RELU); with x2 == NULL (w2 and the flags are then ignored, b2 may still
+ * be given) it is a head projection.  Where x2_row_is_zero[r] != 0 (R bytes, or NULL) row r of x2 counts as zeros and is
+ * NOT READ: a plan that starts at this step has h_0 = 0 whatever the buffer holds (NaN included).
+ * fp32 FMA throughout; a batched GEMV (one wave per neuron, tacorl_rows_linear2_group() rows of [x1 | x2] staged in LDS per
+ * workgroup), each weight read once per row group.  Row determinism: y[r][n] depends on row r's inputs, its flag, n, K1, K2
+ * and the weight pointers only - it is bit-identical whatever R is and wherever the row sits.
+ * Shapes: 1 <= R <= 64, K1 >= 1, K2 >= 0, N >= 1 (each at most 2^24); K1, K2 and the leading dimensions need no alignment
+ * beyond that of a float.  Shapes outside these, a NULL x1 / w1 / b1 / y (or w2 with x2 given and K2 > 0), ldx < K, ldy < N, a
+ * misaligned pointer or y overlapping x1 or x2 is refused with TACORL_EINVAL before anything is launched. */
+int tacorl_rows_linear2_supported(int R, int K1, int K2, int N);
+int tacorl_rows_linear2_group(void);
+int tacorl_rows_linear2_fwd(const float* x1, int ldx1, int K1, const float* w1, const float* b1, const float* x2, int ldx2,
+                            int K2, const float* w2, const float* b2, const unsigned char* x2_row_is_zero, float* y, int ldy,
+                            int R, int N, int act, tacorl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,9 @@ _SIGS = {
     "tacorl_knn_l2_query_block": (_i, [_i]),
     "tacorl_knn_l2": (_i, [_p, _l, _i, _l, _l, _l, _i, _p, _p, _p]),
     "tacorl_nn_margin_filter": (_i, [_p, _l, _i, _l, _p, _l, _l, _p, _p, _p]),
+    "tacorl_rows_linear2_supported": (_i, [_i, _i, _i, _i]),
+    "tacorl_rows_linear2_group": (_i, []),
+    "tacorl_rows_linear2_fwd": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

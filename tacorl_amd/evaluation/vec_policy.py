@@ -1,0 +1,240 @@
+"""Latent-plan policies rolled out for many environments in one step - the inner loop of the reference's rollout managers
+(evaluation/rollout_manager.py:232-283 LatentPlanRollout, :361-407 TACORL; rollout_manager_d4rl.py:137-157, :206-241) for R
+environments whose episodes end and whose plans renew at different steps:
+
+    policy = LatentPlanPolicy(module, n_envs=R, plan_duration=16)
+    policy.reset()                                   # every row re-plans on its next step
+    actions = policy.step(observation, goal)         # (R, A) fp32 on the device
+    infos = rollout_episodes(policy, envs)           # one episode per environment, all at once
+
+A row re-plans on its first step after `reset` and every `plan_duration` steps after that; re-planning restarts that row's
+decoder state (the reference's `clear_hidden_state()`).  The clock is plain host integers, so nothing is read back from
+the device to decide anything.  The plan comes from `actor.get_actions(deterministic=True)` where the module has an actor
+(TACORL; refined by CEMOptimizer with use_cem), from `plan_proposal.get_dist(...).sample()` otherwise (PlayLMP); only the
+rows that re-plan go through it.  The decoder step is ActionDecoderLogistic.step_rows: per-row hidden state, one
+tacorl_rows_linear2_fwd per layer up to 16 rows, and above that - where the training GEMMs are the faster ones
+(profiles/vec_rollout.md) - the kernels `act` is made of, the restarted rows zeroed first.  Nothing is captured in a hipGraph.
+
+`latent_plan_policy_restatement` states the same schedule in plain torch ops over callables, for any device and dtype:
+the yardstick of tests/test_vec_policy_cpu.py (as modules/cem.py's cem_restatement is for the CEM kernel).
+"""
+import numpy as np
+import torch
+
+
+class PlanClock:
+    """The per-row schedule in host integers: steps since the row's plan was made (None: re-plan on the next step)."""
+
+    def __init__(self, n_rows, plan_duration):
+        if n_rows < 1 or plan_duration < 1:
+            raise ValueError(f"n_rows {n_rows}, plan_duration {plan_duration}")
+        self.n, self.duration = int(n_rows), int(plan_duration)
+        self.age = [None] * self.n
+
+    def reset(self, rows=None):
+        for r in _row_list(rows, self.n):
+            self.age[r] = None
+
+    def due(self):
+        """Rows that re-plan (and restart their decoder state) on this step."""
+        return [r for r in range(self.n) if self.age[r] is None or self.age[r] >= self.duration]
+
+    def tick(self, replanned):
+        for r in range(self.n):
+            self.age[r] = 1 if r in replanned else self.age[r] + 1
+
+
+def _row_list(rows, n):
+    if rows is None:
+        return list(range(n))
+    if isinstance(rows, torch.Tensor):
+        rows = rows.cpu().tolist()
+    rows = list(rows)
+    if len(rows) == n and all(isinstance(v, (bool, np.bool_)) for v in rows):
+        return [r for r in range(n) if rows[r]]
+    out = [int(r) for r in rows]
+    if any(r < 0 or r >= n for r in out):
+        raise IndexError(f"rows {out} of {n}")
+    return out
+
+
+def _take(x, idx):
+    """Rows idx (a device index tensor) of a tensor or of a {camera: tensor} dict."""
+    if isinstance(x, dict):
+        return {k: _take(v, idx) for k, v in x.items()}
+    return x.index_select(0, idx)
+
+
+class LatentPlanPolicy:
+    def __init__(self, module, n_envs, plan_duration=16, use_cem=False, cem_kwargs=None):
+        self.module, self.R = module, int(n_envs)
+        self.ad = getattr(module, "ad", None)
+        if self.ad is None:
+            raise ValueError("the module has no action decoder")
+        self.dev = module.dev
+        self.clock = PlanClock(n_envs, plan_duration)
+        self.plan_duration = int(plan_duration)
+        self.image = bool(getattr(module, "action_decoder_modalities", None))
+        actor = getattr(module, "actor", None)
+        self.actor = actor if getattr(actor, "get_actions", None) is not None else None
+        if self.actor is None and getattr(getattr(module, "plan_proposal", None), "get_dist", None) is None:
+            raise ValueError("the module has neither actor.get_actions nor plan_proposal.get_dist")
+        self.cem = None
+        if use_cem:
+            if self.actor is None:
+                raise ValueError("use_cem needs a module with an actor and critics (TACORL)")
+            from ..modules.cem import CEMOptimizer
+
+            self.cem = CEMOptimizer(q1=module.q1, q2=module.q2, action_dim=self.actor.action_dim, discrete_gripper=False,
+                                    **(cem_kwargs or {}))
+        self.state = self.ad.new_rows_state(self.R)
+        self.plan = torch.zeros(self.R, self.ad.P, device=self.dev)
+
+    def reset(self, rows=None):
+        """All rows, or an index list / bool mask: those rows re-plan (and start from h_0 = 0) on their next step."""
+        self.clock.reset(rows)
+
+    @property
+    def hidden(self):
+        return self.state.hidden
+
+    # ------------------------------------------------------------------ plan source
+    def _source(self, observation, goal, idx, eps):
+        """The plan of rows idx: (len(idx), P)."""
+        m = self.module
+        obs, g = _take(observation, idx), _take(goal, idx)
+        if self.actor is not None:
+            o = {"observation": obs, "goal": g} if self.image else torch.cat([obs, g], dim=-1)
+            plan, _ = self.actor.get_actions(o, deterministic=True, reparameterize=False)
+            if self.cem is not None:
+                plan = self.cem.get_action(obs=o, initial_mean=plan)
+            return plan
+        if self.image:
+            pe = m.perceptual_encoder
+            state = pe.get_state_from_observation(observation=obs, modalities=m.plan_proposal_obs_modalities)
+            pp_goal = m.goal_encoder(pe.get_state_from_observation(observation=g, modalities=m.plan_proposal_goal_modalities))
+        else:
+            state, pp_goal = obs, g
+        return m.plan_proposal.get_dist(state_emb=state, goal_emb=pp_goal).sample(noise=eps)
+
+    def step(self, observation, goal, noise=None, plans=None):
+        """observation / goal: {camera: (R,3,H,W)} fp32 dicts (image modules) or (R,S) / (R,G) tensors (D4RL).  noise: any
+        subset of {"plan_eps": (R,P), "rand_a": (R,Da,K), "rand_b": (R,Da)}; the rest is drawn on the device.  plans: (R,P)
+        with NaN rows meaning "not given" - overrides the plan source for the rows that re-plan (an external planner).
+        Returns the (R, A) actions: a view that stays valid until the next step."""
+        R, dev, noise = self.R, self.dev, noise or {}
+        to = lambda x: ({k: to(v) for k, v in x.items()} if isinstance(x, dict) else torch.as_tensor(x).to(dev, torch.float32))  # noqa: E731
+        observation, goal = to(observation), to(goal)
+        due = self.clock.due()
+        if due:
+            need = due
+            if plans is not None and not plans.is_cuda:  # a host tensor: which rows it gives is known without a device read
+                given = (~torch.isnan(plans.reshape(R, -1)).any(dim=1)).tolist()
+                need = [r for r in due if not given[r]]
+            idx = torch.tensor(due, dtype=torch.long, device=dev)
+            new = None
+            if need:
+                nidx = idx if need == due else torch.tensor(need, dtype=torch.long, device=dev)
+                eps = noise.get("plan_eps")
+                eps = None if eps is None else eps.to(dev, torch.float32).reshape(R, -1).index_select(0, nidx)
+                src = self._source(observation, goal, nidx, eps).to(torch.float32).reshape(len(need), -1)
+                new = src if need == due else torch.zeros(R, self.ad.P, device=dev).index_copy_(0, nidx, src).index_select(0, idx)
+            if plans is not None:
+                given_rows = plans.to(dev, torch.float32).reshape(R, -1).index_select(0, idx)
+                if new is None:
+                    new = given_rows
+                else:
+                    new = torch.where(torch.isnan(given_rows).any(dim=1, keepdim=True), new, given_rows)
+            self.plan.index_copy_(0, idx, new)
+        if self.image:
+            emb = self.module.perceptual_encoder.get_state_from_observation(
+                observation=observation, modalities=self.module.action_decoder_modalities)
+        else:
+            emb = observation
+        restart = [False] * R
+        for r in due:
+            restart[r] = True
+        draws = None
+        if "rand_a" in noise or "rand_b" in noise:
+            ra, rb = noise.get("rand_a"), noise.get("rand_b")
+            draws = (ra if ra is not None else torch.rand(R, self.ad.Da, self.ad.K, device=dev),
+                     rb if rb is not None else torch.rand(R, self.ad.Da, device=dev))
+        out = self.ad.step_rows(self.state, self.plan, emb.contiguous(), restart, noise=draws)
+        self.clock.tick(set(due))
+        return out
+
+
+def default_batch_obs(raw, envs):
+    """Vector environments (rollout_manager_d4rl.py:126-135): the stacked observations and each environment's goal -
+    `target_goal`, or `goal_locations[0]`."""
+    goals = [env.target_goal if hasattr(env, "target_goal") else env.goal_locations[0] for env in envs]
+    return (torch.as_tensor(np.stack([np.asarray(o, dtype=np.float32) for o in raw])),
+            torch.as_tensor(np.stack([np.asarray(g, dtype=np.float32) for g in goals])))
+
+
+def rollout_episodes(policy, envs, max_steps=None, batch_obs=None, noise=None):
+    """One episode per environment, all at once: envs is a list of policy.R gym-API objects (`reset()`, `step(a)` ->
+    (obs, reward, done, info), `_max_episode_steps`).  One `.cpu()` of the (R, A) actions per step; finished rows idle (their
+    last observation is fed again, their actions are dropped).  batch_obs(list of raw observations, envs) -> (observation,
+    goal) for policy.step; noise: None or a callable step -> the step's noise dict.  Returns the reference's rollout_info
+    dicts (`episode_length`, `episode_return`, `success`), one per environment."""
+    R = len(envs)
+    if R != policy.R:
+        raise ValueError(f"{R} environments for a policy of {policy.R} rows")
+    batch_obs = batch_obs or default_batch_obs
+    raw = [env.reset() for env in envs]
+    policy.reset()
+    limit = [env._max_episode_steps if max_steps is None else min(max_steps, env._max_episode_steps) for env in envs]
+    steps, returns, info = [0] * R, [0] * R, [{} for _ in range(R)]
+    live = [limit[r] > 0 for r in range(R)]
+    t = 0
+    while any(live):
+        observation, goal = batch_obs(raw, envs)
+        actions = policy.step(observation, goal, noise=noise(t) if noise is not None else None).cpu().numpy()
+        for r in range(R):
+            if not live[r]:
+                continue
+            raw[r], reward, done, info[r] = envs[r].step(actions[r])
+            returns[r] += reward
+            steps[r] += 1
+            live[r] = not (done or steps[r] >= limit[r])
+        t += 1
+    return [{"episode_length": steps[r], "episode_return": returns[r],
+             "success": ("success" in info[r]) and info[r]["success"]} for r in range(R)]
+
+
+def latent_plan_policy_restatement(plan_fn, decoder_fn, observations, goals, n_envs, plan_duration, hidden0, resets=None,
+                                   plans=None):
+    """LatentPlanPolicy's schedule in plain torch ops, over callables standing in for the networks (any device, any dtype).
+      plan_fn(observation rows, goal rows, rows (list), t) -> (len(rows), P): the plan source, called with the rows that
+        re-plan at step t only;
+      decoder_fn(plan (R,P), observation (R,..), hidden, t) -> (actions (R,A), new hidden): one decoder step, `hidden` with
+        the row dimension at index -2 (nn.RNN's (L, R, H));
+      observations[t], goals[t]: the step's inputs; hidden0: zeros of the hidden state's shape;
+      resets: {t: rows} - `reset(rows)` called BEFORE step t (t = 0 resets every row anyway);
+      plans: {t: (R,P)} with NaN rows meaning "not given".
+    Returns dict(actions [T x (R,A)], replanned [T x list of rows], plan [T x (R,P)], hidden (after the last step))."""
+    clock = PlanClock(n_envs, plan_duration)
+    hidden, plan = hidden0.clone(), None
+    out = dict(actions=[], replanned=[], plan=[])
+    for t in range(len(observations)):
+        if resets and t in resets:
+            clock.reset(resets[t])
+        obs, goal = observations[t], goals[t]
+        due = clock.due()
+        for r in due:
+            given = plans is not None and t in plans and not bool(torch.isnan(plans[t][r]).any())
+            row = plans[t][r] if given else plan_fn(obs[r: r + 1], goal[r: r + 1], [r], t)[0]
+            if plan is None:
+                plan = torch.zeros(n_envs, row.shape[-1], dtype=row.dtype, device=row.device)
+            plan = plan.clone()
+            plan[r] = row
+            hidden = hidden.clone()
+            hidden[..., r, :] = 0  # clear_hidden_state(): the row starts from h_0 = 0
+        actions, hidden = decoder_fn(plan, obs, hidden, t)
+        clock.tick(set(due))
+        out["actions"].append(actions)
+        out["replanned"].append(due)
+        out["plan"].append(plan.clone())
+    out["hidden"] = hidden
+    return out

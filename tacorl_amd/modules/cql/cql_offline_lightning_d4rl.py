@@ -69,6 +69,16 @@ class CQL_Offline(_ImageCQL):
             init_views_(blk.views)
         self.sync_targets()
         self._register()
+        self._attach_rollout()
+
+    def _attach_rollout(self, ad=None):
+        """Rollout surface (evaluation/rollout_manager_d4rl.py:183-222): actor.get_actions on [obs | goal] rows, callable
+        critics (modules/cem.py takes them), the action decoder's one-step act where the module has a decoder."""
+        from ..inference import attach_vec_rollout_surface
+
+        e = self.engine
+        attach_vec_rollout_surface(self, self.action_dim, actor_net=e.actor,
+                                   critics={"q1": e.q1, "q2": e.q2, "target_q1": e.tq1, "target_q2": e.tq2}, ad=ad)
 
     def _make_vec_engine(self, state_dim, goal_dim, action_dim, a):
         hp = self._hp

@@ -46,10 +46,151 @@ class EncoderRunner:
         return out.clone()
 
 
-def state_from_observation(owner, runner, net, observation, modalities):
-    """LateFusion.get_state_from_observation: per-camera embeddings concatenated in `modalities` order."""
+def state_from_observation(owner, runner, net, observation, modalities, cat_output=True):
+    """LateFusion.get_state_from_observation: per-camera embeddings concatenated in `modalities` order, or - with
+    cat_output=False (representation_network.py:60-71) - the {camera: embedding} dict."""
     embs = [runner.encode(net.enc(c), observation[c]) for c in modalities]
+    if not cat_output:
+        return dict(zip(modalities, embs))
     return embs[0] if len(embs) == 1 else torch.cat(embs, dim=-1)
+
+
+def _rows(x, dev):
+    """(rows (n, E) fp32 on the device, unbatched?) of an embedding given as (n, E) or (E,)."""
+    x = x.to(dev, torch.float32)
+    return (x.unsqueeze(0), True) if x.dim() == 1 else (x, False)
+
+
+def _mlp_rows(owner, x, ptr_, dims, acts):
+    """One MLP chain of the library on rows x (n, dims[0]); returns the (n, dims[-1]) output (a fresh tensor)."""
+    n, ld = x.shape[0], (dims[0] + 3) // 4 * 4
+    if x.shape[1] != dims[0]:
+        raise ValueError(f"the network takes {dims[0]} input columns, got {x.shape[1]}")
+    xin = torch.zeros(n, ld, device=owner.dev)  # rows of whole 16-byte words, pad columns zero (the chains' vector loads)
+    xin[:, :dims[0]] = x
+    lay = ops.mlp_act_layout(n, dims, acts)
+    act = torch.zeros(lay[2], device=owner.dev)
+    ops.mlp_fwd([xin], ld, [ptr_], [act], [n], dims, acts, owner.compute)
+    yo = lay[1][-1]
+    return act[yo: yo + n * dims[-1]].view(n, dims[-1]).clone()
+
+
+LOG_SIG_MIN, LOG_SIG_MAX, MEAN_MIN, MEAN_MAX = -5.0, 2.0, -9.0, 9.0  # reference actor.py:12-15
+
+
+class TanhNormalDist:
+    """What `get_dist` returns: the reference's TanhNormal (utils/distributions.py:61-153) by its attribute names -
+    normal_mean (the clamped mean), normal_std (exp of the clamped log_std), mean = tanh(normal_mean), stddev - with the draws
+    through the library's sampling kernel.  Holds the policy head as computed; keeps no gradient."""
+
+    def __init__(self, head, A, unbatched=False):
+        self._head, self._A, self._unbatched = head, A, unbatched
+        sq = (lambda t: t[0]) if unbatched else (lambda t: t)
+        self.normal_mean = sq(head[:, :A].clamp(MEAN_MIN, MEAN_MAX))
+        self.normal_std = sq(head[:, A:2 * A].clamp(LOG_SIG_MIN, LOG_SIG_MAX).exp())
+
+    @property
+    def mean(self):
+        return torch.tanh(self.normal_mean)
+
+    @property
+    def stddev(self):
+        return self.normal_std
+
+    def _draw(self, noise, reparameterize):
+        head, A = self._head, self._A
+        n, dev = head.shape[0], head.device
+        eps = torch.randn(n, A, device=dev) if noise is None else noise.to(dev, torch.float32).reshape(n, A).contiguous()
+        act, logp = torch.zeros(n, A, device=dev), torch.zeros(n, device=dev)
+        ops.tanh_normal_sample(head, head.shape[1], eps, None, bool(reparameterize), act, 0, A, logp, None, 1, n, A)
+        return (act[0] if self._unbatched else act), logp
+
+    def sample(self, noise=None):
+        """tanh(normal_mean + normal_std * eps); noise: the N(0,1) draws (n, A)."""
+        return self._draw(noise, False)[0]
+
+    def rsample(self, noise=None):
+        return self._draw(noise, True)[0]
+
+    def sample_and_logprob(self, noise=None):
+        a, lp = self._draw(noise, False)
+        return a, (lp if self._unbatched else lp.view(-1, 1))
+
+
+class PlanProposalSurface:
+    """Bound onto `module.plan_proposal`: Actor.get_dist (actor.py:50-63) over one network block's head MLP."""
+
+    def __init__(self, owner, net, action_dim):
+        self.owner, self.net, self.A = owner, net, int(action_dim)
+
+    def get_dist(self, state_emb, goal_emb=None):
+        """state_emb (n, S) or (S,), goal_emb (n, G) / (G,) or None (state_emb then holds both) -> TanhNormalDist."""
+        s, unb = _rows(state_emb, self.owner.dev)
+        if goal_emb is not None:
+            s = torch.cat([s, _rows(goal_emb, self.owner.dev)[0]], dim=-1)
+        head = _mlp_rows(self.owner, s, self.net.head(), self.net.head_dims, self.net.head_acts)
+        return TanhNormalDist(head, self.A, unb)
+
+
+class VecActorSurface:
+    """Bound onto `module.actor` of the vector-observation modules: Actor.get_actions (actor.py:65-111) on [state | goal]
+    rows (n, E) or one row (E,) (evaluation/rollout_manager_d4rl.py:207-222)."""
+
+    def __init__(self, owner, net, action_dim):
+        self.pp = PlanProposalSurface(owner, net, action_dim)
+        self.A = int(action_dim)
+
+    def emb_representation(self, obs):
+        return obs.to(self.pp.owner.dev, torch.float32)
+
+    def get_actions(self, observation, deterministic=False, reparameterize=False, noise=None):
+        """Returns (actions, log_pi): log_pi is zeros_like(actions) when deterministic, (n, 1) otherwise.
+        noise: {'eps': (n, A) N(0,1)} injects the draws."""
+        d = self.pp.get_dist(observation)
+        if deterministic:
+            # tanh(mean): the sampling kernel with eps = 0
+            a = d.sample(noise=torch.zeros(d._head.shape[0], self.A, device=d._head.device))
+            return a, torch.zeros_like(a)
+        a, lp = d._draw(noise["eps"] if noise else None, reparameterize)
+        return a, (lp if d._unbatched else lp.view(-1, 1))
+
+
+def attach_vec_rollout_surface(module, action_dim, actor_net=None, critics=None, plan_proposal_net=None, ad=None):
+    """The vector-observation modules' rollout methods under the reference's names: `actor.get_actions`, callable critics
+    (which CEMOptimizer accepts), `plan_proposal.get_dist`, `action_decoder.act / clear_hidden_state`."""
+    if actor_net is not None:
+        surf = VecActorSurface(module, actor_net, action_dim)
+        module.__dict__["_actor_surface"] = surf
+        module.actor.get_actions = surf.get_actions
+        module.actor.get_dist = surf.pp.get_dist
+        module.actor.get_emb_representation = surf.emb_representation
+        module.actor.action_dim = int(action_dim)
+        module.actor.discrete_gripper = False
+    for name, net in (critics or {}).items():
+        cs = CriticSurface(module, net, [], [], action_dim)
+        box = getattr(module, name)
+        box.forward = cs.forward
+        box.get_emb_representation = cs.emb_representation
+        box.get_emb_obs_representation = cs.emb_obs_representation
+        box.__dict__["critic_surface"] = cs
+    if plan_proposal_net is not None:
+        pp = PlanProposalSurface(module, plan_proposal_net, action_dim)
+        module.__dict__["_plan_proposal_surface"] = pp
+        module.plan_proposal.get_dist = pp.get_dist
+    if ad is not None:
+        module.action_decoder.clear_hidden_state = ad.clear_hidden_state
+        module.action_decoder.act = lambda latent_plan, perceptual_emb, latent_goal=None, noise=None: ad.act(
+            latent_plan, perceptual_emb, latent_goal, noise=noise, compute=module.compute)
+
+
+def attach_goal_encoder(module, net):
+    """`module.goal_encoder(x)`: the goal-encoder MLP of one network block on embeddings (n, 32 per camera) or one row."""
+    def forward(x):
+        rows, unb = _rows(x, module.dev)
+        y = _mlp_rows(module, rows, net.genc(), net.genc_dims, net.genc_acts)
+        return y[0] if unb else y
+
+    module.goal_encoder.forward = forward
 
 
 class ActorSurface:
@@ -187,8 +328,8 @@ def attach_rollout_surface(module, actor_net, cams, goal_cams, action_dim, discr
         runner = EncoderRunner(module)
         module.__dict__["_pe_runner"] = runner
         module.perceptual_encoder.get_state_from_observation = (
-            lambda observation, modalities=None: state_from_observation(module, runner, lmp_net, observation,
-                                                                        list(modalities or lmp_cams)))
+            lambda observation, modalities=None, cat_output=True: state_from_observation(
+                module, runner, lmp_net, observation, list(modalities or lmp_cams), cat_output))
     if ad is not None:
         module.action_decoder.clear_hidden_state = ad.clear_hidden_state
         module.action_decoder.act = lambda latent_plan, perceptual_emb, latent_goal=None, noise=None: ad.act(

@@ -75,9 +75,11 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         for k, v in self.ad.buffers.items():
             self.action_decoder.register_buffer(k, v)
         self.plan_proposal.action_dim, self.plan_proposal.state_dim, self.plan_proposal.goal_dim = A, self.state_dim, self.goal_dim
-        self.action_decoder.clear_hidden_state = self.ad.clear_hidden_state
-        self.action_decoder.act = lambda latent_plan, perceptual_emb, latent_goal=None, noise=None: self.ad.act(
-            latent_plan, perceptual_emb, latent_goal, noise=noise, compute=self.compute)
+        # rollout surface (evaluation/rollout_manager_d4rl.py:137-146): plan_proposal.get_dist(state_emb (n,29), goal_emb (n,2))
+        # .sample(), action_decoder.clear_hidden_state / act
+        from ..inference import attach_vec_rollout_surface
+
+        attach_vec_rollout_surface(self, A, plan_proposal_net=self.pp, ad=self.ad)
 
     def _blocks(self):
         return [self.pp, self.pr.blk, self.ad.blk]

@@ -100,17 +100,24 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         for k, v in self.ad.buffers.items():
             self.action_decoder.register_buffer(k, v)
         # rollout surface (evaluation/rollout_manager.py PlayLMP manager: plan_proposal.get_actions, action_decoder.act)
-        from ..inference import ActorSurface, EncoderRunner, state_from_observation
+        from ..inference import (ActorSurface, EncoderRunner, PlanProposalSurface, attach_goal_encoder,
+                                 state_from_observation)
 
         surf = ActorSurface(self, self.net, cams, cams, A, False)
         self.__dict__["_actor_surface"] = surf
         self.plan_proposal.get_actions = surf.get_actions
         self.plan_proposal.action_dim = A
+        # LatentPlanRollout (evaluation/rollout_manager.py:234-249): plan_proposal.get_dist(state_emb, goal_emb).sample() on
+        # the embeddings the caller made with perceptual_encoder.get_state_from_observation and goal_encoder
+        pps = PlanProposalSurface(self, self.net, A)
+        self.__dict__["_plan_proposal_surface"] = pps
+        self.plan_proposal.get_dist = pps.get_dist
+        attach_goal_encoder(self, self.net)
         runner = EncoderRunner(self)
         self.__dict__["_pe_runner"] = runner
         self.perceptual_encoder.get_state_from_observation = (
-            lambda observation, modalities=None: state_from_observation(self, runner, self.net, observation,
-                                                                        list(modalities or cams)))
+            lambda observation, modalities=None, cat_output=True: state_from_observation(
+                self, runner, self.net, observation, list(modalities or cams), cat_output))
         self.action_decoder.clear_hidden_state = self.ad.clear_hidden_state
         self.action_decoder.act = lambda latent_plan, perceptual_emb, latent_goal=None, noise=None: self.ad.act(
             latent_plan, perceptual_emb, latent_goal, noise=noise, compute=self.compute)

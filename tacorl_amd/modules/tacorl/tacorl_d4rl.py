@@ -61,6 +61,7 @@ class TACORL(CQL_Offline):
             init_views_(q.views)
         self.sync_targets()
         self._register()
+        self._attach_rollout(ad=self.ad)
         self._pv["action_decoder"] = ad_pv
         e.pre_metrics = [self.ad.finish_loss]  # (the decoder loss leaves its partial sums on the device: loss(lazy=True))
         if self.finetune_action_decoder:

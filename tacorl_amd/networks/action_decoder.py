@@ -20,6 +20,15 @@ from ..blocks import TensorBlock
 RNN_MAXP = 4  # problems one batched ring-GEMM launch takes (RNN_MAXP in csrc/rnn_ops.hip)
 
 
+class RowsState:
+    """Per-row decoder state of ActionDecoderLogistic.step_rows (made by new_rows_state)."""
+
+    @property
+    def hidden(self):
+        """The hidden state the last step left, one (R, H) view per layer (nn.RNN's h_n without the stack)."""
+        return self.h[self.flip]
+
+
 class ActionDecoderLogistic:
     def __init__(self, device, state_dim=32, goal_dim=32, latent_plan_dim=16, hidden_size=256, out_features=7,
                  act_max_bound=(1.0,) * 7, act_min_bound=(-1.0,) * 7, gripper_alpha=1.0, policy_rnn_dropout_p=0.0,
@@ -115,6 +124,112 @@ class ActionDecoderLogistic:
         self._act_flip ^= 1
         self.hidden_state = torch.stack(new)  # (num_layers, B, H) as nn.RNN's h_n
         return self._act_out.view(B, 1, self.AW).clone()
+
+    # ------------------------------------------------------------------ one step for R rows with per-row state
+    def new_rows_state(self, R):
+        """The buffers of step_rows() for R rows (environments), allocated once: ping-pong hidden states per layer, the
+        decoder input, the heads, the two draw buffers and the output."""
+        H, K0 = self.hidden, self.P + self.E
+        sup = ops.L.lib().tacorl_rows_linear2_supported
+        if not (sup(R, K0, H, H) and sup(R, H, H, H) and sup(R, H, 0, self.NH)):
+            raise ValueError(f"step_rows takes 1 to 64 rows, got {R}")
+        ops.note_alloc()
+        f = lambda *s: torch.zeros(*s, device=self.dev)  # noqa: E731
+        st = RowsState()
+        st.R, st.flip = R, 0
+        st.x = f(R, K0)
+        st.h = [[f(R, H) for _ in range(self.L)] for _ in range(2)]  # [flip][layer]: previous / new hidden state
+        st.heads, st.out = f(R, (self.NH + 31) // 32 * 32), f(R, self.AW)
+        st.ra, st.rb = f(R, self.Da, self.K), f(R, self.Da)
+        # restart patterns on the device, made once each (a host sequence is uploaded the first time it is seen: a pageable
+        # copy per step would stall the host behind the stream and leave the step's launches waiting for their enqueue)
+        st.flag_cache = {}
+        st.xin = f(R, H)  # the composed route's input projection (rows_route)
+        nb = ops.L.lib().tacorl_linear_add_fwd_ws_bytes(1, ops.int_array([R]), H, H)
+        st.ws = torch.empty(max(256, nb), dtype=torch.uint8, device=self.dev)
+        return st
+
+    # Up to this many rows step_rows runs the rows kernel; above it, the kernels `act` is made of.  One row group of the rows
+    # kernel reads every weight once; every further group of 8 rows reads them again, and from the third group on the training
+    # GEMMs, which read them once whatever R is, are the faster ones (profiles/vec_rollout.md).
+    ROWS_KERNEL_MAX_R = 16
+
+    def rows_route(self, R):
+        """'rows' (tacorl_rows_linear2_fwd) or 'composed' (act's GEMM launches on the state's buffers) for a step of R rows."""
+        return "rows" if R <= self.ROWS_KERNEL_MAX_R else "composed"
+
+    def _restart_flags(self, state, restart):
+        """(R uint8 flags on the device, may any row restart?) of a host sequence or a device uint8 / bool tensor."""
+        if isinstance(restart, torch.Tensor) and restart.device == state.x.device:
+            t = restart.reshape(state.R)
+            return (t.view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8)), True
+        key = bytes(1 if v else 0 for v in restart)
+        if len(key) != state.R:
+            raise ValueError(f"restart needs {state.R} flags, got {len(key)}")
+        t = state.flag_cache.get(key)
+        if t is None:
+            if len(state.flag_cache) >= 256:
+                state.flag_cache.clear()
+            ops.note_alloc()
+            t = state.flag_cache[key] = torch.tensor(list(key), dtype=torch.uint8, device=state.x.device)
+        return t, any(key)
+
+    def _step_rows_composed(self, state, prev, new, flags):
+        """The RNN cells and the heads of step_rows by the training GEMMs (`act`'s launches, fp32) on the state's buffers, the
+        restarted rows' previous hidden state zeroed first (flags: None when no row restarts; a fill, not a product - whatever
+        the rows hold, NaN included)."""
+        R, H, blk = state.R, self.hidden, self.blk
+        x, K = state.x, self.P + self.E
+        for l in range(self.L):
+            if flags is not None:
+                prev[l].masked_fill_(flags.view(torch.bool).unsqueeze(1), 0.0)
+            self._lin(x, K, blk.p(f"rnn.weight_ih_l{l}"), blk.p(f"rnn.bias_ih_l{l}"), state.xin, R, K, H, ACT_NONE, ops.F32)
+            call("tacorl_linear_add_fwd", 1, ops.ptr_array([prev[l]]), H, ops.ptr_array([blk.p(f"rnn.weight_hh_l{l}")]),
+                 ops.ptr_array([blk.p(f"rnn.bias_hh_l{l}")]), ops.ptr_array([state.xin]), H, ops.ptr_array([new[l]]), H,
+                 ops.int_array([R]), H, H, ACT_RELU, ops.F32, ptr(state.ws), state.ws.numel(), ops.stream())
+            x, K = new[l], H
+        self._lin(x, H, blk.p("mean_fc.weight"), blk.p("mean_fc.bias"), state.heads, R, H, self.NH, ACT_NONE, ops.F32,
+                  ldy=state.heads.shape[1])
+
+    def step_rows(self, state, plan, emb, restart, noise=None):
+        """One decoder step (reference :87-97) for the R rows of `state`, each with its OWN hidden state: a row flagged in
+        `restart` (R flags: a host sequence, or a device uint8 / bool tensor) starts from h_0 = 0 in every layer, whatever its
+        buffers hold; the others continue from their previous step.  plan (R,P) and emb (R,E) fp32 device tensors;
+        noise = (rand_a (R,Da,K), rand_b (R,Da)) injects the two U(0,1) draws of `_sample`.  A fixed launch sequence -
+        tacorl_build_ad_input, one tacorl_rows_linear2_fwd per RNN layer and one for the heads, the mixture sampler - without
+        allocation (but a restart pattern's first upload) or host read; above ROWS_KERNEL_MAX_R rows the cells and the heads go through the kernels `act` is made of
+        instead (rows_route), the restarted rows zeroed first.  fp32 from the master weights whatever the module's compute dtype.  Returns (R, AW): a view
+        of the state's output buffer, valid until the next call on that state."""
+        R, H, L, blk = state.R, self.hidden, self.L, self.blk
+        if plan.shape != (R, self.P) or emb.shape != (R, self.E) or plan.dtype != torch.float32 or emb.dtype != torch.float32:
+            raise ValueError(f"step_rows takes fp32 plan ({R}, {self.P}) and emb ({R}, {self.E}), got {tuple(plan.shape)} and "
+                             f"{tuple(emb.shape)}")
+        if not (plan.is_contiguous() and emb.stride(1) == 1 and plan.device == state.x.device == emb.device):
+            raise ValueError("step_rows takes device tensors with contiguous rows")
+        flags, any_restart = self._restart_flags(state, restart)
+        call("tacorl_build_ad_input", ptr(plan), ptr(emb), emb.stride(0), ptr(state.x), R, 1, 1, self.P, self.E, ops.stream())
+        prev, new = state.h[state.flip], state.h[state.flip ^ 1]
+        if self.rows_route(R) == "composed":
+            self._step_rows_composed(state, prev, new, flags if any_restart else None)
+        else:
+            x, K = state.x, self.P + self.E
+            for l in range(L):
+                call("tacorl_rows_linear2_fwd", ptr(x), K, K, blk.p(f"rnn.weight_ih_l{l}"), blk.p(f"rnn.bias_ih_l{l}"), ptr(prev[l]),
+                     H, H, blk.p(f"rnn.weight_hh_l{l}"), blk.p(f"rnn.bias_hh_l{l}"), ptr(flags), ptr(new[l]), H, R, H,
+                     ACT_RELU, ops.stream())
+                x, K = new[l], H
+            call("tacorl_rows_linear2_fwd", ptr(x), H, H, blk.p("mean_fc.weight"), blk.p("mean_fc.bias"), None, 0, 0, None, None,
+                 None, ptr(state.heads), state.heads.shape[1], R, self.NH, ACT_NONE, ops.stream())
+        if noise is not None:
+            state.ra.copy_(noise[0].reshape(state.ra.shape))
+            state.rb.copy_(noise[1].reshape(state.rb.shape))
+        else:
+            state.ra.uniform_()
+            state.rb.uniform_()
+        call("tacorl_logistic_mixture_sample" if self.discrete_gripper else "tacorl_logistic_mixture_nogrip_sample",
+             ptr(state.heads), state.heads.shape[1], ptr(state.ra), ptr(state.rb), ptr(state.out), R, self.Da, self.K, ops.stream())
+        state.flip ^= 1
+        return state.out
 
     def _ensure(self, B, Tm):
         if self._shape == (B, Tm):
