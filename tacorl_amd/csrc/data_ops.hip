@@ -8,6 +8,8 @@
 #include "../../include/tacorl_hip.h"
 #include "common.h"
 
+#include <initializer_list>
+
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH)
 
 namespace {
@@ -189,20 +191,50 @@ __device__ __forceinline__ long pick_of(double u, long n) {  // floor(u * n) kep
   return k < 0 ? 0 : (k > n - 1 ? n - 1 : k);
 }
 
+// What the four samplers below share.
+// v kept inside [lo, hi]; a clamp that had to change it sets `bad` (the status word).
+__device__ __forceinline__ long clamped(long v, long lo, long hi, bool& bad) {
+  if (v < lo || v > hi) { bad = true; v = v < lo ? lo : hi; }
+  return v;
+}
+
+// The index of the last episode whose start is <= step (binary search over the sorted starts), -1 where there is none.
+__device__ __forceinline__ int episode_of(const long* ep_start, int n_ep, long step) {
+  int lo = 0, hi = n_ep;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (ep_start[mid] <= step) lo = mid + 1; else hi = mid;
+  }
+  return lo - 1;
+}
+
+// How the two wavefront-per-window kernels begin: item b's position in the lookup table, its window size in
+// [min_window, Tmax] and its first frame s, so that the rows s .. s + ws - 1 exist.
+struct Window { long pos; int ws; long s; };
+__device__ __forceinline__ Window window_of(const long* idx, const long* window, const long* lookup, long n_items, long n_frames,
+                                            int b, int min_window, int Tmax, bool& bad) {
+  Window w;
+  w.pos = clamped(idx[b], 0, n_items - 1, bad);
+  w.ws = (int)clamped(window[b], min_window, Tmax, bad);
+  w.s = clamped(lookup[w.pos], 0, n_frames - w.ws, bad);
+  return w;
+}
+
+// Every pointer non-null (unless it may be absent) and aligned to `align` bytes, a power of two.
+bool pointers_ok(std::initializer_list<const void*> ps, uintptr_t align, bool may_be_null = false) {
+  for (const void* p : ps)
+    if ((!p && !may_be_null) || ((uintptr_t)p & (align - 1))) return false;
+  return true;
+}
+
 __global__ __launch_bounds__(256) void sample_transitions_kernel(TransTbl t, int B, int A) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   bool bad = false;
-  long pos = t.idx[b];
-  if (pos < 0 || pos >= t.n_steps) { bad = true; pos = pos < 0 ? 0 : t.n_steps - 1; }
+  const long pos = clamped(t.idx[b], 0, t.n_steps - 1, bad);
   const long step = t.steps[pos];
-  // episode end: the last episode whose start is <= step (binary search over the sorted starts)
-  int lo = 0, hi = t.n_ep;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (t.ep_start[mid] <= step) lo = mid + 1; else hi = mid;
-  }
-  const long end = t.ep_end[lo > 0 ? lo - 1 : 0];
+  const int ep = episode_of(t.ep_start, t.n_ep, step);
+  const long end = t.ep_end[ep > 0 ? ep : 0];
   const double u = t.u[b];
   long strat = t.strategy[b];
   long goal = step + 1;
@@ -235,12 +267,7 @@ __global__ __launch_bounds__(256) void sample_transitions_kernel(TransTbl t, int
   const long top = t.n_frames - 1;
   long id[3] = {step, step + 1, goal};
 #pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const long c = id[k] < 0 ? 0 : (id[k] > top ? top : id[k]);
-    bad |= c != id[k];
-    t.ids[(long)k * B + b] = c;
-    id[k] = c;
-  }
+  for (int k = 0; k < 3; k++) t.ids[(long)k * B + b] = id[k] = clamped(id[k], 0, top, bad);
   const float r = goal == step + 1 ? 1.f : 0.f;
   t.reward[b] = r;
   t.done[b] = r;
@@ -266,19 +293,11 @@ __global__ __launch_bounds__(256) void sample_relay_kernel(RelayTbl t, int B, in
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
   bool bad = false;
-  long pos = t.idx[b];
-  if (pos < 0 || pos >= t.n_items) { bad = true; pos = pos < 0 ? 0 : t.n_items - 1; }
+  const long pos = clamped(t.idx[b], 0, t.n_items - 1, bad);
   const long top = t.n_frames - 1;
-  long step = t.lookup[pos];
-  if (step < 0 || step > top) { bad = true; step = step < 0 ? 0 : top; }
-  // episode end: the last episode whose start is <= step (binary search over the sorted starts)
-  int lo = 0, hi = t.n_ep;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (t.ep_start[mid] <= step) lo = mid + 1; else hi = mid;
-  }
-  long end = t.ep_end[lo > 0 ? lo - 1 : 0];
-  if (end < step || end > top) { bad = true; end = end < step ? step : top; }
+  const long step = clamped(t.lookup[pos], 0, top, bad);
+  const int ep = episode_of(t.ep_start, t.n_ep, step);
+  const long end = clamped(t.ep_end[ep > 0 ? ep : 0], step, top, bad);
   // min(end, step + window) without the overflow of a huge window
   const long sub = t.low_window >= end - step ? end : step + t.low_window;    // the subgoal frame (high_level_action)
   const long hmax = t.high_window >= end - step ? end : step + t.high_window;
@@ -288,11 +307,7 @@ __global__ __launch_bounds__(256) void sample_relay_kernel(RelayTbl t, int B, in
   const long high = nh > 0 ? sub + pick_of(t.u_high[b], nh) : hmax;
   const long id[4] = {step, low, high, sub};  // obs | low_level_goal | high_level_goal | high_level_action
 #pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const long c = id[k] < 0 ? 0 : (id[k] > top ? top : id[k]);
-    bad |= c != id[k];
-    t.ids[(long)k * B + b] = c;
-  }
+  for (int k = 0; k < 4; k++) t.ids[(long)k * B + b] = clamped(id[k], 0, top, bad);
   const float* __restrict__ a = t.actions + step * A;
   for (int k = 0; k < A; k++) t.action[(long)b * A + k] = a[k];
   if (bad) *t.status = 1;
@@ -318,28 +333,19 @@ __global__ __launch_bounds__(256) void sample_d4rl_windows_kernel(D4rlTbl t, int
   const int lane = threadIdx.x & 63;
   if (b >= B) return;
   bool bad = false;
-  long pos = t.idx[b];
-  if (pos < 0 || pos >= t.n_items) { bad = true; pos = pos < 0 ? 0 : t.n_items - 1; }
-  long wl = t.window[b];
-  if (wl < min_window || wl > Tmax) { bad = true; wl = wl < min_window ? min_window : Tmax; }
-  const int ws = (int)wl;
-  long s = t.lookup[pos];
-  if (s < 0 || s > t.n_frames - ws) { bad = true; s = s < 0 ? 0 : t.n_frames - ws; }  // rows s .. s + ws - 1 exist
+  const Window w = window_of(t.idx, t.window, t.lookup, t.n_items, t.n_frames, b, min_window, Tmax, bad);
+  const int ws = w.ws;
+  const long s = w.s;
   long goal_step = s;
   if (G > 0) {
-    // episode end: the last episode whose start is <= s (binary search over the sorted starts)
-    int lo = 0, hi = t.n_ep;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (t.ep_start[mid] <= s) lo = mid + 1; else hi = mid;
-    }
-    const long end = t.ep_end[lo > 0 ? lo - 1 : 0];
+    const int ep = episode_of(t.ep_start, t.n_ep, s);
+    const long end = t.ep_end[ep > 0 ? ep : 0];
     long d = t.disp[b];
     if (d < 1) { bad = true; d = 1; }
     // min(end, s + (ws - 1) * disp) without the overflow of a huge draw: the product is formed only where it stays <= end
     const long stride = ws - 1;
     goal_step = (stride == 0 || end < s || d > (end - s) / stride) ? (stride == 0 ? s : end) : s + stride * d;
-    if (goal_step < 0 || goal_step > t.n_frames - 1) { bad = true; goal_step = goal_step < 0 ? 0 : t.n_frames - 1; }
+    goal_step = clamped(goal_step, 0, t.n_frames - 1, bad);
   }
   {
     const float* __restrict__ src = t.observations + s * S;
@@ -395,34 +401,23 @@ __global__ __launch_bounds__(256) void sample_play_windows_kernel(PlayTbl t, int
   if (b >= B) return;
   bool bad = false;
   const long top = t.n_frames - 1;
-  long pos = t.idx[b];
-  if (pos < 0 || pos >= t.n_items) { bad = true; pos = pos < 0 ? 0 : t.n_items - 1; }
-  long wl = t.window[b];
-  if (wl < min_window || wl > Tmax) { bad = true; wl = wl < min_window ? min_window : Tmax; }
-  const int ws = (int)wl;
-  long s = t.lookup[pos];
-  if (s < 0 || s > t.n_frames - ws) { bad = true; s = s < 0 ? 0 : t.n_frames - ws; }  // frames s .. s + ws - 1 exist
-  long strat = t.strategy[b];
-  if (strat < 0 || strat > 1) { bad = true; strat = strat < 0 ? 0 : 1; }
+  const Window w = window_of(t.idx, t.window, t.lookup, t.n_items, t.n_frames, b, min_window, Tmax, bad);
+  const int ws = w.ws;
+  const long s = w.s;
+  const long strat = clamped(t.strategy[b], 0, 1, bad);
   long d = t.disp[b];
   if (d < 1) { bad = true; d = 1; }
   // the random state (play_dataset.py:262-264): another item's first frame
-  long rs = t.lookup[pick_of(t.u_random[b], t.n_items)];
-  if (rs < 0 || rs > top) { bad = true; rs = rs < 0 ? 0 : top; }
+  const long rs = clamped(t.lookup[pick_of(t.u_random[b], t.n_items)], 0, top, bad);
   long goal;
   if (strat == 0) {
-    // find_episode_end: the last episode whose start is <= s (binary search over the sorted starts), -1 where s lies in none
-    int lo = 0, hi = t.n_ep;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (t.ep_start[mid] <= s) lo = mid + 1; else hi = mid;
-    }
-    const long end = lo > 0 ? t.ep_end[lo - 1] : -1;
+    // find_episode_end: -1 where s lies in no episode (before the first start, or behind the end of the one found)
+    const int ep = episode_of(t.ep_start, t.n_ep, s);
+    const long end = ep >= 0 ? t.ep_end[ep] : -1;
     if (end < s) {
       goal = rs;
     } else {
-      long nz = t.noise ? t.noise[b] : 0;
-      if (nz < -1 || nz > 1) { bad = true; nz = nz < 0 ? -1 : 1; }
+      const long nz = clamped(t.noise ? t.noise[b] : 0, -1, 1, bad);
       // min(end, s + (ws - 1) * disp + noise) without the overflow of a huge draw: the product is formed only where the sum
       // stays <= end, i.e. (ws - 1) * disp <= lim; a one-frame window has stride 0 and is not divided by
       const long stride = ws - 1, lim = end - s - nz;
@@ -436,9 +431,7 @@ __global__ __launch_bounds__(256) void sample_play_windows_kernel(PlayTbl t, int
     if (t.n_nn > 0) total = t.nn_ptr[t.n_nn];
     if (key >= 0 && key < t.n_nn) { first = t.nn_ptr[key]; cnt = t.nn_ptr[key + 1] - first; }
     if (cnt > 0 && total > 0) {
-      long at = first + pick_of(t.u_choice[b], cnt);
-      if (at < 0 || at > total - 1) { bad = true; at = at < 0 ? 0 : total - 1; }
-      goal = t.nn_val[at];
+      goal = t.nn_val[clamped(first + pick_of(t.u_choice[b], cnt), 0, total - 1, bad)];
       if (goal < 0 || goal > top) bad = true;  // (the clip below brings it inside)
     } else {
       goal = rs;  // no neighbour recorded: the reference's fallback
@@ -478,15 +471,11 @@ extern "C" int tacorl_sample_play_windows(const long* episode_lookup, long n_ite
   if (B <= 0 || Tmax <= 0 || A <= 0 || n_items <= 0 || n_episodes <= 0 || n_frames <= 0 || n_nn < 0) return TACORL_EINVAL;
   if (min_window < 1 || min_window > Tmax || n_frames < Tmax || last_end < 0 || last_end >= n_frames) return TACORL_EINVAL;
   if ((long)Tmax * A > 0x7fffffffL || (long)B + 3 > 0x7fffffffL) return TACORL_EINVAL;
-  const void* p8[] = {episode_lookup, ep_start, ep_end, idx, window, strategy, disp, u_choice, u_random_state, ids, disp_out,
-                      window_size};
-  const void* p4[] = {actions, act, status};
-  for (const void* p : p8)
-    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
-  for (const void* p : p4)
-    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
-  if ((uintptr_t)noise_step & 7) return TACORL_EINVAL;
-  if (n_nn > 0 && (!nn_ptr || !nn_val || ((uintptr_t)nn_ptr & 7) || ((uintptr_t)nn_val & 7))) return TACORL_EINVAL;
+  if (!pointers_ok({episode_lookup, ep_start, ep_end, idx, window, strategy, disp, u_choice, u_random_state, ids, disp_out,
+                    window_size}, 8) ||
+      !pointers_ok({actions, act, status}, 4) || !pointers_ok({noise_step}, 8, true) ||
+      (n_nn > 0 && !pointers_ok({nn_ptr, nn_val}, 8)))
+    return TACORL_EINVAL;
   const PlayTbl t{episode_lookup, n_items, ep_start, ep_end, n_episodes, nn_ptr, n_nn, nn_val, actions, n_frames, last_end,
                   idx, window, strategy, disp, noise_step, u_choice, u_random_state, ids, act, disp_out, window_size, status};
   hipLaunchKernelGGL(sample_play_windows_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, t, B, Tmax, A,
@@ -503,14 +492,9 @@ extern "C" int tacorl_sample_d4rl_windows(const long* episode_lookup, long n_ite
   if (B <= 0 || Tmax <= 0 || S <= 0 || A <= 0 || n_items <= 0 || n_episodes <= 0) return TACORL_EINVAL;
   if (G < 0 || G == 1 || G > S || min_window < 1 || min_window > Tmax || n_frames < Tmax) return TACORL_EINVAL;
   if ((long)Tmax * S > 0x7fffffffL || (long)Tmax * A > 0x7fffffffL || (long)B + 3 > 0x7fffffffL) return TACORL_EINVAL;
-  const void* p8[] = {episode_lookup, ep_start, ep_end, idx, window, disp};
-  const void* p4[] = {observations, actions, obs, act, status};
-  for (const void* p : p8)
-    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
-  for (const void* p : p4)
-    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
-  if (((uintptr_t)goal & 3) || ((uintptr_t)reached & 3) || ((uintptr_t)done & 3) || ((uintptr_t)window_size & 7) ||
-      ((uintptr_t)ids & 7))
+  if (!pointers_ok({episode_lookup, ep_start, ep_end, idx, window, disp}, 8) ||
+      !pointers_ok({observations, actions, obs, act, status}, 4) || !pointers_ok({goal, reached, done}, 4, true) ||
+      !pointers_ok({window_size, ids}, 8, true))
     return TACORL_EINVAL;
   const D4rlTbl t{episode_lookup, n_items, ep_start, ep_end, n_episodes, observations, actions, n_frames, idx, window, disp,
                   obs, act, goal, reached, done, window_size, ids, status};
@@ -526,13 +510,9 @@ extern "C" int tacorl_sample_transitions(const long* possible_steps, long n_poss
                                          int B, int A, long* ids, float* action, float* reward, float* done, int* status,
                                          tacorl_stream_t stream) {
   if (B <= 0 || A <= 0 || n_possible <= 0 || n_episodes <= 0 || n_frames <= 0 || n_nn < 0) return TACORL_EINVAL;
-  const void* p8[] = {possible_steps, ep_start, ep_end, idx, strategy, disp, u_choice, ids};
-  const void* p4[] = {actions, action, reward, done, status};
-  for (const void* p : p8)
-    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
-  for (const void* p : p4)
-    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
-  if (n_nn > 0 && (!nn_ptr || !nn_val || ((uintptr_t)nn_ptr & 7) || ((uintptr_t)nn_val & 7))) return TACORL_EINVAL;
+  if (!pointers_ok({possible_steps, ep_start, ep_end, idx, strategy, disp, u_choice, ids}, 8) ||
+      !pointers_ok({actions, action, reward, done, status}, 4) || (n_nn > 0 && !pointers_ok({nn_ptr, nn_val}, 8)))
+    return TACORL_EINVAL;
   const TransTbl t{possible_steps, n_possible, ep_start, ep_end, n_episodes, nn_ptr, n_nn, nn_val, actions, idx, strategy,
                    disp, u_choice, current_horizon, n_frames, ids, action, reward, done, status};
   hipLaunchKernelGGL(sample_transitions_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, B, A);
@@ -546,12 +526,8 @@ extern "C" int tacorl_sample_relay(const long* episode_lookup, long n_items, con
   if (B <= 0 || A <= 0 || n_items <= 0 || n_episodes <= 0 || n_frames <= 0 || max_low_level_window <= 0 ||
       max_high_level_window <= 0)
     return TACORL_EINVAL;
-  const void* p8[] = {episode_lookup, ep_start, ep_end, idx, u_low, u_high, ids};
-  const void* p4[] = {actions, action, status};
-  for (const void* p : p8)
-    if (!p || ((uintptr_t)p & 7)) return TACORL_EINVAL;
-  for (const void* p : p4)
-    if (!p || ((uintptr_t)p & 3)) return TACORL_EINVAL;
+  if (!pointers_ok({episode_lookup, ep_start, ep_end, idx, u_low, u_high, ids}, 8) || !pointers_ok({actions, action, status}, 4))
+    return TACORL_EINVAL;
   const RelayTbl t{episode_lookup, n_items, ep_start, ep_end, n_episodes, actions, n_frames, idx, u_low, u_high,
                    max_low_level_window, max_high_level_window, ids, action, status};
   hipLaunchKernelGGL(sample_relay_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, B, A);

@@ -29,6 +29,39 @@ class AugmentSpec:
         return shift, torch.cat([b[:, None], c[:, None], h[:, None], order, apply[:, None]], dim=1).contiguous()
 
 
+def augment_specs(transform_manager, cams, split="train"):
+    """{camera: AugmentSpec or None} out of a transform manager config of the `rl` form (config/datamodule/transform_manager/
+    rl.yaml: transforms.<split>.<camera> = a list of {_target_, ...}): Resize(size) -> spec.resize, RandomShiftsAug(pad) ->
+    spec.pad, ColorTransform(contrast, brightness, hue, prob) -> the spec's jitter; ScaleImageTensor and Normalize(0.5, 0.5)
+    are what the uint8 pack computes anyway.  Any other transform of a camera in `cams` is not built.  None: no config."""
+    if transform_manager is None:
+        return {c: None for c in cams}
+    cfg = dict(transform_manager)
+    lists = dict(dict(cfg.get("transforms", cfg) or {}).get(split) or {})
+    out = {}
+    for c in cams:
+        kw, seen = {"pad": 0, "prob": 0.0}, False
+        for t in lists.get(c) or []:
+            t = dict(t)
+            name = str(t.get("_target_", "")).rsplit(".", 1)[-1]
+            if name == "Resize":
+                size = t["size"]
+                kw["resize"] = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+            elif name == "RandomShiftsAug":
+                kw["pad"], seen = int(t.get("pad", 4)), True
+            elif name == "ColorTransform":
+                kw.update(brightness=t.get("brightness", 0.0), contrast=t.get("contrast", 0.0), hue=t.get("hue", 0.0),
+                          prob=t.get("prob", 1.0))
+                seen = True
+            elif name == "Normalize":
+                if [float(x) for x in t.get("mean", [0.5])] != [0.5] or [float(x) for x in t.get("std", [0.5])] != [0.5]:
+                    raise NotImplementedError(f"transform {t.get('_target_')} of {c}: only Normalize(0.5, 0.5) is part of the pack")
+            elif name != "ScaleImageTensor":  # (x / 255: part of the pack)
+                raise NotImplementedError(f"transform {t.get('_target_')} of {c} is not built")
+        out[c] = AugmentSpec(**kw) if seen or "resize" in kw else None
+    return out
+
+
 def draw_play_batch_augmentation(specs, B, T, device, generator=None):
     """batch["aug"] for a play batch: per camera a different draw for every frame of the window and for the goal frame,
     as the reference's dataset applies its transform to (T,3,H,W) windows and to the goal frame separately

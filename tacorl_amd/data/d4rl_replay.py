@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from .resident import ResidentLoader, ResidentReplay, episode_end, index_tables, validate_episodes
 
 GOAL_DIM = 2  # the goal is the (x, y) position: observations[goal_step][:2] (:117-118)
 NPZ_KEYS = ("observations", "actions", "timeouts", "terminals")  # env.get_dataset()'s names
@@ -59,9 +60,8 @@ class D4RLWindowIndex:
         self.episode_lookup = np.concatenate([np.arange(s, max(e + 1 - self.max, s)) for s, e in self.ep]).astype(np.int64)
         if len(self.episode_lookup) == 0:
             raise ValueError("no episode as long as max_window_size: the dataset has no item")
-        end = self.episode_end(self.episode_lookup)
-        if (self.ep.min() < 0 or self.ep.max() >= self.n_frames or (self.ep[1:, 0] <= self.ep[:-1, 1]).any()
-                or (self.episode_lookup + self.max - 1 > end).any()):
+        validate_episodes(self.ep, self.n_frames)
+        if (self.episode_lookup + self.max - 1 > self.episode_end(self.episode_lookup)).any():
             raise ValueError("episode tables outside the dataset")
 
     def __len__(self):
@@ -92,9 +92,8 @@ class D4RLWindowIndex:
         return {"idx": idx, "window": win, "disp": disp}
 
     def episode_end(self, step):
-        """find_episode_end (:107-111) by binary search: the end of the episode with start <= step <= end."""
-        k = np.maximum(np.searchsorted(self.ep[:, 0], np.asarray(step), side="right") - 1, 0)
-        return self.ep[k, 1]
+        """find_episode_end (:107-111): the end of the episode with start <= step <= end."""
+        return episode_end(self.ep, step)
 
     def sample(self, idx, d, observations, actions):
         """The numpy definition.  idx (n,) items (None: d["idx"]); d = draw(...); observations (N, S), actions (N, A) float32.
@@ -123,29 +122,26 @@ class D4RLWindowIndex:
                 "goal": goal.astype(np.float32), "goal_reached": reached}
 
 
-class HbmD4RLReplay:
-    """The D4RL window batches out of a dataset resident in HBM: the (N, S) observation and (N, A) action tables and the index
-    tables live on the device, and a batch is one launch of the sampler kernel (`tacorl_sample_d4rl_windows`) on the current
-    stream - no host synchronisation, nothing over PCIe.  Dense batches are views of this object's own buffers, a ring of
-    `slots` sets (as HbmTransitionReplay's): a batch stays valid until `slots - 1` more have been drawn."""
+class HbmD4RLReplay(ResidentReplay):
+    """The D4RL window batches out of a dataset resident in HBM (data/resident.py ResidentReplay): the (N, S) observation and
+    (N, A) action tables and the index tables live on the device, and a batch is one launch of the sampler kernel
+    (`tacorl_sample_d4rl_windows`) on the current stream - no host synchronisation, nothing over PCIe.  The ring holds the
+    dense batches only: a fused batch is its draws, and the module's staging samples into its own buffers (`sample_into`)."""
+
+    SUBJECT = "d4rl replay"
+    DRAWS = {"idx": np.int64, "window": np.int64, "disp": np.int64}
 
     def __init__(self, observations, actions, index, device=None, batch_size=64, slots=6):
         as_t = lambda a: torch.as_tensor(a if torch.is_tensor(a) else np.asarray(a, dtype=np.float32))  # noqa: E731
         obs, acts = as_t(observations), as_t(actions)
-        self.dev = torch.device(device) if device is not None else obs.device
-        self.index, self.batch_size = index, int(batch_size)
         if obs.dim() != 2 or acts.dim() != 2 or obs.shape[0] < index.n_frames or acts.shape[0] < index.n_frames or obs.shape[1] < GOAL_DIM:
             raise ValueError(f"observations (N,S) and actions (N,A) must cover the index's {index.n_frames} frames")
-        i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)  # noqa: E731
-        self.tables = {"lookup": i64(index.episode_lookup), "ep_start": i64(index.ep[:, 0]), "ep_end": i64(index.ep[:, 1]),
+        super().__init__(device if device is not None else obs.device, index, batch_size, slots)
+        self.tables = {**index_tables(self.dev, index, lookup=index.episode_lookup),
                        "observations": obs.to(self.dev, torch.float32).contiguous(),
                        "actions": acts.to(self.dev, torch.float32).contiguous(), "n_frames": index.n_frames}
         self.S, self.A, self.T = int(obs.shape[1]), int(acts.shape[1]), index.max
         self.G = GOAL_DIM if index.include_goal else 0
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        if int(slots) < 1:
-            raise ValueError("slots must be >= 1")
-        self._cap, self._ring, self._k = 0, [{} for _ in range(int(slots))], 0
         self._grow(self.batch_size)
 
     @classmethod
@@ -160,29 +156,10 @@ class HbmD4RLReplay:
         return cls(a["observations"], a["actions"], D4RLWindowIndex(a["timeouts"], a["terminals"], **index_kwargs),
                    device=device, batch_size=batch_size, slots=slots)
 
-    def _grow(self, B):
-        """The batch buffers exist before the first batch and are replaced only for a larger one - under the capture lock,
-        and captured graphs that could hold an old address are dropped (as HbmTransitionReplay._grow)."""
-        if B <= self._cap:
-            return
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=self.dev)  # noqa: E731
-        with ops.capture_lock:
-            for k in range(len(self._ring)):
-                self._ring[k] = {"obs": z(B * self.T * self.S), "act": z(B * self.T * self.A), "goal": z(B * GOAL_DIM),
-                                 "reached": z(B), "window_size": z(B, dt=torch.int64), "ids": z(2 * B, dt=torch.int64)}
-            self._cap = B
-            ops.note_alloc()
-
-    def check(self):
-        """Reads the sampler's status word back (a host synchronisation: call it when you ask, not per step)."""
-        if int(self.status.item()) != 0:
-            raise IndexError("d4rl replay: the sampler had to clamp an id (tables or draws outside the dataset)")
-
-    def _draws(self, draws, batch_size=None):
-        if draws is None:
-            draws = self.index.draw_device(batch_size or self.batch_size, self.dev)
-        return {k: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.int64))).to(self.dev).contiguous()
-                for k, v in draws.items() if k in ("idx", "window", "disp")}
+    def _slot(self, B):
+        f32, i64 = torch.float32, torch.int64
+        return {"obs": (B * self.T * self.S, f32), "act": (B * self.T * self.A, f32), "goal": (B * GOAL_DIM, f32),
+                "reached": (B, f32), "window_size": (B, i64), "ids": (2 * B, i64)}
 
     def sample_into(self, d, obs, actions, goal=None, reached=None, done=None, window_size=None, ids=None):
         """One sampler launch that writes the caller's buffers: obs (B, T, S), actions (B, T, A) and, where given, goal (B, 2),
@@ -204,9 +181,7 @@ class HbmD4RLReplay:
         B = int(d["idx"].numel())
         if fused:
             return {"replay": {"kind": "d4rl_window", "replay": self, "draws": d, "B": B, "T": self.T}}
-        self._grow(B)
-        self._k = slot = (self._k + 1) % len(self._ring)
-        buf = self._ring[slot]
+        _, buf = self._next(B)
         obs, act = buf["obs"][: B * self.T * self.S].view(B, self.T, self.S), buf["act"][: B * self.T * self.A].view(B, self.T, self.A)
         ws, ids = buf["window_size"][:B], buf["ids"][: 2 * B].view(2, B)
         b = {"observations": obs, "actions": act, "idx": d["idx"], "window_size": ws}
@@ -216,23 +191,12 @@ class HbmD4RLReplay:
         return b
 
 
-class D4RLWindowLoader:
-    """`steps_per_epoch` batches of `batch_size` fresh device draws per pass: what Trainer.fit takes as train_dataloaders for
-    the D4RL modules (the counterpart of TransitionLoader).  A dense batch is views of the replay's ring of buffers
-    (HbmD4RLReplay(slots=6)): a trainer may hold up to `slots - 1` batches ahead of the one it is running; a fused batch
-    holds nothing but its draws."""
+class D4RLWindowLoader(ResidentLoader):
+    """The loader of the D4RL modules (data/resident.py ResidentLoader) over an HbmD4RLReplay: no augmentation, no validation
+    form; a fused batch holds nothing but its draws."""
 
     def __init__(self, replay, batch_size, steps_per_epoch, generator=None, fused=True):
-        self.replay, self.batch_size, self.steps_per_epoch = replay, int(batch_size), int(steps_per_epoch)
-        self.generator, self.fused = generator, fused
-
-    def __len__(self):
-        return self.steps_per_epoch
-
-    def __iter__(self):
-        rp = self.replay
-        for _ in range(self.steps_per_epoch):
-            yield rp.batch(rp.index.draw_device(self.batch_size, rp.dev, self.generator), fused=self.fused)
+        super().__init__(replay, batch_size, steps_per_epoch, generator=generator, fused=fused)
 
 
 _INDEX_KEYS = ("min_window_size", "max_window_size", "pad", "include_goal", "goal_sampling_prob", "goal_augmentation",

@@ -13,10 +13,9 @@ import torch
 
 from .. import ops
 from .augment import draw_play_batch_augmentation
-from .relay_replay import augment_specs
-from .replay import PlayIndex, _is_table
-
-DRAW_KEYS = ("idx", "window_size", "strategy", "disp", "noise_step", "u_choice", "u_random_state")
+from .replay import PlayIndex
+from .resident import (FrameDataModule, ResidentLoader, ResidentReplay, index_tables, is_table, neighbour_tables,
+                       resident_frames, validate_episodes)
 
 
 def validate_play_tables(index, n_frames):
@@ -34,10 +33,7 @@ def validate_play_tables(index, n_frames):
         raise ValueError(f"play replay: min_window_size {index.min_ws} < 1")
     if n_frames < index.max_ws:
         raise ValueError(f"play replay: {n_frames} frames hold no window of {index.max_ws}")
-    if ep.min() < 0 or ep.max() >= n_frames:
-        raise ValueError(f"play replay: episode bounds outside [0, {n_frames})")
-    if (ep[:, 0] > ep[:, 1]).any() or (ep[1:, 0] <= ep[:-1, 1]).any():
-        raise ValueError("play replay: episodes must be sorted by start and must not overlap")
+    validate_episodes(ep, n_frames, what="play replay: ")
     look = np.asarray(index.episode_lookup, dtype=np.int64)
     if len(look) == 0:
         raise ValueError("play replay: the index has no item")
@@ -54,84 +50,36 @@ def validate_play_tables(index, n_frames):
         raise ValueError("play replay: the neighbour CSR is not a row pointer over its values")
 
 
-class HbmPlayReplay:
-    """The play-window batches out of a dataset resident in HBM: frames[cam] = (N,H,W,3) uint8, the (N,A) action table and
-    the index tables (episode_lookup, the episode bounds, the neighbour CSR) all live on the device, and `batch()` is one
-    launch of the sampler kernel (`tacorl_sample_play_windows`) on the current stream - no host synchronisation, nothing
-    over PCIe, no feeder thread.  The tables are validated here, once (validate_play_tables).
-    The returned tensors are views of this object's own buffers, a ring of `slots` sets (as HbmTransitionReplay's): a batch
-    stays valid until `slots - 1` more have been drawn, so a trainer that fetches a batch or two ahead of the step it runs
-    still trains on the batch it was given.
+class HbmPlayReplay(ResidentReplay):
+    """The play-window batches out of a dataset resident in HBM (data/resident.py ResidentReplay): frames[cam] = (N,H,W,3)
+    uint8, the (N,A) action table and the index tables (episode_lookup, the episode bounds, the neighbour CSR) all live on the
+    device, and `batch()` is one launch of the sampler kernel (`tacorl_sample_play_windows`) on the current stream - no host
+    synchronisation, nothing over PCIe, no feeder thread.  The tables are validated here, once (validate_play_tables); the
+    dataset is as long as its shortest table.
     include_goal=False (PlayLMP's dataset, config/datamodule/dataset/play_dataset.yaml): the batch carries no `goal` and no
     `disp`, as the reference's."""
 
+    SUBJECT = "play replay"
+    DRAWS = {"idx": np.int64, "window_size": np.int64, "strategy": np.int64, "disp": np.int64, "noise_step": np.int64,
+             "u_choice": np.float64, "u_random_state": np.float64}
+
     def __init__(self, frames, actions, index, device=None, batch_size=64, slots=6, include_goal=True):
-        acts = torch.as_tensor(np.asarray(actions, dtype=np.float32) if not torch.is_tensor(actions) else actions)
-        frames = {c: torch.as_tensor(v) for c, v in frames.items()}
-        self.dev =torch.device(device) if device is not None else (next(iter(frames.values())).device if frames else acts.device)
-        self.index, self.batch_size, self.include_goal = index, int(batch_size), bool(include_goal)
-        bad = [c for c, v in frames.items() if v.dtype != torch.uint8 or v.dim() != 4]
-        if bad or acts.dim() != 2:
-            raise ValueError(f"frames must be uint8 (N,H,W,3) and actions (N,A): {bad or tuple(acts.shape)}")
-        n_frames = min([int(v.shape[0]) for v in frames.values()] + [int(acts.shape[0])])
+        dev = torch.device(device if device is not None else torch.as_tensor(next(iter(frames.values()), actions)).device)
+        self.frames, acts, n_frames = resident_frames(frames, actions, dev)
         validate_play_tables(index, n_frames)
-        if int(slots) < 1:
-            raise ValueError("slots must be >= 1")
-        self.frames = {c: v.to(self.dev).contiguous() for c, v in frames.items()}
-        acts = acts.to(self.dev, torch.float32).contiguous()
-        i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)  # noqa: E731
-        tab = index.nn_table
-        if tab is not None and tab.val.numel() and tab.device == torch.empty(0, device=self.dev).device:
-            # a NeighbourTable built on this device: its tensors are the sampler's tables (ptr cut as the index keeps it)
-            nn_ptr, nn_val = tab.ptr[: len(index._nn_ptr)], tab.val
-        else:
-            nn_ptr, nn_val = i64(index._nn_ptr), i64(index._nn_val if len(index._nn_val) else [0])
-        self.tables = {"lookup": i64(index.episode_lookup), "ep_start": i64(index.ep[:, 0]), "ep_end": i64(index.ep[:, 1]),
-                       "nn_ptr": nn_ptr, "nn_val": nn_val, "actions": acts, "n_nn": len(index._nn_ptr) - 1,
+        super().__init__(dev, index, batch_size, slots)
+        self.include_goal = bool(include_goal)
+        self.tables = {**index_tables(dev, index, lookup=index.episode_lookup), **neighbour_tables(index, dev), "actions": acts,
                        "n_frames": n_frames, "last_end": int(index.ep[:, 1].max())}
         self.A, self.T = int(acts.shape[1]), index.max_ws
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self._cap, self._ring, self._k, self._u8 = 0, [{} for _ in range(int(slots))], 0, {}
         self._grow(self.batch_size)
 
-    def _grow(self, B):
-        """The batch buffers exist before the first batch and are replaced only for a larger one - under the capture lock,
-        and captured graphs that could hold an old address are dropped (as HbmD4RLReplay._grow)."""
-        if B <= self._cap:
-            return
-        z = lambda n, dt: torch.zeros(n, dtype=dt, device=self.dev)  # noqa: E731
-        with ops.capture_lock:
-            for k in range(len(self._ring)):
-                self._ring[k] = {"ids": z(B * self.T + B, torch.int64), "act": z(B * self.T * self.A, torch.float32),
-                                 "disp": z(B, torch.int64), "window_size": z(B, torch.int64)}
-            self._cap = B
-            ops.note_alloc()
-
-    def _out(self, key, shape):
-        n = int(np.prod(shape))
-        t = self._u8.get(key)
-        if t is None or t.numel() < n:
-            with ops.capture_lock:
-                t = self._u8[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
-                ops.note_alloc()
-        return t[:n].view(shape)
-
-    def check(self):
-        """Reads the sampler's status word back (a host synchronisation: call it when you ask, not per step)."""
-        if int(self.status.item()) != 0:
-            raise IndexError("play replay: the sampler had to clamp a value (tables or draws outside the dataset)")
+    def _slot(self, B):
+        return {"ids": (B * self.T + B, torch.int64), "act": (B * self.T * self.A, torch.float32), "disp": (B, torch.int64),
+                "window_size": (B, torch.int64)}
 
     def _draws(self, draws, batch_size=None):
-        if draws is None:
-            return self.index.draw_device(batch_size or self.batch_size, self.dev)
-        d = {}
-        for k in DRAW_KEYS:
-            if k not in draws:
-                raise KeyError(f"play replay: the draws have no `{k}` (PlayIndex.draw_device, or draw() plus `idx`)")
-            v = draws[k]
-            if not torch.is_tensor(v):  # the host form (PlayIndex.draw): a pageable copy - tests and tools, not the training path
-                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64 if k.startswith("u_") else np.int64))
-            d[k] = v.to(self.dev).contiguous()
+        d = super()._draws(draws, batch_size)
         if self.index.min_ws == self.index.max_ws:  # the window is no draw (PlayIndex.sample ignores it too)
             d["window_size"] = self.index.device_constants(int(d["idx"].numel()), self.dev)[0]
         return d
@@ -145,9 +93,7 @@ class HbmPlayReplay:
         Both: `actions` (B,T,A) f32, `disp`, `idx`, `window_size` (B) int64 on the device, and `aug` where given."""
         d = self._draws(draws, batch_size)
         B, T = int(d["idx"].numel()), self.T
-        self._grow(B)
-        self._k = slot = (self._k + 1) % len(self._ring)
-        buf = self._ring[slot]
+        slot, buf = self._next(B)
         ids, act = buf["ids"][: B * T + B], buf["act"][: B * T * self.A].view(B, T, self.A)
         disp, ws = buf["disp"][:B], buf["window_size"][:B]
         ops.sample_play_windows(self.tables, d, T, self.index.min_ws, ids, act, disp, ws, self.status,
@@ -172,115 +118,62 @@ class HbmPlayReplay:
         return b
 
 
-class PlayWindowLoader:
-    """`steps_per_epoch` batches of `batch_size` fresh device draws per pass: what Trainer.fit takes as train_dataloaders /
-    val_dataloaders for TACORL and PlayLMP (the counterpart of RelayLoader).  A training batch carries
-    draw_play_batch_augmentation(aug_specs, ...); train=False (validation) draws none.  A batch is views of the replay's ring
-    of buffers (HbmPlayReplay(slots=6)): a trainer may hold up to `slots - 1` batches ahead of the one it runs."""
+class PlayWindowLoader(ResidentLoader):
+    """The loader of TACORL and PlayLMP (data/resident.py ResidentLoader) over an HbmPlayReplay: a training batch carries
+    draw_play_batch_augmentation(aug_specs, ...), one draw per frame of the window and one for the goal frame."""
 
-    def __init__(self, replay, batch_size, steps_per_epoch, aug_specs=None, generator=None, train=True, fused=True):
-        self.replay, self.batch_size, self.steps_per_epoch = replay, int(batch_size), int(steps_per_epoch)
-        self.aug_specs, self.generator, self.train, self.fused = aug_specs, generator, train, fused
-
-    def __len__(self):
-        return self.steps_per_epoch
-
-    def __iter__(self):
-        rp = self.replay
-        for _ in range(self.steps_per_epoch):
-            draws = rp.index.draw_device(self.batch_size, rp.dev, self.generator)
-            aug = None
-            if self.train and self.aug_specs:
-                aug = draw_play_batch_augmentation(self.aug_specs, self.batch_size, rp.T, rp.dev, self.generator)
-            yield rp.batch(draws, aug=aug, fused=self.fused)
+    def _augment(self, rp):
+        return draw_play_batch_augmentation(self.aug_specs, self.batch_size, rp.T, rp.dev, self.generator)
 
 
 _INDEX_KEYS = ("min_window_size", "max_window_size", "goal_sampling_prob", "goal_strategy_prob", "goal_augmentation")
-_DATASET_KEYS = _INDEX_KEYS + ("pad", "include_goal", "nn_steps_from_step", "nn_steps_from_step_val", "nn_steps_from_step_path",
-                               "path", "arrays")
-_DATASET_UNUSED = ("_target_", "_recursive_", "modalities", "action_type", "n_digits", "transf_type", "transform_manager",
-                   "num_nn", "real_world", "skip_frames", "data_dir", "train")
 
 
-class PlayDataModule:
+class PlayDataModule(FrameDataModule):
     """Drop-in for the reference's BasicDataModule with the PlayDataset configs (config/datamodule/{tacorl,play_lmp}.yaml with
-    dataset/{tacorl,play_dataset}.yaml): `Trainer.fit(model, datamodule=dm)`.  `dataset` is the reference's dataset config
-    (min_window_size, max_window_size, pad, include_goal, goal_sampling_prob, goal_strategy_prob, goal_augmentation) plus
-    where the data is: `path`, an .npz with `frames/<camera>` (N,H,W,3) uint8, `actions` (N,A) and the episode tables
-    `ep_start_end_ids_train` / `ep_start_end_ids_val` over those N frames, or `arrays`, a dict of the same.
+    dataset/{tacorl,play_dataset}.yaml; data/resident.py FrameDataModule says what the two frame datamodules share).  `dataset`
+    is the reference's dataset config (min_window_size, max_window_size, pad, include_goal, goal_sampling_prob,
+    goal_strategy_prob, goal_augmentation) plus `path` or `arrays`; n_frames is what the cameras and the action table hold.
     include_goal false (PlayLMP's play_dataset.yaml): the batch has no `goal` and no `disp`, and no neighbour table is read.
     `nn_steps_from_step` (here or in `dataset`; `nn_steps_from_step_val` for the validation split): a NeighbourTable
     (data/neighbours.py), the reference's dict {step: [steps]}, or the path of the reference's JSON file, read with
     NeighbourTable.load_json ("train" / "validation"); the config's `nn_steps_from_step_path` is read the same way where it
     names an existing file and no table was given.  Without a table a similar_robot_obs goal is the reference's fallback, a
-    random state.  train_percentage / val_percentage keep the first int(len * p) items (BasicDataModule's Subset);
-    val_percentage 0: no validation loader.  pad must be true: the reference cannot collate unpadded windows of varying
-    length either.  `_target_`, `modalities`, `action_type`, `n_digits`, `transf_type`, `num_nn`, `real_world`, `num_workers`,
-    `pin_memory`, `shuffle_val`, `data_dir` are accepted and unused: the dataset is resident and a batch is one kernel launch.
-    transform_manager: the `rl` form (see relay_replay.augment_specs); its train list becomes the train loader's
-    augmentation, a Resize to the stored size is no stage, and validation batches carry no augmentation - the frames must be
-    stored at the size the validation list resizes to.
-    steps_per_epoch defaults to len(train index) // batch_size; batches are fresh i.i.d. device draws with replacement
-    (PlayIndex.draw_device), not the reference's shuffled pass without replacement.  Validation batches are device draws
-    like the training ones (as RILDataModule's): the reference chooses a validation window size with hash(str(idx)), which
-    Python salts per process, so its validation set is not reproducible from run to run even there."""
+    random state.  pad must be true: the reference cannot collate unpadded windows of varying length either.  `_target_`,
+    `modalities`, `action_type`, `n_digits`, `transf_type`, `num_nn`, `real_world`, `num_workers`, `pin_memory`, `shuffle_val`,
+    `data_dir` are accepted and unused: the dataset is resident and a batch is one kernel launch.
+    Validation batches are device draws like the training ones (as RILDataModule's): the reference chooses a validation
+    window size with hash(str(idx)), which Python salts per process, so its validation set is not reproducible from run to
+    run even there."""
+
+    DATASET_KEYS = _INDEX_KEYS + ("pad", "include_goal", "nn_steps_from_step", "nn_steps_from_step_val", "nn_steps_from_step_path")
+    DATASET_UNUSED = ("_target_", "_recursive_", "modalities", "action_type", "n_digits", "transf_type", "transform_manager",
+                      "num_nn", "real_world", "skip_frames", "data_dir", "train")
+    LOADER = PlayWindowLoader
 
     def __init__(self, dataset, batch_size=64, train_percentage=1.0, val_percentage=1.0, transform_manager=None,
                  steps_per_epoch=None, val_steps=None, num_workers=4, pin_memory=True, shuffle_val=False, data_dir=None,
                  create_vis_dataset=False, nn_steps_from_step=None, nn_steps_from_step_val=None, device=None, fused=True,
                  generator=None, slots=6, **unused):
-        bad = [k for k in unused if k not in ("_target_", "_recursive_")]
-        if bad:
-            raise TypeError(f"PlayDataModule: unknown settings {bad}")
         if create_vis_dataset:
             raise NotImplementedError("PlayDataModule: create_vis_dataset is not built")
-        self.dataset_cfg, self.batch_size = dict(dataset), int(batch_size)
-        self.train_percentage, self.val_percentage = float(train_percentage), float(val_percentage)
-        self.transform_manager, self.steps_per_epoch, self.val_steps = transform_manager, steps_per_epoch, val_steps
-        self.device, self.fused, self.generator, self.slots = device, fused, generator, slots
-        c = self.dataset_cfg
-        unknown = [k for k in c if k not in _DATASET_KEYS + _DATASET_UNUSED]
-        if unknown:
-            raise TypeError(f"PlayDataModule: unknown dataset settings {unknown}")
-        if ("path" in c) == ("arrays" in c):
-            raise ValueError("PlayDataModule: give the dataset as `path` (an .npz) or as `arrays`")
-        if not c.get("pad", True):
+        if not dict(dataset).get("pad", True):
             raise NotImplementedError("PlayDataModule: pad=false (windows of varying length cannot be collated)")
-        for p, name in ((self.train_percentage, "train_percentage"), (self.val_percentage, "val_percentage")):
-            if not 0.0 <= p <= 1.0:
+        for p, name in ((train_percentage, "train_percentage"), (val_percentage, "val_percentage")):
+            if not 0.0 <= float(p) <= 1.0:
                 raise ValueError(f"PlayDataModule: {name} {p} outside [0, 1]")
+        super().__init__(dataset, batch_size, train_percentage, val_percentage, transform_manager, steps_per_epoch, val_steps,
+                         device, fused, generator, slots, unused)
+        c = self.dataset_cfg
         self.include_goal = bool(c.get("include_goal", False))
         self.index_kwargs = {k: c[k] for k in _INDEX_KEYS if k in c}
         if "goal_strategy_prob" in self.index_kwargs:
             self.index_kwargs["goal_strategy_prob"] = dict(self.index_kwargs["goal_strategy_prob"])
         self._nn = {"train": nn_steps_from_step if nn_steps_from_step is not None else c.get("nn_steps_from_step"),
                     "validation": nn_steps_from_step_val if nn_steps_from_step_val is not None else c.get("nn_steps_from_step_val")}
-        self.cams = self._cameras()
-        self.aug_specs = augment_specs(self.transform_manager, self.cams, "train")  # (raises for what is not built)
-        self._val_specs = augment_specs(self.transform_manager, self.cams, "validation")
-        self.train_replay = self.val_replay = None
 
-    def _cameras(self):
-        c = self.dataset_cfg
-        if "arrays" in c:
-            a = c["arrays"]
-            fr = a["frames"] if "frames" in a else {k.split("/", 1)[1]: None for k in a if k.startswith("frames/")}
-            return sorted(fr)
-        with np.load(c["path"]) as z:
-            return sorted(k.split("/", 1)[1] for k in z.files if k.startswith("frames/"))
-
-    def _arrays(self):
-        c = self.dataset_cfg
-        if "arrays" in c:
-            a = c["arrays"]
-            frames = a["frames"] if "frames" in a else {k.split("/", 1)[1]: v for k, v in a.items() if k.startswith("frames/")}
-            return dict(frames), a["actions"], a["ep_start_end_ids_train"], a.get("ep_start_end_ids_val")
-        with np.load(c["path"]) as z:
-            missing = [k for k in ("actions", "ep_start_end_ids_train") if k not in z.files]
-            if missing or not self.cams:
-                raise KeyError(f"{c['path']}: no array named {missing or 'frames/<camera>'}")
-            return ({cam: z["frames/" + cam] for cam in self.cams}, z["actions"], z["ep_start_end_ids_train"],
-                    z["ep_start_end_ids_val"] if "ep_start_end_ids_val" in z.files else None)
+    def _n_frames(self, frames, acts):
+        return min([int(v.shape[0]) for v in frames.values()] + [int(acts.shape[0])])
 
     def _neighbours(self, split, n_frames, dev):
         """The split's nn_steps_from_step as PlayIndex takes it (a NeighbourTable or a dict), or None."""
@@ -301,7 +194,7 @@ class PlayDataModule:
                 if split == "train":
                     raise
                 return None
-        return nn.to(dev) if _is_table(nn) else nn
+        return nn.to(dev) if is_table(nn) else nn
 
     def _index(self, ep, percentage, split, n_frames, dev):
         ix = PlayIndex(ep, nn_steps_from_step=self._neighbours(split, n_frames, dev), train=split == "train", **self.index_kwargs)
@@ -310,53 +203,7 @@ class PlayDataModule:
             raise ValueError(f"PlayDataModule: the {split} index has no item (percentage {percentage})")
         return ix
 
-    def prepare_data(self, *args, **kwargs):
-        pass
+    def _replay(self, frames, acts, index, dev):
+        return HbmPlayReplay(frames, acts, index, device=dev, batch_size=self.batch_size, slots=self.slots,
+                             include_goal=self.include_goal)
 
-    def setup(self, stage=None):
-        if self.train_replay is not None:
-            return
-        from ..lightning import default_device
-
-        dev = torch.device(self.device if self.device is not None else default_device())  # one process per GPU
-        frames, actions, ep_train, ep_val = self._arrays()
-        frames = {c: torch.as_tensor(v).to(dev).contiguous() for c, v in frames.items()}  # both splits share the frames
-        acts = torch.as_tensor(np.asarray(actions, dtype=np.float32)).to(dev)
-        n = min([int(v.shape[0]) for v in frames.values()] + [int(acts.shape[0])])
-        for c, v in frames.items():
-            stored = tuple(v.shape[1:3])
-            sp, vs = self.aug_specs[c], self._val_specs[c]
-            if sp is not None and sp.resize == stored:
-                sp.resize = None
-            resized = [s.resize for s in (sp, vs) if s is not None and s.resize not in (None, stored)]
-            if resized and self.val_percentage > 0:
-                raise NotImplementedError(f"{c}: validation batches carry no resize - store the frames at {resized[0]}, not {stored}")
-        specs = {c: s for c, s in self.aug_specs.items() if s is not None and (s.resize is not None or s.pad or s.prob)}
-        self._train_specs = specs or None
-        kw = dict(device=dev, batch_size=self.batch_size, slots=self.slots, include_goal=self.include_goal)
-        ix = self._index(ep_train, self.train_percentage, "train", n, dev)
-        self.train_replay = HbmPlayReplay(frames, acts, ix, **kw)
-        self.index = ix
-        if self.val_percentage > 0:
-            if ep_val is None:
-                raise KeyError("PlayDataModule: val_percentage > 0 needs `ep_start_end_ids_val`")
-            vix = self._index(ep_val, self.val_percentage, "validation", n, dev)
-            self.val_replay = HbmPlayReplay(frames, acts, vix, **kw)
-            if self.val_steps is None:
-                self.val_steps = max(len(vix) // self.batch_size, 1)
-        if self.steps_per_epoch is None:
-            self.steps_per_epoch = len(ix) // self.batch_size
-        if int(self.steps_per_epoch) < 1:
-            raise ValueError(f"{len(ix)} items give no batch of {self.batch_size}")
-
-    def train_dataloader(self):
-        self.setup()
-        return PlayWindowLoader(self.train_replay, self.batch_size, self.steps_per_epoch, aug_specs=self._train_specs,
-                                generator=self.generator, fused=self.fused)
-
-    def val_dataloader(self):
-        self.setup()
-        if self.val_replay is None:
-            return None
-        return PlayWindowLoader(self.val_replay, self.batch_size, self.val_steps, generator=self.generator, train=False,
-                                fused=self.fused)

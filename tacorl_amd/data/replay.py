@@ -15,13 +15,11 @@ import numpy as np
 import torch
 
 from .. import ops
+from .augment import draw_transition_batch_augmentation
+from .resident import (ResidentLoader, ResidentReplay, episode_end, index_tables, neighbour_csr, neighbour_tables, pick,
+                       resident_frames, validate_episodes)
 
 GEOMETRIC, SIMILAR = 0, 1
-
-
-def _is_table(nn_steps_from_step):
-    """A neighbours.NeighbourTable (the CSR itself) rather than the reference's dict {step: [steps]}."""
-    return hasattr(nn_steps_from_step, "index_csr")
 
 
 class PlayIndex:
@@ -39,19 +37,7 @@ class PlayIndex:
         self.goal_augmentation = bool(goal_augmentation)
         # the ragged neighbour lists as one CSR table indexed by frame id (a python loop over half the batch was the
         # sampler's hot spot: 180 us per 256-sample batch, a fifth of the device step)
-        self.nn_table = nn_steps_from_step if _is_table(nn_steps_from_step) else None
-        if self.nn_table is not None:
-            # a NeighbourTable (data/neighbours.py) is that CSR already: adopted as it stands, no loop over its keys
-            self.nn = None
-            self._nn_ptr, self._nn_val = self.nn_table.index_csr()
-        else:
-            self.nn = {int(k): np.asarray(v, dtype=np.int64) for k, v in (nn_steps_from_step or {}).items()}
-            top = (max(self.nn) + 1) if self.nn else 0
-            cnt = np.zeros(top, dtype=np.int64)
-            for k, v in self.nn.items():
-                cnt[k] = len(v)
-            self._nn_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-            self._nn_val = (np.concatenate([self.nn[k] for k in sorted(self.nn)]) if self.nn else np.zeros(0, np.int64))
+        self.nn_table, self.nn, self._nn_ptr, self._nn_val = neighbour_csr(nn_steps_from_step)  # (nothing is validated here)
         # load_file_indices (:452-473): every start frame that leaves room for a max-size window
         look = []
         for s, e in self.ep:
@@ -105,10 +91,7 @@ class PlayIndex:
 
     def episode_end(self, step):
         """find_episode_end (:238-242): end (inclusive) of the first episode with start <= step <= end, -1 if none."""
-        step = np.asarray(step)
-        k = np.searchsorted(self.ep[:, 0], step, side="right") - 1
-        ok = (k >= 0) & (step <= self.ep[np.maximum(k, 0), 1])
-        return np.where(ok, self.ep[np.maximum(k, 0), 1], -1)
+        return episode_end(self.ep, step, missing=-1)
 
     def sample(self, idx, d):
         """idx (n,) dataset indices; d = draw(...).  Returns frame ids (n, max_ws) padded by repetition of the last
@@ -471,38 +454,13 @@ class TransitionIndex:
         self.p_geom_goal = float(goal_sampling_prob)
         self.initial_horizon, self.horizon_step, self.max_horizon = int(initial_horizon), int(horizon_step), int(max_horizon)
         self.current_horizon = self.initial_horizon
-        self.ep = np.asarray(ep_start_end_ids, dtype=np.int64).reshape(-1, 2)
-        if len(self.ep) == 0:
-            raise ValueError("no episodes")
-        self.n_frames = int(n_frames) if n_frames is not None else int(self.ep[:, 1].max()) + 1
-        if self.ep.min() < 0 or self.ep.max() >= self.n_frames:
-            raise ValueError(f"episode bounds outside [0, {self.n_frames})")
-        if (self.ep[:, 0] > self.ep[:, 1]).any() or (self.ep[1:, 0] <= self.ep[:-1, 1]).any():
-            raise ValueError("episodes must be sorted by start and must not overlap")
+        self.ep, self.n_frames = validate_episodes(ep_start_end_ids, n_frames)
         # set_possible_steps (:174-178): every step but the episodes' end steps, so step + 1 always exists
         self.possible_steps = np.concatenate([np.arange(s, e) for s, e in self.ep])
         if len(self.possible_steps) < 2:
             raise ValueError("fewer than two possible steps: the `random` strategy has nothing to choose from")
-        self.nn_table = nn_steps_from_step if _is_table(nn_steps_from_step) else None
-        if self.nn_table is not None:
-            # a NeighbourTable (data/neighbours.py): its CSR is adopted as it stands and validated as arrays
-            self.nn = None
-            self._nn_ptr, self._nn_val = self.nn_table.index_csr()
-            keys = self.nn_table.host()[2]
-            if (len(keys) and (keys.min() < 0 or keys.max() >= self.n_frames)) or \
-                    (len(self._nn_val) and (self._nn_val.min() < 0 or self._nn_val.max() >= self.n_frames)):
-                raise ValueError(f"nn_steps_from_step: a step outside [0, {self.n_frames})")
-        else:
-            self.nn = {int(k): np.asarray(v, dtype=np.int64).reshape(-1) for k, v in (nn_steps_from_step or {}).items()}
-            for k, v in self.nn.items():
-                if not 0 <= k < self.n_frames or (len(v) and (v.min() < 0 or v.max() >= self.n_frames)):
-                    raise ValueError(f"nn_steps_from_step[{k}]: a step outside [0, {self.n_frames})")
-            top = (max(self.nn) + 1) if self.nn else 0
-            cnt = np.zeros(top, dtype=np.int64)
-            for k, v in self.nn.items():
-                cnt[k] = len(v)
-            self._nn_ptr = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
-            self._nn_val = np.concatenate([self.nn[k] for k in sorted(self.nn)] + [np.zeros(0, np.int64)]).astype(np.int64)
+        # a dict is validated key by key, a NeighbourTable (data/neighbours.py) as the arrays of its CSR
+        self.nn_table, self.nn, self._nn_ptr, self._nn_val = neighbour_csr(nn_steps_from_step, self.n_frames)
 
     def __len__(self):
         return len(self.possible_steps)
@@ -540,16 +498,14 @@ class TransitionIndex:
                 "u_choice": torch.rand(n, device=dev, generator=g, dtype=torch.float64)}
 
     def episode_end(self, step):
-        """find_episode_end (:203-207) by binary search: the end of the episode with start <= step <= end."""
-        k = np.maximum(np.searchsorted(self.ep[:, 0], np.asarray(step), side="right") - 1, 0)
-        return self.ep[k, 1]
+        """find_episode_end (:203-207): the end of the episode with start <= step <= end."""
+        return episode_end(self.ep, step)
 
     def sample(self, idx, d):
         """idx (n,) items (None: d["idx"]); d = draw(...).  Returns step, next (= step + 1), goal frame ids, reward, done."""
         idx = np.asarray(d["idx"] if idx is None else idx, dtype=np.int64)
         strat, disp = np.asarray(d["strategy"], dtype=np.int64), np.asarray(d["disp"], dtype=np.int64)
         u = np.asarray(d["u_choice"], dtype=np.float64)
-        pick = lambda n: np.clip((u * n).astype(np.int64), 0, np.maximum(n - 1, 0))  # noqa: E731  floor(u n) in [0, n)
         step = self.possible_steps[idx]
         end = self.episode_end(step)
         goal = step + 1  # next_state
@@ -560,93 +516,47 @@ class TransitionIndex:
         lo = self._nn_ptr[kc] if len(self._nn_ptr) > 1 else np.zeros(len(idx), np.int64)
         cnt = np.where(inside, self._nn_ptr[np.minimum(kc + 1, len(self._nn_ptr) - 1)] - lo, 0)
         if len(self._nn_val):
-            goal = np.where((strat == S_SIMILAR) & (cnt > 0), self._nn_val[np.minimum(lo + pick(cnt), len(self._nn_val) - 1)], goal)
+            goal = np.where((strat == S_SIMILAR) & (cnt > 0), self._nn_val[np.minimum(lo + pick(u, cnt), len(self._nn_val) - 1)], goal)
         # increasing_horizon / episode_future: uniform over [step + 1, last] (get_random_future_step, :216-222)
         last = np.where((strat == S_HORIZON) & (self.current_horizon < end - step), step + self.current_horizon, end)
         future = (strat == S_HORIZON) | (strat == S_EPISODE)
-        goal = np.where(future & (last > step), step + 1 + pick(last - step), goal)
+        goal = np.where(future & (last > step), step + 1 + pick(u, last - step), goal)
         # random, and the reference's fallback to it: possible_steps without `step`, the removal as an index shift
         fallback = (strat == S_RANDOM) | ((strat == S_SIMILAR) & (cnt == 0)) | (future & (last <= step))
-        j = pick(np.full(len(idx), len(self) - 1))
+        j = pick(u, np.full(len(idx), len(self) - 1))
         goal = np.where(fallback, self.possible_steps[j + (j >= idx)], goal)
         r = (goal == step + 1).astype(np.int64)
         return {"step": step, "next": step + 1, "goal": goal, "reward": r, "done": r.copy(), "idx": idx}
 
 
-class HbmTransitionReplay:
-    """CQL_Offline's transition batches out of a dataset resident in HBM: frames[cam] = (N,H,W,3) uint8, the (N,A) action
-    table and the index tables all live on the device, and `batch()` is one launch of the sampler kernel
-    (`tacorl_sample_transitions`) on the current stream - no host synchronisation, nothing over PCIe.
-    The returned tensors are views of this object's own buffers, a ring of `slots` sets (as HbmReplay's staging ring): a
-    batch stays valid until `slots - 1` more have been drawn, so a trainer that fetches a batch or two ahead of the step
-    it runs (pytorch_lightning looks one ahead to learn which batch is the last) still trains on the batch it was given."""
+class HbmTransitionReplay(ResidentReplay):
+    """CQL_Offline's transition batches out of a dataset resident in HBM (data/resident.py ResidentReplay): frames[cam] =
+    (N,H,W,3) uint8, the (N,A) action table and the index tables all live on the device, and `batch()` is one launch of the
+    sampler kernel (`tacorl_sample_transitions`) on the current stream - no host synchronisation, nothing over PCIe."""
+
+    SUBJECT = "transition replay"
+    DRAWS = {"idx": np.int64, "strategy": np.int64, "disp": np.int64, "u_choice": np.float64}
 
     def __init__(self, frames, actions, index, device=None, batch_size=256, slots=6):
-        self.dev = torch.device(device) if device is not None else next(iter(frames.values())).device
-        self.index, self.batch_size = index, int(batch_size)
-        self.frames = {c: v.to(self.dev).contiguous() for c, v in frames.items()}
-        acts = torch.as_tensor(np.asarray(actions, dtype=np.float32) if not torch.is_tensor(actions) else actions)
-        acts = acts.to(self.dev, torch.float32).contiguous()
-        short = [c for c, v in self.frames.items() if v.dtype != torch.uint8 or v.dim() != 4 or v.shape[0] < index.n_frames]
-        if short or acts.dim() != 2 or acts.shape[0] < index.n_frames:
-            raise ValueError(f"frames (uint8 (N,H,W,3)) and actions (N,A) must cover the index's {index.n_frames} frames")
-        i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.dev)  # noqa: E731
-        tab = getattr(index, "nn_table", None)
-        if tab is not None and tab.val.numel() and tab.device == torch.empty(0, device=self.dev).device:
-            # a NeighbourTable built on this device: its tensors are the sampler's tables (ptr cut as the index keeps it)
-            nn_ptr, nn_val = tab.ptr[: len(index._nn_ptr)], tab.val
-        else:
-            nn_ptr, nn_val = i64(index._nn_ptr), i64(index._nn_val if len(index._nn_val) else [0])
-        self.tables = {"steps": i64(index.possible_steps), "ep_start": i64(index.ep[:, 0]), "ep_end": i64(index.ep[:, 1]),
-                       "nn_ptr": nn_ptr, "nn_val": nn_val,
-                       "actions": acts, "n_nn": len(index._nn_ptr) - 1, "n_frames": index.n_frames}
+        super().__init__(device if device is not None else next(iter(frames.values())).device, index, batch_size, slots)
+        self.frames, acts, _ = resident_frames(frames, actions, self.dev, cover=index.n_frames)
+        self.tables = {**index_tables(self.dev, index, steps=index.possible_steps), **neighbour_tables(index, self.dev),
+                       "actions": acts, "n_frames": index.n_frames}
         self.A = int(acts.shape[1])
-        self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        if int(slots) < 1:
-            raise ValueError("slots must be >= 1")
-        self._cap, self._ring, self._k, self._u8 = 0, [{} for _ in range(int(slots))], 0, {}
         self._grow(self.batch_size)
 
-    def _grow(self, B):
-        """The batch buffers exist before the first batch and are replaced only for a larger one - under the capture lock,
-        and captured graphs that could hold an old address are dropped (as _PinnedRing.put_all)."""
-        if B <= self._cap:
-            return
-        with ops.capture_lock:
-            for k in range(len(self._ring)):
-                self._ring[k] = {"ids": torch.zeros(3 * B, dtype=torch.int64, device=self.dev),
-                                 "action": torch.zeros(B * self.A, device=self.dev), "reward": torch.zeros(B, device=self.dev),
-                                 "done": torch.zeros(B, device=self.dev)}
-            self._cap = B
-            ops.note_alloc()
-
-    def _out(self, key, shape):
-        n = int(np.prod(shape))
-        t = self._u8.get(key)
-        if t is None or t.numel() < n:
-            with ops.capture_lock:
-                t = self._u8[key] = torch.empty(n, dtype=torch.uint8, device=self.dev)
-                ops.note_alloc()
-        return t[:n].view(shape)
-
-    def check(self):
-        """Reads the sampler's status word back (a host synchronisation: call it when you ask, not per step)."""
-        if int(self.status.item()) != 0:
-            raise IndexError("transition replay: the sampler had to clamp a frame id (tables or draws outside the dataset)")
+    def _slot(self, B):
+        f32 = torch.float32
+        return {"ids": (3 * B, torch.int64), "action": (B * self.A, f32), "reward": (B, f32), "done": (B, f32)}
 
     def batch(self, draws=None, aug=None, fused=True, batch_size=None):
         """draws: TransitionIndex.draw_device(...) (None: drawn here for `batch_size`), or the host form `draw(...)`.
         fused=True: no frame moves here - the batch carries the dataset tensors and the id table [step | step+1 | goal]
         (`batch["replay"]`), and CQL_Offline's image pack reads the frames by index on their way into the encoders.
         fused=False: the reference dataset's schema with the uint8 frames gathered (tacorl_gather_frames_u8)."""
-        if draws is None:
-            draws = self.index.draw_device(batch_size or self.batch_size, self.dev)
-        d = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))).to(self.dev).contiguous()
-             for k, v in draws.items() if k in ("idx", "strategy", "disp", "u_choice")}
+        d = self._draws(draws, batch_size)
         B = int(d["idx"].numel())
-        self._grow(B)
-        self._k = slot = (self._k + 1) % len(self._ring)
-        buf = self._ring[slot]
+        slot, buf = self._next(B)
         ids = buf["ids"][: 3 * B].view(3, B)
         act, rew, done = buf["action"][: B * self.A].view(B, self.A), buf["reward"][:B], buf["done"][:B]
         ops.sample_transitions(self.tables, d, self.index.current_horizon, ids, act, rew, done, self.status)
@@ -666,25 +576,9 @@ class HbmTransitionReplay:
         return b
 
 
-class TransitionLoader:
-    """`steps_per_epoch` batches of `batch_size` fresh device draws per pass: what Trainer.fit takes as train_dataloaders /
-    val_dataloaders for CQL_Offline.  train=False (validation) draws no augmentation.  A batch is views of the replay's ring
-    of buffers (HbmTransitionReplay(slots=6)): a trainer may hold up to `slots - 1` batches ahead of the one it is running."""
+class TransitionLoader(ResidentLoader):
+    """The loader of CQL_Offline (data/resident.py ResidentLoader) over an HbmTransitionReplay."""
 
-    def __init__(self, replay, batch_size, steps_per_epoch, aug_specs=None, generator=None, train=True, fused=True):
-        self.replay, self.batch_size, self.steps_per_epoch = replay, int(batch_size), int(steps_per_epoch)
-        self.aug_specs, self.generator, self.train, self.fused = aug_specs, generator, train, fused
+    def _augment(self, rp):
+        return draw_transition_batch_augmentation(self.aug_specs, self.batch_size, rp.dev, self.generator)
 
-    def __len__(self):
-        return self.steps_per_epoch
-
-    def __iter__(self):
-        from .augment import draw_transition_batch_augmentation
-
-        rp = self.replay
-        for _ in range(self.steps_per_epoch):
-            draws = rp.index.draw_device(self.batch_size, rp.dev, self.generator)
-            aug = None
-            if self.train and self.aug_specs:
-                aug = draw_transition_batch_augmentation(self.aug_specs, self.batch_size, rp.dev, self.generator)
-            yield rp.batch(draws, aug=aug, fused=self.fused)

@@ -334,7 +334,20 @@ class GraphMixin:
         capture(s) of the step for later calls."""
         eager()  # warm-up: sizes every workspace, so the capture allocates nothing
         torch.cuda.synchronize()
-        self._capture_only(key, segs, collectives, side)
+        # Python's cyclic collector stays out of the capture: a dead module's graphs, streams and buffers sit in reference
+        # cycles (the closures of its step), and a collection that falls inside the capture runs their finalisers - HIP calls
+        # - on the capturing thread (the whole GPU suite in one process aborted that way; torch.cuda.graph no longer collects
+        # before it begins).  Only deferred, not forced: a gc.collect() here destroys the previous module's graphs at once,
+        # and with RCCL nodes captured in them (TACORL_GRAPH_COLLECTIVES=1) the next case of the one-rank test then crashed.
+        import gc
+
+        was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            self._capture_only(key, segs, collectives, side)
+        finally:
+            if was_enabled:
+                gc.enable()
 
     def _capture_only(self, key, segs, collectives, side):
         from .. import dist as D

@@ -297,24 +297,48 @@ def gather_frames_u8(frames, index, out):
     return out
 
 
+# ---- the samplers over resident tables (data/resident.py).  What their four wrappers check alike:
+def _all_dev(dtype, *ts):
+    """Every tensor is of `dtype`, on the device and contiguous."""
+    for t in ts:
+        if not (t.dtype == dtype and t.is_cuda and t.is_contiguous()):
+            return False
+    return True
+
+
+def _sampler_checks(tables, draws, B, tabs, i64, f64, status):
+    """Of a sampler call: the int64 tables `tabs`, the int64 and float64 draws (B each), the action table and the int32
+    status word.  (Plain loops: this runs once per batch on the trainer's thread.)"""
+    for k in tabs:
+        assert _all_dev(torch.int64, tables[k]), k
+    for k in i64:
+        assert _all_dev(torch.int64, draws[k]) and draws[k].numel() == B, k
+    for k in f64:
+        assert _all_dev(torch.float64, draws[k]) and draws[k].numel() == B, k
+    assert tables["ep_start"].numel() == tables["ep_end"].numel() and tables["actions"].shape[0] >= tables["n_frames"]
+    assert "nn_ptr" not in tables or tables["nn_ptr"].numel() == tables["n_nn"] + 1
+    _f32(tables["actions"])
+    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
+
+
+def _episode_args(tables, items):
+    """The leading arguments of every sampler: the item table and its length, the episode bounds and their number."""
+    return ptr(tables[items]), tables[items].numel(), ptr(tables["ep_start"]), ptr(tables["ep_end"]), tables["ep_start"].numel()
+
+
 def sample_transitions(tables, draws, current_horizon, ids, action, reward, done, status):
     """The transition sampler over resident tables (data/replay.py HbmTransitionReplay): tables = device tensors
     `steps`, `ep_start`, `ep_end`, `nn_ptr`, `nn_val` (int64), `actions` (N, A) f32 and the int `n_nn`, `n_frames`;
     draws = device `idx`, `strategy`, `disp` (int64) and `u_choice` (f64), B each.  Writes ids (3, B) int64
     [step | step+1 | goal], action (B, A), reward (B), done (B) f32 and raises the int32 `status` word on a clamped id."""
     B, A = ids.shape[1], tables["actions"].shape[1]
-    i64 = [tables[k] for k in ("steps", "ep_start", "ep_end", "nn_ptr", "nn_val")] + [draws[k] for k in ("idx", "strategy", "disp")]
-    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64 + [ids])
-    assert all(draws[k].numel() == B for k in ("idx", "strategy", "disp", "u_choice")) and ids.shape == (3, B)
-    assert draws["u_choice"].dtype == torch.float64 and draws["u_choice"].is_cuda and draws["u_choice"].is_contiguous()
-    assert tables["nn_ptr"].numel() == tables["n_nn"] + 1 and tables["actions"].shape[0] >= tables["n_frames"]
-    for t, n in ((_f32(tables["actions"]), None), (_f32(action), B * A), (_f32(reward), B), (_f32(done), B)):
-        assert n is None or t.numel() == n
-    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
-    call("tacorl_sample_transitions", ptr(tables["steps"]), tables["steps"].numel(), ptr(tables["ep_start"]), ptr(tables["ep_end"]),
-         tables["ep_start"].numel(), ptr(tables["nn_ptr"]), tables["n_nn"], ptr(tables["nn_val"]), ptr(tables["actions"]),
-         ptr(draws["idx"]), ptr(draws["strategy"]), ptr(draws["disp"]), ptr(draws["u_choice"]), int(current_horizon),
-         int(tables["n_frames"]), B, A, ptr(ids), ptr(action), ptr(reward), ptr(done), ptr(status), stream())
+    _sampler_checks(tables, draws, B, ("steps", "ep_start", "ep_end", "nn_ptr", "nn_val"), ("idx", "strategy", "disp"),
+                    ("u_choice",), status)
+    assert _all_dev(torch.int64, ids) and ids.shape == (3, B)
+    assert _f32(action).numel() == B * A and _f32(reward).numel() == B and _f32(done).numel() == B
+    call("tacorl_sample_transitions", *_episode_args(tables, "steps"), ptr(tables["nn_ptr"]), tables["n_nn"], ptr(tables["nn_val"]),
+         ptr(tables["actions"]), ptr(draws["idx"]), ptr(draws["strategy"]), ptr(draws["disp"]), ptr(draws["u_choice"]),
+         int(current_horizon), int(tables["n_frames"]), B, A, ptr(ids), ptr(action), ptr(reward), ptr(done), ptr(status), stream())
 
 
 def sample_relay(tables, draws, low_window, high_window, ids, action, status):
@@ -323,17 +347,11 @@ def sample_relay(tables, draws, low_window, high_window, ids, action, status):
     `u_high` (f64), B each.  Writes ids (4, B) int64 [obs | low_level_goal | high_level_goal | high_level_action] and
     action (B, A) f32, and raises the int32 `status` word on a clamped id."""
     B, A = ids.shape[1], tables["actions"].shape[1]
-    i64 = [tables[k] for k in ("lookup", "ep_start", "ep_end")] + [draws["idx"]]
-    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64 + [ids])
-    assert all(draws[k].numel() == B for k in ("idx", "u_low", "u_high")) and ids.shape == (4, B)
-    assert all(draws[k].dtype == torch.float64 and draws[k].is_cuda and draws[k].is_contiguous() for k in ("u_low", "u_high"))
-    assert tables["actions"].shape[0] >= tables["n_frames"] and tables["ep_start"].numel() == tables["ep_end"].numel()
-    for t, n in ((_f32(tables["actions"]), None), (_f32(action), B * A)):
-        assert n is None or t.numel() == n
-    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
-    call("tacorl_sample_relay", ptr(tables["lookup"]), tables["lookup"].numel(), ptr(tables["ep_start"]), ptr(tables["ep_end"]),
-         tables["ep_start"].numel(), ptr(tables["actions"]), int(tables["n_frames"]), ptr(draws["idx"]), ptr(draws["u_low"]),
-         ptr(draws["u_high"]), int(low_window), int(high_window), B, A, ptr(ids), ptr(action), ptr(status), stream())
+    _sampler_checks(tables, draws, B, ("lookup", "ep_start", "ep_end"), ("idx",), ("u_low", "u_high"), status)
+    assert _all_dev(torch.int64, ids) and ids.shape == (4, B) and _f32(action).numel() == B * A
+    call("tacorl_sample_relay", *_episode_args(tables, "lookup"), ptr(tables["actions"]), int(tables["n_frames"]),
+         ptr(draws["idx"]), ptr(draws["u_low"]), ptr(draws["u_high"]), int(low_window), int(high_window), B, A, ptr(ids),
+         ptr(action), ptr(status), stream())
 
 
 def sample_d4rl_windows(tables, draws, Tmax, G, min_window, threshold, obs, act, status, goal=None, reached=None, done=None,
@@ -344,18 +362,13 @@ def sample_d4rl_windows(tables, draws, Tmax, G, min_window, threshold, obs, act,
     done (B) f32, window_size (B) and ids (2, B) int64 = [start | goal_step]; raises the int32 `status` word on a clamp."""
     B = draws["idx"].numel()
     S, A = tables["observations"].shape[1], tables["actions"].shape[1]
-    i64 = [tables[k] for k in ("lookup", "ep_start", "ep_end")] + [draws[k] for k in ("idx", "window", "disp")]
-    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64)
-    assert all(draws[k].numel() == B for k in ("idx", "window", "disp"))
-    assert tables["observations"].shape[0] >= tables["n_frames"] and tables["actions"].shape[0] >= tables["n_frames"]
-    _f32(tables["observations"]), _f32(tables["actions"])
+    _sampler_checks(tables, draws, B, ("lookup", "ep_start", "ep_end"), ("idx", "window", "disp"), (), status)
+    assert _f32(tables["observations"]).shape[0] >= tables["n_frames"]
     for t, n in ((obs, B * Tmax * S), (act, B * Tmax * A), (goal, B * G), (reached, B), (done, B)):
         assert t is None or _f32(t).numel() == n, (None if t is None else tuple(t.shape), n)
     for t, n in ((window_size, B), (ids, 2 * B)):
-        assert t is None or (t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.numel() == n)
-    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
-    call("tacorl_sample_d4rl_windows", ptr(tables["lookup"]), tables["lookup"].numel(), ptr(tables["ep_start"]),
-         ptr(tables["ep_end"]), tables["ep_start"].numel(), ptr(tables["observations"]), ptr(tables["actions"]),
+        assert t is None or (_all_dev(torch.int64, t) and t.numel() == n)
+    call("tacorl_sample_d4rl_windows", *_episode_args(tables, "lookup"), ptr(tables["observations"]), ptr(tables["actions"]),
          int(tables["n_frames"]), ptr(draws["idx"]), ptr(draws["window"]), ptr(draws["disp"]), B, int(Tmax), S, A, int(G),
          int(min_window), float(threshold), ptr(obs), ptr(act), ptr(goal), ptr(reached), ptr(done), ptr(window_size), ptr(ids),
          ptr(status), stream())
@@ -369,19 +382,13 @@ def sample_play_windows(tables, draws, Tmax, min_window, ids, act, disp_out, win
     (B, Tmax, A) f32, disp_out (B) and window_size (B) int64; raises the int32 `status` word on a clamp."""
     B, A = draws["idx"].numel(), tables["actions"].shape[1]
     ints = ("idx", "window_size", "strategy", "disp") + (("noise_step",) if goal_augmentation else ())
-    i64 = [tables[k] for k in ("lookup", "ep_start", "ep_end", "nn_ptr", "nn_val")] + [draws[k] for k in ints]
-    assert all(t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() for t in i64 + [ids, disp_out, window_size])
-    assert all(draws[k].numel() == B for k in ints + ("u_choice", "u_random_state"))
-    assert all(draws[k].dtype == torch.float64 and draws[k].is_cuda and draws[k].is_contiguous() for k in ("u_choice", "u_random_state"))
+    _sampler_checks(tables, draws, B, ("lookup", "ep_start", "ep_end", "nn_ptr", "nn_val"), ints, ("u_choice", "u_random_state"),
+                    status)
+    assert _all_dev(torch.int64, ids, disp_out, window_size)
     assert ids.numel() == B * Tmax + B and disp_out.numel() == B and window_size.numel() == B
-    assert tables["nn_ptr"].numel() == tables["n_nn"] + 1 and tables["actions"].shape[0] >= tables["n_frames"]
-    assert tables["ep_start"].numel() == tables["ep_end"].numel()
-    _f32(tables["actions"])
     assert _f32(act).numel() == B * Tmax * A
-    assert status.dtype == torch.int32 and status.is_cuda and status.numel() == 1
     n_nn = int(tables["n_nn"])
-    call("tacorl_sample_play_windows", ptr(tables["lookup"]), tables["lookup"].numel(), ptr(tables["ep_start"]),
-         ptr(tables["ep_end"]), tables["ep_start"].numel(), ptr(tables["nn_ptr"]) if n_nn else None, n_nn,
+    call("tacorl_sample_play_windows", *_episode_args(tables, "lookup"), ptr(tables["nn_ptr"]) if n_nn else None, n_nn,
          ptr(tables["nn_val"]) if n_nn else None, ptr(tables["actions"]), int(tables["n_frames"]), int(tables["last_end"]),
          ptr(draws["idx"]), ptr(draws["window_size"]), ptr(draws["strategy"]), ptr(draws["disp"]),
          ptr(draws["noise_step"]) if goal_augmentation else None, ptr(draws["u_choice"]), ptr(draws["u_random_state"]), B,
