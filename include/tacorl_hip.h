@@ -860,6 +860,31 @@ int tacorl_rows_linear2_fwd(const float* x1, int ldx1, int K1, const float* w1, 
                             int K2, const float* w2, const float* b2, const unsigned char* x2_row_is_zero, float* y, int ldy,
                             int R, int N, int act, tacorl_stream_t stream);
 
+/* A whole MLP chain for a handful of rows (1 <= R <= 64) in ONE host call and without an allocation: n_layers (1..8) linear
+ * layers dims[0] -> dims[1] -> .. -> dims[n_layers] with activations acts[l], weights w[l] (dims[l+1], dims[l]) row-major fp32
+ * and biases b[l] as they lie in torch's masters (dims, w, b, acts: host arrays).  Every layer but the last is one launch of
+ * the tacorl_rows_linear2_fwd kernel (x2 absent) on the caller's stream, so the per-neuron summation order and the row
+ * determinism are that entry point's; there is no synchronisation between workgroups, layers are separate launches.
+ * ws: the outputs of the layers before the last, layer l's (R, dims[l+1]) dense at offset R * (dims[1] + .. + dims[l]) - for
+ * equal hidden widths (n_layers - 1) x R x hidden floats; they stay there after the call.  May be NULL with one layer.
+ * The last layer, by mode:
+ *   TACORL_ROWS_MLP_PLAIN          y (R, dims[n_layers]) = acts[last](..), an ordinary layer (a goal encoder);
+ *   TACORL_ROWS_MLP_POLICY_ACTION  the layer is a policy head [fc_mean (Ac) | fc_log_std (Ac) | gripper_action (2)]
+ *     (reference actor.py:65-104 with deterministic=True): y (R, Ac + dg) = [tanh(clamp(mean, -9, 9)) | gripper], the gripper
+ *     column +1 where logit 1 > logit 0 and -1 otherwise (a tie is -1, torch.argmax's index 0).  Only the Ac mean rows and,
+ *     with discrete_gripper, the two logit rows of the head are read; acts[last] is not applied.
+ * npw: neurons per wave of the hidden layers, 1 or 2 (bit-identical results), 0 = the library's choice.
+ * Refused with TACORL_EINVAL before anything is launched: R outside 1..64, n_layers outside 1..8, a width outside 1..2^24, a
+ * NULL or misaligned (4 bytes) pointer, ldx < dims[0], ldy below the output width, an unknown mode / activation / npw, Ac < 1,
+ * a head narrower than 2 Ac (+ 2 with discrete_gripper), y or ws overlapping x, a weight, a bias or each other. */
+#define TACORL_ROWS_MLP_PLAIN 0
+#define TACORL_ROWS_MLP_POLICY_ACTION 1
+int tacorl_rows_mlp_supported(int R, int n_layers, const int* dims, int mode, int Ac, int discrete_gripper);
+int tacorl_rows_mlp_npw(int N, int R); /* the neurons per wave npw = 0 stands for in a layer of N neurons and R rows */
+int tacorl_rows_mlp_fwd(const float* x, int ldx, int n_layers, const int* dims, const float* const* w, const float* const* b,
+                        const int* acts, float* ws, float* y, int ldy, int R, int mode, int Ac, int discrete_gripper, int npw,
+                        tacorl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,9 @@ _SIGS = {
     "tacorl_rows_linear2_supported": (_i, [_i, _i, _i, _i]),
     "tacorl_rows_linear2_group": (_i, []),
     "tacorl_rows_linear2_fwd": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "tacorl_rows_mlp_supported": (_i, [_i, _i, _p, _i, _i, _i]),
+    "tacorl_rows_mlp_npw": (_i, [_i, _i]),
+    "tacorl_rows_mlp_fwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 _lib = None

@@ -17,6 +17,10 @@ tacorl_rows_linear2_fwd per layer up to 16 rows, and above that - where the trai
 
 `latent_plan_policy_restatement` states the same schedule in plain torch ops over callables, for any device and dtype:
 the yardstick of tests/test_vec_policy_cpu.py (as modules/cem.py's cem_restatement is for the CEM kernel).
+
+`RelayPolicy` / `relay_policy_restatement` below are the same for RelayImitationLearning (rollout_manager.py:434-557): the same
+clock, a latent sub-goal from the high-level policy in place of the plan, the low-level policy in place of the decoder, no
+recurrent state.  `rollout_episodes` drives either policy.
 """
 import numpy as np
 import torch
@@ -237,4 +241,158 @@ def latent_plan_policy_restatement(plan_fn, decoder_fn, observations, goals, n_e
         out["replanned"].append(due)
         out["plan"].append(plan.clone())
     out["hidden"] = hidden
+    return out
+
+
+# ------------------------------------------------------------------------------------------ relay imitation learning
+class RelayPolicy:
+    """The relay-imitation rollout (reference evaluation/rollout_manager.py:480-510) for R environments in one step:
+
+        policy = RelayPolicy(module, n_envs=R, plan_duration=16)
+        policy.reset(rows=None)
+        actions = policy.step(observation, goal)                 # {camera: (R,3,H,W)} dicts -> (R, A) fp32 on the device
+        actions = policy.step_embeddings(obs_emb, goal_emb)      # {camera: (R,32)} dicts in, the same out
+
+    No recurrent state: every `plan_duration` steps, per row, the high-level policy turns [enc(obs) | goal_encoder(enc(goal))]
+    into the latent sub-goal tanh(mean); on every step the low-level policy turns [enc(obs) | sub-goal] into tanh(mean) and an
+    arg-max gripper bit.  The clock is PlanClock's host integers; nothing is read back from the device.  Each chain is ONE
+    tacorl_rows_mlp_fwd call (route "rows") up to ROWS_KERNEL_MAX_R rows and the training chain plus the sampling kernel
+    (route "composed") above it (profiles/ril_rollout.md); fp32 from the masters whatever the module's compute dtype.
+    Nothing is captured in a hipGraph."""
+
+    # profiles/ril_rollout.md: the rows chain is the faster route at every R measured (1 .. 64), so every row count a policy can
+    # have takes it; a lower value set on an instance sends the chains above it through the composed route
+    ROWS_KERNEL_MAX_R = 64
+    MAX_ENVS = 64
+
+    def __init__(self, module, n_envs, plan_duration=16):
+        nets = getattr(module, "__dict__", {}).get("_rollout_nets")
+        for name in ("high_level_policy", "low_level_policy"):
+            if getattr(getattr(module, name, None), "get_actions", None) is None:
+                raise ValueError(f"the module has no {name}.get_actions")
+        if nets is None:
+            raise ValueError("the module has no relay-imitation rollout surface")
+        if not 1 <= int(n_envs) <= self.MAX_ENVS:
+            raise ValueError(f"n_envs {n_envs}: 1 .. {self.MAX_ENVS}")
+        from ..modules.inference import RowsMLP
+
+        self.module, self.R, self.dev = module, int(n_envs), module.dev
+        self.clock = PlanClock(n_envs, plan_duration)
+        self.plan_duration = int(plan_duration)
+        self.high_cams, self.low_cams = list(module.high_level_policy_modalities), list(module.low_level_policy_modalities)
+        self.cams = list(self.low_cams)  # the union (each list is a permutation of it)
+        g, hi, lo = nets["goal_encoder"], nets["high"], nets["low"]
+        self.Eo, self.GO, self.A = 32 * len(self.cams), g.G, lo.A
+        self.E = self.Eo + self.GO
+        R = self.R
+        self.genc = RowsMLP(module, g.genc, g.genc_dims, g.genc_acts, R)
+        self.high = RowsMLP(module, hi.head, hi.head_dims, hi.head_acts, R, policy=(hi.Ac, hi.dg))
+        self.low = RowsMLP(module, lo.head, lo.head_dims, lo.head_acts, R, policy=(lo.Ac, lo.dg))
+        f = lambda *s: torch.zeros(*s, device=self.dev)  # noqa: E731
+        self.ld = (self.E + 3) // 4 * 4  # rows of whole 16-byte words, pad columns zero (the composed route's vector loads)
+        self.gin, self.hin, self.lin = f(R, self.Eo), f(R, self.ld), f(R, self.ld)
+        self.hout, self.subgoal, self.actions = f(R, self.GO), f(R, self.GO), f(R, self.A)
+        self._rows_ok = {}  # row count -> tacorl_rows_mlp_supported, asked once
+
+    def reset(self, rows=None):
+        """All rows, or an index list / bool mask: those rows get a new sub-goal on their next step."""
+        self.clock.reset(rows)
+
+    def rows_route(self, n):
+        """'rows' (tacorl_rows_mlp_fwd) or 'composed' (ops.mlp_fwd + ops.tanh_normal_sample) for a chain of n rows."""
+        if n not in self._rows_ok:
+            self._rows_ok[n] = self.low.supported(n)
+        return "rows" if n <= self.ROWS_KERNEL_MAX_R and self._rows_ok[n] else "composed"
+
+    # ------------------------------------------------------------------ the two halves of a step
+    def replan(self, obs_rows, goal_rows, n, route=None):
+        """Sub-goals of n rows: obs_rows / goal_rows {camera: (n,32)} -> self.hout[:n] (a view)."""
+        route = route or self.rows_route(n)
+        for j, c in enumerate(self.high_cams):
+            self.gin[:n, 32 * j: 32 * j + 32] = goal_rows[c]
+            self.hin[:n, 32 * j: 32 * j + 32] = obs_rows[c]
+        self.genc.run(self.gin, self.Eo, n, self.hin, self.Eo, self.ld, route)
+        self.high.run(self.hin, self.ld, n, self.hout, 0, self.GO, route)
+        return self.hout[:n]
+
+    def decode(self, obs_emb, route=None):
+        """The low-level chain over all R rows on [state in low order | self.subgoal] -> self.actions."""
+        for j, c in enumerate(self.low_cams):
+            self.lin[:, 32 * j: 32 * j + 32] = obs_emb[c]
+        self.lin[:, self.Eo: self.E] = self.subgoal
+        self.low.run(self.lin, self.ld, self.R, self.actions, 0, self.A, route or self.rows_route(self.R))
+        return self.actions
+
+    def _advance(self, obs_emb, goal_rows_of, subgoals):
+        R, dev = self.R, self.dev
+        due = self.clock.due()
+        if due:
+            need = due
+            if subgoals is not None and not subgoals.is_cuda:  # a host tensor: which rows it gives is known without a device read
+                given = (~torch.isnan(subgoals.reshape(R, -1)).any(dim=1)).tolist()
+                need = [r for r in due if not given[r]]
+            idx = torch.tensor(due, dtype=torch.long, device=dev)
+            new = None
+            if need:
+                nidx = idx if need == due else torch.tensor(need, dtype=torch.long, device=dev)
+                src = self.replan(_take(obs_emb, nidx), goal_rows_of(nidx), len(need))
+                new = src if need == due else torch.zeros(R, self.GO, device=dev).index_copy_(0, nidx, src).index_select(0, idx)
+            if subgoals is not None:
+                given_rows = subgoals.to(dev, torch.float32).reshape(R, -1).index_select(0, idx)
+                new = given_rows if new is None else torch.where(torch.isnan(given_rows).any(dim=1, keepdim=True), new, given_rows)
+            self.subgoal.index_copy_(0, idx, new)
+        out = self.decode(obs_emb)
+        self.clock.tick(set(due))
+        return out
+
+    def step_embeddings(self, obs_emb, goal_emb, subgoals=None):
+        """obs_emb / goal_emb: {camera: (R,32)} state embeddings of every camera of the union.  subgoals: (R, goal_out) with NaN
+        rows meaning "not given" - overrides the high-level policy for the rows that are due.  Returns the (R, A) actions: a
+        view that stays valid until the next step."""
+        to = lambda d: {c: torch.as_tensor(d[c]).to(self.dev, torch.float32) for c in self.cams}  # noqa: E731
+        obs_emb, goal_emb = to(obs_emb), to(goal_emb)
+        return self._advance(obs_emb, lambda nidx: _take(goal_emb, nidx), subgoals)
+
+    def step(self, observation, goal, noise=None, subgoals=None):
+        """observation / goal: {camera: (R,3,H,W)} fp32 dicts.  Every camera of the union is encoded once for all R rows; the
+        goal images of the rows that are due only.  noise is accepted for rollout_episodes and unused (the actions are
+        deterministic)."""
+        to = lambda d: {c: torch.as_tensor(d[c]).to(self.dev, torch.float32) for c in self.cams}  # noqa: E731
+        observation, goal = to(observation), to(goal)
+        pe = self.module.perceptual_encoder
+        obs_emb = pe.get_state_from_observation(observation=observation, modalities=self.cams, cat_output=False)
+        goal_rows = lambda nidx: pe.get_state_from_observation(  # noqa: E731
+            observation=_take(goal, nidx), modalities=self.cams, cat_output=False)
+        return self._advance(obs_emb, goal_rows, subgoals)
+
+
+def relay_policy_restatement(high_fn, low_fn, obs_embs, goal_embs, n_envs, plan_duration, resets=None, subgoals=None):
+    """RelayPolicy's schedule in plain torch ops, over callables standing in for the networks (any device, any dtype).
+      high_fn(obs rows {camera: (1,32)}, goal rows {camera: (1,32)}, rows (list), t) -> (len(rows), GO): the sub-goal of the
+        rows that are due at step t - goal encoder and high-level policy;
+      low_fn(obs {camera: (R,32)}, sub-goal (R,GO), t) -> (R,A): one low-level step over all rows;
+      obs_embs[t], goal_embs[t]: the step's per-camera embeddings;
+      resets: {t: rows} - `reset(rows)` called BEFORE step t (t = 0 resets every row anyway);
+      subgoals: {t: (R,GO)} with NaN rows meaning "not given".
+    Returns dict(actions [T x (R,A)], replanned [T x list of rows], subgoal [T x (R,GO)])."""
+    clock = PlanClock(n_envs, plan_duration)
+    sub = None
+    out = dict(actions=[], replanned=[], subgoal=[])
+    for t in range(len(obs_embs)):
+        if resets and t in resets:
+            clock.reset(resets[t])
+        obs, goal = obs_embs[t], goal_embs[t]
+        due = clock.due()
+        for r in due:
+            given = subgoals is not None and t in subgoals and not bool(torch.isnan(subgoals[t][r]).any())
+            row = subgoals[t][r] if given else high_fn({c: v[r: r + 1] for c, v in obs.items()},
+                                                       {c: v[r: r + 1] for c, v in goal.items()}, [r], t)[0]
+            if sub is None:
+                sub = torch.zeros(n_envs, row.shape[-1], dtype=row.dtype, device=row.device)
+            sub = sub.clone()
+            sub[r] = row
+        out["actions"].append(low_fn(obs, sub, t))
+        clock.tick(set(due))
+        out["replanned"].append(due)
+        out["subgoal"].append(sub.clone())
     return out

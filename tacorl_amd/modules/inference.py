@@ -334,3 +334,113 @@ def attach_rollout_surface(module, actor_net, cams, goal_cams, action_dim, discr
         module.action_decoder.clear_hidden_state = ad.clear_hidden_state
         module.action_decoder.act = lambda latent_plan, perceptual_emb, latent_goal=None, noise=None: ad.act(
             latent_plan, perceptual_emb, latent_goal, noise=noise, compute=module.compute)
+
+
+# ---------------------------------------------------------------------------------- relay imitation learning
+class RILNetView:
+    """One network of the relay-imitation block (RILBlock: one encoder per camera, one goal encoder, two policies) in the
+    form the surfaces above read a network block: `enc(cam)`, `genc() / genc_dims / genc_acts / G` and - for key "high" or
+    "low" - that policy's `head() / head_dims / head_acts`."""
+
+    def __init__(self, engine, key=None):
+        blk = engine.blk
+        self.enc, self.genc = blk.enc, blk.genc
+        self.genc_dims, self.genc_acts, self.G = list(engine.genc_dims), list(engine.genc_acts), engine.GO
+        self.key = key
+        if key is not None:
+            self.head = lambda: blk.pol(key)
+            self.head_dims, self.head_acts = list(engine.pol_dims[key]), list(engine.pol_acts[key])
+            self.Ac, self.dg = engine.Ac[key], bool(engine.dg) if key == "low" else False
+            self.A = self.Ac + int(self.dg)
+
+
+class RowsMLP:
+    """One MLP chain of the library for 1 .. max_rows (<= 64) rows on buffers allocated once - the rollout's inner loop.
+    route "rows": ONE tacorl_rows_mlp_fwd call (csrc/rollout_ops.hip), fp32 from the masters; route "composed": the training
+    chain ops.mlp_fwd in fp32 and, for a policy head, ops.tanh_normal_sample with eps = 0 and equal Gumbel noise.
+    policy: None (the last layer is an ordinary one: mode "plain") or (Ac, discrete_gripper): the output is the (n, Ac + dg)
+    deterministic action."""
+
+    def __init__(self, owner, base, dims, acts, max_rows, policy=None):
+        self.dev, self.base, self.dims, self.acts, self.R = owner.dev, base, list(dims), list(acts), int(max_rows)
+        self.policy = None if policy is None else (int(policy[0]), bool(policy[1]))
+        self.n_out = self.dims[-1] if policy is None else self.policy[0] + int(self.policy[1])
+        self.wo, self.bo, _ = ops.mlp_param_layout(self.dims)
+        self._c_dims, self._c_acts = ops.int_array(self.dims), ops.int_array(self.acts)
+        self._at, self._w, self._b = None, None, None
+        ops.note_alloc()
+        f = lambda *s: torch.zeros(*s, device=self.dev)  # noqa: E731
+        self.ws = f(max(self.R * sum(self.dims[1:-1]), 1))
+        self.act = f(ops.mlp_act_layout(self.R, self.dims, self.acts)[2])
+        if self.policy is not None:
+            Ac, dg = self.policy
+            self.eps, self.logp = f(self.R, Ac), f(self.R)
+            self.gu = torch.full((self.R, 2), 0.5, device=self.dev) if dg else None
+            self.grip = torch.zeros(self.R, dtype=torch.int32, device=self.dev) if dg else None
+        self._yoff = {}
+
+    def supported(self, n):
+        Ac, dg = self.policy or (0, False)
+        return bool(ops.L.lib().tacorl_rows_mlp_supported(int(n), len(self.acts), self._c_dims, int(self.policy is not None),
+                                                          Ac, int(dg)))
+
+    def _params(self):
+        base = self.base()
+        if base != self._at:
+            n = len(self.acts)
+            self._w = (ops.C.c_void_p * n)(*[base + 4 * o for o in self.wo])
+            self._b = (ops.C.c_void_p * n)(*[base + 4 * o for o in self.bo])
+            self._at = base
+        return base
+
+    def hidden(self, n, l):
+        """Layer l's (n, dims[l+1]) output of the last "rows" call of n rows."""
+        o = n * sum(self.dims[1: l + 1])
+        return self.ws[o: o + n * self.dims[l + 1]].view(n, self.dims[l + 1])
+
+    def run(self, x, ldx, n, y, y_off, ldy, route, npw=0):
+        """Rows [0, n) of x (row pitch ldx; "composed": a multiple of 4 with zero pad columns) -> columns [y_off, y_off + width)
+        of rows [0, n) of y (row pitch ldy)."""
+        if not 1 <= n <= self.R:
+            raise ValueError(f"{n} rows for a chain of at most {self.R}")
+        base = self._params()
+        if route == "rows":
+            Ac, dg = self.policy or (0, False)
+            call("tacorl_rows_mlp_fwd", ptr(x), ldx, len(self.acts), self._c_dims, self._w, self._b, self._c_acts, ptr(self.ws),
+                 ops._at(y, y_off), ldy, n, int(self.policy is not None), Ac, int(dg), int(npw), ops.stream())
+            return
+        if route != "composed":
+            raise ValueError(f"route {route!r}")
+        if n not in self._yoff:
+            self._yoff[n] = ops.mlp_act_layout(n, self.dims, self.acts)[1][-1]
+        yo = self._yoff[n]
+        ops.mlp_fwd([x], ldx, [base], [self.act], [n], self.dims, self.acts, F32)
+        if self.policy is None:
+            ops.copy_cols(self.act, yo, self.dims[-1], y, y_off, ldy, n, self.dims[-1])
+        else:
+            Ac, dg = self.policy
+            ops.tanh_normal_sample(self.act[yo:], self.dims[-1], self.eps, self.gu, False, y, y_off, ldy, self.logp, self.grip,
+                                   1, n, Ac)
+
+
+def attach_ril_rollout_surface(module, engine):
+    """RelayImitationLearning's rollout methods under the reference's names (evaluation/rollout_manager.py:434-557):
+    `perceptual_encoder.get_state_from_observation`, a callable `goal_encoder`, and on `high_level_policy` /
+    `low_level_policy` `get_actions`, `get_dist`, `action_dim`, `discrete_gripper`."""
+    union = [c for c in engine.cams]
+    shared = RILNetView(engine)
+    runner = EncoderRunner(module)
+    module.__dict__["_pe_runner"] = runner
+    module.perceptual_encoder.get_state_from_observation = (
+        lambda observation, modalities=None, cat_output=True: state_from_observation(
+            module, runner, shared, observation, list(modalities if modalities is not None else union), cat_output))
+    attach_goal_encoder(module, shared)
+    module.__dict__["_rollout_nets"] = {"goal_encoder": shared}
+    for key in ("high", "low"):
+        net = RILNetView(engine, key)
+        surf = ActorSurface(module, net, engine.order[key], engine.order[key], net.A, net.dg)
+        box = getattr(module, key + "_level_policy")
+        box.get_actions = surf.get_actions
+        box.get_dist = PlanProposalSurface(module, net, net.Ac).get_dist
+        box.action_dim, box.discrete_gripper = net.A, net.dg
+        module.__dict__["_rollout_nets"][key] = net

@@ -66,6 +66,10 @@ class RelayImitationLearning(GraphMixin, ModuleMixin, LightningModuleBase):
             img_dtype=self.img_dtype, world_size=self.world_size)
         init_views_(self.engine.blk.views)
         self._pv = register_views(self, "", self.engine.blk.views)
+        # rollout surface (evaluation/rollout_manager.py:434-557; evaluation/vec_policy.py RelayPolicy is built on it)
+        from ..inference import attach_ril_rollout_surface
+
+        attach_ril_rollout_surface(self, self.engine)
 
     def sync_from_rank0(self):
         """Broadcast rank 0's parameters and optimiser state (PL's DDP wrap does this for the reference module)."""
