@@ -231,6 +231,19 @@ int tacorl_encoder_fwd_fused(int nprob, const void* const* img, const void* cons
 int tacorl_encoder_fwd_fused_wg(int nprob, const void* const* img, const void* const* packed,
                                 const float* const* params, float* const* out, float* const* act,
                                 const int* n_img, int H, int W, int max_workgroups, tacorl_stream_t stream);
+/* The same launch with a source per problem: src NULL or src[p] NULL - the packed bf16 NHWC images at img[p]; otherwise src[p]
+ * is the DEVICE address of a table entry (tacorl_encoder_src_entry_bytes() each, written by tacorl_encoder_src_fill) that
+ * names n_img[p] contiguous fp32 CHW images, image i at base + i * img_pitch floats.  The kernel converts them itself (round
+ * to nearest even, as tacorl_pack_images*) while it computes the image before: out is bit-identical to the packed route.  The
+ * entry is read when the kernel RUNS, so a captured launch follows whatever the last fill named.  84 x 84 only, never with
+ * act[p] (a backward reads the packed image): TACORL_EINVAL otherwise.  tacorl_encoder_src_supported: would fill accept it? */
+long tacorl_encoder_src_entry_bytes(void);
+int tacorl_encoder_src_supported(const float* base, long img_pitch, long plane_pitch, long row_pitch, int H, int W);
+int tacorl_encoder_src_fill(void* table, int n, const float* const* base, const long* img_pitch, const long* plane_pitch,
+                            const long* row_pitch, int H, int W, tacorl_stream_t stream);
+int tacorl_encoder_fwd_fused_src(int nprob, const void* const* img, const void* const* src, const void* const* packed,
+                                 const float* const* params, float* const* out, float* const* act, const int* n_img, int H,
+                                 int W, int max_workgroups, tacorl_stream_t stream);
 
 /* Backward twin of the fused forward (same preconditions: bf16 NHWC images, bf16 MFMA, a geometry
  * tacorl_encoder_fused_supported() accepts; at most 4 problems): FC tail and soft-argmax as

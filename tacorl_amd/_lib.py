@@ -116,6 +116,10 @@ _SIGS = {
     "tacorl_encoder_pack_weights": (_i, [_i, _p, _p, _p]),
     "tacorl_encoder_fwd_fused": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "tacorl_encoder_fwd_fused_wg": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "tacorl_encoder_src_entry_bytes": (_l, []),
+    "tacorl_encoder_src_supported": (_i, [_p, _l, _l, _l, _i, _i]),
+    "tacorl_encoder_src_fill": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _p]),
+    "tacorl_encoder_fwd_fused_src": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "tacorl_encoder_bwd_fused_ws_bytes": (_sz, [_i, _p, _i, _i]),
     "tacorl_encoder_bwd_fused": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _sz, _p]),
     "tacorl_encoder_bwd_fused_pack": (_i, [_i, _p, _p, _i, _i, _p, _sz, _p]),

@@ -16,8 +16,17 @@ constexpr int cmaxi(int a, int b) { return a > b ? a : b; }
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
+// Source of a problem whose images the kernel converts itself: n fp32 CHW images, image i at base + i * img_pitch, its
+// colour planes plane_pitch apart, rows row_pitch apart (all in floats; the kernel's fp32 mode takes contiguous images only:
+// row_pitch = W, plane_pitch = H * W, checked where the table is filled).  The entry lives in DEVICE memory and is read by
+// the kernel when it runs: a captured launch follows the batch tensor that the last tacorl_encoder_src_fill named.
+struct EFSrc {
+  const float* base;
+  long img_pitch, plane_pitch, row_pitch;
+};
 struct EFProblem {
-  const __bf16* img;   // [n][H][W][3]
+  const __bf16* img;   // [n][H][W][3] (bf16 source; unused with src)
+  const EFSrc* src;    // fp32 CHW source (device table entry), or NULL: the packed bf16 NHWC images at img
   const u32x4* wpk;    // packed bf16 fragments (tacorl_encoder_pack_weights)
   const float* params; // fp32 block (biases, temperature)
   float* out;          // [n][32]

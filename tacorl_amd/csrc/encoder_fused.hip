@@ -474,11 +474,87 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
   };
 #undef EF_LEAN_LD
 
+  // ---- fp32 CHW source (P.src): the waves convert the NEXT image themselves instead of streaming a packed copy in.  An
+  // image is NG groups of four x-adjacent pixels; group q is three 16-byte plane reads (global -> VGPR), six packed
+  // conversions (round to nearest even - the pack kernel's own cast) and 24 contiguous bytes of the NHWC bf16 image buffer the
+  // DMA would have filled.  Lane t owns the groups t + 256 k, k < FP_NK; only TWO groups (sA, sB: 24 VGPRs) are in flight at
+  // a time, issued and retired at nine fixed places spread over conv1 / conv2 / conv3 (fp_slot), so that a group's HBM round
+  // trip has a fifth of an image to complete in.  conv1 and everything behind it read the same bytes as on the packed route.
+  constexpr bool FP_OK = G::WHOLE && H_ == 84 && W_ == 84;  // (the only geometry the mode is instantiated for)
+  constexpr int FP_NG = G::H * G::W / 4, FP_NK = (FP_NG + 255) / 256;
+  static_assert(!FP_OK || (G::W % 4 == 0 && FP_NK == 7), "fp32 source: seven groups per lane");
+  const bool fp = FP_OK && P.src != nullptr;
+  // (the table entry, made wave-uniform by hand: hipcc cannot prove the table unwritten and loads it per lane)
+  unsigned long fp_base = 0, fp_ibytes = 0;
+  constexpr unsigned long fp_pbytes = (unsigned long)G::H * G::W * 4;  // (contiguous images only: tacorl_encoder_src_fill)
+  if (fp) {
+    auto uni = [](long v) {
+      return (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)v) |
+             ((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32);
+    };
+    fp_base = uni((long)P.src->base); fp_ibytes = uni(P.src->img_pitch * 4);
+  }
+  unsigned long fp_img = 0;  // the image being fetched (wave-uniform address)
+  unsigned fp_buf = 0;       // ... the image buffer it goes to (byte offset in the LDS)
+  int fp_t = 0;              // ... and this lane's first group
+  f32x4 sA[3], sB[3];
+  auto fp_begin = [&](long img_idx, int buf) {
+    fp_img = fp_base + (unsigned long)img_idx * fp_ibytes;
+    fp_buf = (unsigned)buf * (unsigned)a.lds_img;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(fp_t));  // (opaque: the lane's addresses are derived per image, not hoisted and spilled)
+    fp_t += tid;
+  };
+  // group of this lane at step k (the last step covers FP_NG - 256 (FP_NK - 1) groups: the lanes beyond them repeat the
+  // image's last group - the same bytes to the same place, no branch)
+  auto fp_lane = [&](int k) -> unsigned {
+    return (unsigned)(k + 1 < FP_NK ? fp_t : min(fp_t, FP_NG - 256 * (FP_NK - 1) - 1));
+  };
+  // The loads are inline asm (SGPR base + 32-bit lane offset) and so are their waits: as plain C++ they came out as FLAT
+  // loads - which count on lgkmcnt, the counter every fragment wait of the conv phases is tuned on - behind vmcnt(0).
+  // hipcc does not know that the registers fill late: fp_wait names them again, and between a load and its wait nothing
+  // else may touch them (two groups of three registers, written only here).
+  auto fp_load = [&](int k, f32x4 (&r)[3]) {
+    const unsigned o = fp_lane(k) * 16u;
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+      asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(r[c]) : "v"(o), "s"(fp_img + (unsigned long)k * 4096u + c * fp_pbytes));
+  };
+  auto fp_store = [&](int k, f32x4 (&r)[3], bool more_in_flight) {
+    // (never build this without the waits, not even to time them: hipcc hands the registers of a finished group to other
+    // values - addresses among them - and a load that is still in flight then lands in those)
+    if (more_in_flight) asm volatile("s_waitcnt vmcnt(3)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]));
+    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]));
+    unsigned char* d = lds + fp_buf + (256u * k + fp_lane(k)) * 24u;
+    *reinterpret_cast<u32x2*>(d) = pack4_bf16(r[0][0], r[1][0], r[2][0], r[0][1]);
+    *reinterpret_cast<u32x2*>(d + 8) = pack4_bf16(r[1][1], r[2][1], r[0][2], r[1][2]);
+    *reinterpret_cast<u32x2*>(d + 16) = pack4_bf16(r[2][2], r[0][3], r[1][3], r[2][3]);
+  };
+  // place n = 0 .. 8 of an image: loads of group n (n < 7) and the stores of group n - 2 (n >= 2), alternating sA / sB
+  auto fp_slot_store = [&](int n) {
+    if (!FP_OK || n < 2 || n >= FP_NK + 2) return;
+    const bool more = n - 1 < FP_NK;  // (the group loaded one place earlier is still in flight)
+    if (n & 1) fp_store(n - 2, sB, more); else fp_store(n - 2, sA, more);
+  };
+  auto fp_slot_load = [&](int n) {
+    if (!FP_OK || n < 0 || n >= FP_NK) return;
+    if (n & 1) fp_load(n, sB); else fp_load(n, sA);
+  };
+
   // images this workgroup processes: worker, worker + nworkers, ... (image granularity: at most one image
   // of imbalance); the FC tail runs after every EF_CHUNK processed images (slots) or at the end.
   long cur = worker;
   int it = 0, buf = 0;
-  dma_load(cur, 0, 0);
+  if (fp) {
+    // the run's first image: every group at once (the fragment registers are free here), one HBM round trip
+    fp_begin(cur, 0);
+    f32x4 first[FP_NK][3];
+#pragma unroll
+    for (int k = 0; k < FP_NK; k++) fp_load(k, first[k]);
+#pragma unroll
+    for (int k = 0; k < FP_NK; k++) fp_store(k, first[k], false);
+  } else {
+    dma_load(cur, 0, 0);
+  }
   // vmcnt(0) as the BUILTIN: it empties the compiler's own scoreboard too (an asm wait does not) - see the note at the
   // bias registers above; the weights load straight into AGPRs and would otherwise be waited for inside the loop
   __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -507,6 +583,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       if (G::WHOLE) lean_begin(worker, buf ^ 1);
 #else
       if (G::WHOLE) lean_begin(has_next ? nxt : cur, buf ^ 1);  // (the workgroup's last image fetches itself again: no branch per piece)
+      if (fp) fp_begin(has_next ? nxt : cur, buf ^ 1);          // (fp32 source: the same rule - the groups never branch on has_next)
 #endif
       STAMP(1);  // DMA issue
       const unsigned char* ib = lds + buf * a.lds_img;
@@ -592,7 +669,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       u32x4 fa[6], fb[6];
       auto dma_of_tile = [&](int i) {
 #if !(EF_X & 1)
-        if (G::WHOLE) {
+        if (G::WHOLE && !fp) {
 #pragma unroll
           for (int q = 0; q < DPT; q++) lean_piece(i * DPT + q);
         }
@@ -608,7 +685,13 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
         for (int s = 1; s < 6; s++) {
           MFMA_AW(A0[i], wc1a[s], bf[s]);
 #if !(EF_X & 1)
-          if (G::WHOLE && (s == 1 || s == 3) && (s >> 1) < DPT) lean_piece(i * DPT + (s >> 1));
+          if (G::WHOLE && (s == 1 || s == 3) && (s >> 1) < DPT) {
+            // fp32 source: places 0 .. 3 of the image's nine ride in tiles 0, 1, 3 and 5 (every wave has those), the stores
+            // where the first piece went, the loads where the second one did
+            const int n = i < 2 ? i : (i == 3 ? 2 : (i == 5 ? 3 : -1));
+            if (fp) { if (s == 1) fp_slot_store(n); else fp_slot_load(n); }
+            else lean_piece(i * DPT + (s >> 1));
+          }
 #endif
           if (s == 4 && prev >= 0) {
             asm volatile("" : "+v"(A0[prev]), "+v"(A1[prev]));
@@ -770,6 +853,10 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
               epi2(t2 - 1);
             }
             if (t2 == 0) fb[i - 1] = ld2one(bfirst, 8 + i - 1);
+            if (FP_OK && fp) {  // places 4 and 5 of the next image's fp32 groups
+              if (i == 2) fp_slot_store(4 + t2);
+              if (i == 6) fp_slot_load(4 + t2);
+            }
             __builtin_amdgcn_sched_barrier(0);
           }
           if (t2 == 0) fb[7] = ld2one(bfirst, 15);
@@ -881,7 +968,8 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
     // clocks ago) are waited for HERE, so that this barrier also publishes "the next image has landed" and the
     // end-of-image barrier can go - the waves then absorb their skew (fc2 runs on two of them) instead of meeting a
     // fourth time per image.  With saved activations the wait would also cover conv2's global stores: old scheme there.
-    const bool early_land = G::WHOLE && P.act == nullptr;
+    // (fp32 source: the last groups are stored during conv3 - the end-of-image barrier, as with saved activations)
+    const bool early_land = G::WHOLE && P.act == nullptr && !fp;
 #if EF_X & 32  // scratch: nobody waits for the next image's DMA (what would a landing wait that never stalls be worth?)
     if (early_land) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #else
@@ -971,6 +1059,10 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
           if (mt == 0 && i <= 9) fb[i - 1] = ld3one(bfirst, 9 + i - 1);
           if (more) { if (i - 1 < 9) fa[i - 1] = ld3one(bcur, i - 1); else fb[i - 10] = ld3one(bcur, i - 1); }
           if (i == 4 && mt > 0) { asm volatile("" : "+v"(accs[mt - 1])); epi3(mt - 1); }
+          if (FP_OK && fp) {  // places 6, 7 and 8 (the last stores: the end-of-image barrier publishes them)
+            if (i == 2) fp_slot_store(6 + mt);
+            if (i == 7) fp_slot_load(6 + mt);
+          }
           __builtin_amdgcn_sched_barrier(0);
         }
         if (more) fb[8] = ld3one(bcur, 17);
@@ -1258,8 +1350,51 @@ extern "C" int tacorl_encoder_fwd_fused(int nprob, const void* const* img, const
 extern "C" int tacorl_encoder_fwd_fused_wg(int nprob, const void* const* img, const void* const* packed,
                                            const float* const* params, float* const* out, float* const* act,
                                            const int* n_img, int H, int W, int max_workgroups, tacorl_stream_t stream) {
+  if (max_workgroups > 0 && max_workgroups < nprob) return TACORL_EINVAL;
+  return tacorl_encoder_fwd_fused_src(nprob, img, nullptr, packed, params, out, act, n_img, H, W, max_workgroups, stream);
+}
+
+// ---- fp32 CHW sources.  The table entries are written by a launch of their own, in stream order, from the caller's
+// arguments: the encoder launch may be a captured graph node, the batch tensor changes from step to step.
+struct EFSrcFill {
+  EFSrc e[EF_MAXP];
+  int n;
+};
+__global__ void ef_src_fill_kernel(EFSrc* __restrict__ tbl, EFSrcFill f) {
+  if ((int)threadIdx.x < f.n) tbl[threadIdx.x] = f.e[threadIdx.x];
+}
+extern "C" long tacorl_encoder_src_entry_bytes(void) { return (long)sizeof(EFSrc); }
+/* Is (base, pitches in floats) a source the fused kernel converts itself?  Contiguous fp32 CHW images of the one geometry
+ * the mode is built for, 16-byte aligned, every pitch a multiple of four floats. */
+extern "C" int tacorl_encoder_src_supported(const float* base, long img_pitch, long plane_pitch, long row_pitch, int H, int W) {
+  if (H != 84 || W != 84 || W % 4) return 0;
+  if (((uintptr_t)base & 15) || img_pitch % 4 || img_pitch < 0) return 0;
+  return row_pitch == W && plane_pitch == (long)H * W;
+}
+extern "C" int tacorl_encoder_src_fill(void* table, int n, const float* const* base, const long* img_pitch,
+                                       const long* plane_pitch, const long* row_pitch, int H, int W, tacorl_stream_t stream) {
+  if (n < 1 || n > EF_MAXP || !table) return TACORL_EINVAL;
+  EFSrcFill f{};
+  f.n = n;
+  for (int i = 0; i < n; i++) {
+    if (!tacorl_encoder_src_supported(base[i], img_pitch[i], plane_pitch[i], row_pitch[i], H, W)) return TACORL_EINVAL;
+    f.e[i] = EFSrc{base[i], img_pitch[i], plane_pitch[i], row_pitch[i]};
+  }
+  hipLaunchKernelGGL(ef_src_fill_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (EFSrc*)table, f);
+  return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
+}
+
+/* The launch with a source per problem: src[p] NULL - the packed bf16 NHWC images at img[p]; else the DEVICE address of an
+ * EFSrc entry (tacorl_encoder_src_fill) naming n_img[p] fp32 CHW images, which the kernel converts on the way in (84 x 84
+ * only, and never a problem whose activations are saved: its backward reads the packed image). */
+extern "C" int tacorl_encoder_fwd_fused_src(int nprob, const void* const* img, const void* const* src,
+                                            const void* const* packed, const float* const* params, float* const* out,
+                                            float* const* act, const int* n_img, int H, int W, int max_workgroups,
+                                            tacorl_stream_t stream) {
   if (nprob < 1 || nprob > EF_MAXP || !tacorl_encoder_fused_supported(H, W)) return TACORL_EINVAL;
-  if (max_workgroups < 0 || (max_workgroups > 0 && max_workgroups < nprob)) return TACORL_EINVAL;
+  // (a budget below the problem count is served - a workgroup walks every problem its units touch; tacorl_encoder_fwd_fused_wg
+  // keeps refusing it)
+  if (max_workgroups < 0) return TACORL_EINVAL;
   EFArgs a{};
   a.nprob = nprob; a.H = H; a.W = W;
   long total = 0;
@@ -1276,10 +1411,14 @@ extern "C" int tacorl_encoder_fwd_fused_wg(int nprob, const void* const* img, co
   long units = 0;
   int first = 1;
   for (int p = 0; p < nprob; p++) {
+    a.p[p].src = src ? (const EFSrc*)src[p] : nullptr;
+    if (a.p[p].src && ((act && act[p]) || H != 84 || W != 84 || ((uintptr_t)a.p[p].src & 7))) return TACORL_EINVAL;
     a.p[p].img = (const __bf16*)img[p]; a.p[p].wpk = (const u32x4*)packed[p]; a.p[p].params = params[p];
     a.p[p].out = out[p]; a.p[p].n_img = n_img[p];
     a.p[p].act = act ? act[p] : nullptr;
-    a.p[p].cost = a.p[p].act ? (ring ? (a.act_bf16 ? 84 : 96) : EF_ACT_COST) : 64;  // (ring, 150 x 200: 243 KB of stores per image with bf16 y1 / y2, 406 KB as fp32)
+    a.p[p].cost = a.p[p].act ? (ring ? (a.act_bf16 ? 84 : 96) : EF_ACT_COST) : 64;
+    // (an image converted from fp32 takes 1.22 x a packed one - 4 096 images 92 against 75.5 us - but weights of 72, 80 and 88
+    // units for it moved the bench-shaped launch by less than its run-to-run spread: it keeps the plain cost)  // (ring, 150 x 200: 243 KB of stores per image with bf16 y1 / y2, 406 KB as fp32)
     if (n_img[p] > 0 && !first) units += setup_cost;
     a.p[p].ustart = units;
     units += (long)a.p[p].cost * n_img[p];

@@ -105,9 +105,50 @@ def geometry_groups(cams, hw, ok, n_problems, limit):
 
 
 # ---------------------------------------------------------------- 4. forward dispatch
+def problem_src(x):
+    """The optional 8th field of a problem: the device address of its fp32-source table entry (SourceTable), or None - its
+    images are the packed NHWC buffer at x[0]."""
+    return x[7] if len(x) > 7 else None
+
+
+class SourceTable:
+    """Device table of fp32 CHW sources that the fused forward converts itself (tacorl_encoder_fwd_fused_src): the launch -
+    possibly a captured graph node - holds the address of an ENTRY, and `fill`, an eager launch in front of it, writes into
+    the entry where this step's batch tensor lies.  Only forward-only problems of the 84 x 84 fused kernel qualify (`ok`)."""
+
+    def __init__(self, device, n):
+        self.esz = int(ops.L.lib().tacorl_encoder_src_entry_bytes())
+        self.n, self.buf = n, torch.zeros(n * self.esz, dtype=torch.uint8, device=device)
+
+    def entry(self, i):
+        return self.buf.data_ptr() + i * self.esz
+
+    @staticmethod
+    def ok(base, img_pitch, hw):
+        """base: device address; img_pitch in floats; the images themselves contiguous (3, H, W) fp32."""
+        H, W = hw
+        return bool(ops.L.lib().tacorl_encoder_src_supported(ops.C.c_void_p(base), img_pitch, H * W, W, H, W))
+
+    def fill(self, sources, hw):
+        """sources: [(base address, image pitch in floats)] for entries 0 .. len - 1."""
+        H, W = hw
+        n, Lg = len(sources), ops.C.c_long * len(sources)
+        assert 0 < n <= self.n
+        call("tacorl_encoder_src_fill", ops.ptr(self.buf), n, ops.ptr_array([b for b, _ in sources]), Lg(*[p for _, p in sources]),
+             Lg(*[H * W] * n), Lg(*[W] * n), H, W, ops.stream())
+
+
 def launch_fused(pr, packs, hw, max_wg=0):
     """One fused encoder launch over the problems pr (each carries its camera: cameras of one geometry may share a launch)
     on at most max_wg workgroups (0: one per CU); activations are saved only for the problems a backward follows."""
+    srcs = [problem_src(x) for x in pr]
+    if any(srcs):  # fp32 CHW sources (problem_src): the same launch, the kernel converts those problems' images itself
+        assert not any(s_ and x[5] for s_, x in zip(srcs, pr)), "a problem with a backward reads the packed image"
+        call("tacorl_encoder_fwd_fused_src", len(pr), ops.ptr_array([x[0] for x in pr]), ops.ptr_array(srcs),
+             ops.ptr_array([packs.buffer(x[1], x[6]) for x in pr]), ops.ptr_array([x[1].enc(x[6]) for x in pr]),
+             ops.ptr_array([x[2] for x in pr]), ops.ptr_array([x[3] if x[5] else None for x in pr]),
+             ops.int_array([x[4] for x in pr]), *hw, int(max_wg), ops.stream())
+        return
     call("tacorl_encoder_fwd_fused_wg", len(pr), ops.ptr_array([x[0] for x in pr]),
          ops.ptr_array([packs.buffer(x[1], x[6]) for x in pr]), ops.ptr_array([x[1].enc(x[6]) for x in pr]),
          ops.ptr_array([x[2] for x in pr]), ops.ptr_array([x[3] if x[5] else None for x in pr]),

@@ -168,6 +168,7 @@ class ACEngine:
         self.arena_extra = []
         self._bind_arena()
         self.extra_enc, self.packs, self._prepacked = [], stage.PackedWeights(device), False
+        self.fp_src = {}  # camera -> {"next": address of a stage.SourceTable entry}: set by the step that owns the batch
         self.B = None
         if B:
             self.ensure_batch(B)
@@ -245,7 +246,7 @@ class ACEngine:
                 self.erow[(k, c)] = {s_: (sl[s_] - r0) * B for s_ in have}  # first enc_out row of each role's images
             self.cam_probs[c] = pr
             self.nbwd[c] = (("obs" in sl) + ("goal" in sl)) * B  # images of a problem that has a backward (GRAD_PROBS)
-        self.X3 = {c: torch.zeros(len(self.slot[c]) * B, *self.hw[c], 3, device=dev, dtype=self.img_dtype) for c in self.enc_cams}
+        self.X3 = ingest.LazyImages({c: torch.zeros(len(self.slot[c]) * B, *self.hw[c], 3, device=dev, dtype=self.img_dtype) for c in self.enc_cams})
         # (the first camera's table - every camera's when the two lists name the same cameras)
         self.enc_probs = self.cam_probs[self.enc_cams[0]]
         nimg = {(k, c): n_ for c in self.enc_cams for k, _, _, n_ in self.cam_probs[c]}
@@ -340,7 +341,8 @@ class ACEngine:
         uniform image pitch, e.g. states[:,0]); the images of a role the camera does not have are not read (None)."""
         given = {"obs": obs, "goal": goal, "next": nxt}
         sl = self.slot[cam]
-        ingest.pack_slots(self.X3[cam], list(sl.values()), self.B, self.hw[cam], [given[s_] for s_ in sl], nchw, self.img_dtype)
+        self.X3.drop(cam)
+        ingest.pack_slots(self.X3.raw(cam), list(sl.values()), self.B, self.hw[cam], [given[s_] for s_ in sl], nchw, self.img_dtype)
 
     def load_transition(self, action, reward, done):
         self.action.copy_(action.reshape(self.B, self.A).float())
@@ -350,7 +352,8 @@ class ACEngine:
     # ----------------------------------------------------------------- forward
     def _img_ptr(self, cam, first_row):
         H, W = self.hw[cam]
-        return self.X3[cam].data_ptr() + first_row * H * W * 3 * self.X3[cam].element_size()
+        x3 = self.X3.raw(cam)  # (as it stands: on TACORL's fp32 route the next observations' slot is filled only for a reader)
+        return x3.data_ptr() + first_row * H * W * 3 * x3.element_size()
 
     # Every encoder problem of a camera goes through the fused single-launch kernel when it applies
     # (bf16 images + bf16 MFMA + a templated camera geometry); the ones a backward follows (GRAD_PROBS)
@@ -371,11 +374,20 @@ class ACEngine:
     def _all_problems(self, c, which="all"):
         """(image pointer, net, out, act, n_img, needs_backward, camera) of every encoder problem of camera c
         (which = "own": the update's networks only, "extra": the caller's frozen ones only - TACORL's LMP window)."""
-        pr = [] if which == "extra" else [
-            (self._img_ptr(c, r0), net, self.enc_out[(k, c)], self.enc_act[(k, c)], n, k in self.GRAD_PROBS, c)
-            for k, net, r0, n in self.cam_probs[c]]
+        pr, B = [], self.B
+        nxt = self.fp_src.get(c, {}).get("next")  # the next observations as an fp32 source (TACORL's eligible batches)
+        for k, net, r0, n in ([] if which == "extra" else self.cam_probs[c]):
+            rows = self.erow[(k, c)]
+            if nxt is None or "next" not in rows or k in self.GRAD_PROBS:
+                pr.append((self._img_ptr(c, r0), net, self.enc_out[(k, c)], self.enc_act[(k, c)], n, k in self.GRAD_PROBS, c))
+                continue
+            # a forward-only problem over the next observations: their slot of X3 is not packed on this route - one problem
+            # per role, the next observations read from where the batch lies, the others from their packed slots
+            for role, row in rows.items():
+                pr.append((self._img_ptr(c, self.slot[c][role] * B), net, self.enc_out[(k, c)][row: row + B], self.enc_act[(k, c)],
+                           B, False, c, nxt if role == "next" else None))
         if which != "own":
-            pr += [(x["img"], x["net"], x["out"], x["act"], x["n"], False, c) for x in self.extra_enc if x["cam"] == c]
+            pr += [(x["img"], x["net"], x["out"], x["act"], x["n"], False, c, x.get("src")) for x in self.extra_enc if x["cam"] == c]
         return pr
 
     def encode_split(self, between):

@@ -73,6 +73,44 @@ def transition_form(images, nchw=True, aug=None, replay=None, rows=3):
     return _form(first, nchw, first.shape[0], None, images, aug)
 
 
+class LazyImages(dict):
+    """NHWC image buffers by camera.  A step that feeds the encoder straight from the batch (TACORL's fp32 route) leaves
+    part of a buffer unpacked and registers how to fill it (`defer`); whoever then READS the buffer by name - a test, a
+    per-layer fallback, a tool - gets it filled first, so the buffers mean what they always meant.  The step's own launches
+    take `raw(c)` (the tensor as it stands) and `drop(c)` what a new batch supersedes."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self._pending = {}
+
+    def raw(self, c):
+        return dict.__getitem__(self, c)
+
+    def defer(self, c, fill):
+        self._pending[c] = fill
+
+    def drop(self, c=None):
+        if c is None:
+            self._pending.clear()
+        else:
+            self._pending.pop(c, None)
+
+    def _settle(self, c):
+        fill = self._pending.pop(c, None)
+        if fill is not None:
+            fill()
+
+    def __getitem__(self, c):
+        self._settle(c)
+        return dict.__getitem__(self, c)
+
+    def values(self):
+        return [self[c] for c in self]
+
+    def items(self):
+        return [(c, self[c]) for c in self]
+
+
 # ------------------------------------------------------------------------- augmentation tables
 def flat_table(t):
     """A (B,T,k) table of per-frame draws as the window job's (B*T,k)."""

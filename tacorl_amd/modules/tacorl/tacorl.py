@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from ... import dist as D
+from ... import encoder_stage as stage
 from ... import image_ingest as ingest
 from ... import ops
 from ..._lib import call, ptr
@@ -107,7 +108,7 @@ class TACORL(CQL_Offline):
             return
         ops.note_alloc()
         dev = self.dev
-        self.frames = {c: torch.zeros(B * T, *hw[c], 3, device=dev, dtype=self.img_dtype) for c in self.all_modalities}
+        self.frames = ingest.LazyImages({c: torch.zeros(B * T, *hw[c], 3, device=dev, dtype=self.img_dtype) for c in self.all_modalities})
         self.f_out = {c: torch.zeros(B * T, 32, device=dev) for c in self.all_modalities}
         self.f_act = {c: torch.zeros(ops.encoder_act_layout(B * T, *hw[c])[1], device=dev) for c in self.all_modalities}
         npr = len(self.plan_recognition_modalities)
@@ -118,8 +119,11 @@ class TACORL(CQL_Offline):
         assert e.action.shape == (B, self.action_dim) and e.action.dtype == torch.float32
         self.plan, self.reward = e.action, e.reward
         # the frozen LMP encoder over the B*T window frames rides in the engine's encoder launches
-        self.engine.extra_enc = [dict(cam=c, img=self.frames[c], net=self.lmp_net, out=self.f_out[c],
+        self.engine.extra_enc = [dict(cam=c, img=self.frames.raw(c), net=self.lmp_net, out=self.f_out[c],
                                       act=self.f_act[c], n=B * T) for c in self.all_modalities]
+        # entries [window | next] per camera for the batches whose forward-only images the encoder reads as fp32 (_fold_ok)
+        self.src_tbl = {c: stage.SourceTable(dev, 2) for c in sorted(set(self.all_modalities) | set(self.engine.cams))}
+        self._folded = None
         self._T = (B, T, tuple(sorted(hw.items())))
 
     def _stage_small(self, batch, noise, B, T):
@@ -140,7 +144,24 @@ class TACORL(CQL_Offline):
             e.done.copy_(self.reward)
         e.set_noise(noise)
 
-    def _stage_frames(self, batch, noise, nchw=True):
+    def _fold_ok(self, f, c, T, batch):
+        """May camera c's forward-only images - the window frames of the frozen LMP encoder, the next observations of
+        actor(next) and both targets - skip the pack?  The fused 84 x 84 forward then converts them itself, straight from the
+        batch (tacorl_encoder_fwd_fused_src), and only [obs; goal], which conv1's weight gradient reads as packed bf16, are
+        packed.  Needs: transformed fp32 CHW frames as they stand (no index table, no augmentation), bf16 compute on the fused
+        kernel, 16-byte aligned tensors.  Everything else keeps the pack."""
+        e, hw = self.engine, f.hw[c]
+        if not (f.form == "f32_nchw" and f.aug is None and T >= 2 and e.use_fused and stage.fused_fwd_ok(hw, self.compute, self.img_dtype)):
+            return False
+        goal = batch["goal"][c] if c in e.cams else None
+        if c in e.cams and not (c in e.slot and list(e.slot[c]) == ["obs", "goal", "next"] and goal.is_cuda and goal.is_contiguous()
+                                and goal.dtype == torch.float32 and ingest.vector_ok(
+                [ingest.PackJob(goal.data_ptr(), 3 * hw[0] * hw[1], 0, 1)], f.form, hw)):
+            return False
+        v, simg = f.frames[c], 3 * hw[0] * hw[1]
+        return stage.SourceTable.ok(v.data_ptr(), simg, hw) and stage.SourceTable.ok(v.data_ptr() + 4 * (T - 1) * simg, T * simg, hw)
+
+    def _stage_frames(self, batch, noise, nchw=True, fold=False):
         """Eager part of the step: pack the window frames (reference NCHW fp32 -> NHWC image dtype) into
         fixed buffers, copy the small tensors, draw / copy the noise.
         uint8 frames - the dataset's own format, (B, T, H, W, 3) with goal (B, H, W, 3) - are taken as they are
@@ -168,15 +189,39 @@ class TACORL(CQL_Offline):
         with torch.cuda.stream(side):
             self._stage_small(batch, noise, B, T)
         u8, Job, ip = f.form in ingest.U8_FORMS, ingest.PackJob, None if f.ids is None else f.ids.data_ptr()
-        for c in sorted(set(self.all_modalities) | set(e.cams)):
+        cams_all = sorted(set(self.all_modalities) | set(e.cams))
+        for c in cams_all:
             v = f.frames[c]
             assert v.is_cuda and v.is_contiguous() and v.dtype == (torch.uint8 if u8 else torch.float32)
+        folded = tuple(c for c in cams_all if fold and self._fold_ok(f, c, T, batch))
+        if folded != self._folded:  # (a captured step holds the route: a batch of another kind drops it)
+            ops.note_alloc()
+            self._folded = folded
+        self.frames.drop()  # (what the previous batch left for a reader is superseded)
+        e.X3.drop()
+        e.fp_src = {c: {"next": self.src_tbl[c].entry(1)} for c in folded if c in e.cams}
+        for x in e.extra_enc:
+            x["src"] = self.src_tbl[x["cam"]].entry(0) if x["cam"] in folded else None
+        for c in cams_all:
+            v = f.frames[c]
             src, simg = v.data_ptr(), 3 * f.src_hw[c][0] * f.src_hw[c][1]  # (simg: elements of a source frame)
+            if c in folded:
+                # entries [window | next = window frame T - 1]; of the images only s = states[:, 0] and the goal are packed
+                self.src_tbl[c].fill([(src, simg), (src + 4 * (T - 1) * simg, T * simg)], hw[c])
+                form, shw = f.form, f.src_hw[c]
+                later = lambda jobs, c=c, keep=v, form=form, shw=shw: ingest.pack(jobs, form, self.img_dtype, shw, hw[c])  # noqa: E731 (keep: the batch tensor stays alive for a reader)
+                if c in self.all_modalities:
+                    self.frames.defer(c, lambda c=c, later=later, src=src, simg=simg: later([Job(src, simg, self.frames.raw(c).data_ptr(), B * T)]))
+                if c in e.cams:
+                    x3, slot = e.X3.raw(c).data_ptr(), B * 3 * hw[c][0] * hw[c][1] * e.X3.raw(c).element_size()
+                    ingest.pack([Job(src, T * simg, x3, B), Job(batch["goal"][c].data_ptr(), simg, x3 + slot, B)], form, self.img_dtype, shw, hw[c])
+                    e.X3.defer(c, lambda later=later, src=src, simg=simg, x3=x3, slot=slot: later([Job(src + 4 * (T - 1) * simg, T * simg, x3 + 2 * slot, B)]))
+                continue
             jobs, roles = [], []
             if c in self.all_modalities:  # a camera's jobs: the window into self.frames ...
-                jobs, roles = [Job(src, simg, self.frames[c].data_ptr(), B * T, ip, 1)], ["window"]
+                jobs, roles = [Job(src, simg, self.frames.raw(c).data_ptr(), B * T, ip, 1)], ["window"]
             if c in e.cams:  # ... and s = states[:,0], the goal, s' = states[:,-1] (get_rl_batch, tacorl.py:142-179) into X3's slots
-                x3, slot = e.X3[c].data_ptr(), B * 3 * hw[c][0] * hw[c][1] * e.X3[c].element_size()
+                x3, slot = e.X3.raw(c).data_ptr(), B * 3 * hw[c][0] * hw[c][1] * e.X3.raw(c).element_size()
                 if ip is not None:  # by index (ids[i * stride]): obs = ids[b T], goal = the table's tail, next = ids[b T + T - 1]
                     jobs += [Job(src, simg, x3, B, ip, T), Job(src, simg, x3 + slot, B, ip + 8 * B * T, 1),
                              Job(src, simg, x3 + 2 * slot, B, ip + 8 * (T - 1), T)]
@@ -337,7 +382,7 @@ class TACORL(CQL_Offline):
         self._step(batch, noise, optimize=False, log_type="validation")
 
     def _step(self, batch, noise, optimize, log_type, nchw=True):
-        B, T, hw = self._stage_frames(batch, noise, nchw)
+        B, T, hw = self._stage_frames(batch, noise, nchw, fold=getattr(self, "fp32_ingest", True))
         with_ad = self._ad_due()
         key = ("tacorl", B, T, tuple(sorted(hw.items())), self.current_epoch < self.bc_epochs, optimize, with_ad)
         e, bc = self.engine, self.current_epoch < self.bc_epochs
