@@ -1136,6 +1136,7 @@ static int pr_encoder_fused_launch(const float* emb, int ld_emb, const float* pa
   if (((uintptr_t)emb | (uintptr_t)params | (uintptr_t)params_bf16 | (uintptr_t)pooled) & 15) return TACORL_EINVAL;
   PrArgs a{};
   a.emb = emb; a.P = params; a.Pb = (const __bf16*)params_bf16; a.pooled = pooled; a.ld_emb = ld_emb; a.B = B; a.FF = FF; a.L = L;
+  if (offsets[0] % 4) return TACORL_EINVAL;  // (read as f32x4 like every other operand of the block)
   a.pos = offsets[0];
   for (int l = 0; l < L; l++) {
     const long* q = offsets + 1 + 12 * l;
