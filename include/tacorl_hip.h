@@ -898,6 +898,38 @@ int tacorl_rows_mlp_fwd(const float* x, int ldx, int n_layers, const int* dims, 
                         const int* acts, float* ws, float* y, int ldy, int R, int mode, int Ac, int discrete_gripper, int npw,
                         tacorl_stream_t stream);
 
+/* ---- a step's noise from a counter-based generator (DESIGN.md "Device noise"; tacorl_amd/noise.py restates it in NumPy) ----
+ * Replaces the torch generator launches in front of a step (normal_ / uniform_ / bernoulli_): every element is a pure function
+ * of (seed, step, draw id, global sample index, position inside the sample), computed by ONE launch for all of a step's buffers.
+ * Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (j >> 2, sample0 + b, draw_id << 16 | k, step) for element j of
+ * the `inner` elements of sample b, outer index k; element j takes output word j & 3 (a ragged last group leaves words unused).
+ *   uniform: (w >> 8) 2^-24 in [0, 1);    keep: uniform < keep_p (uint8 1 / 0);
+ *   normal:  Box-Muller on the word pairs (0,1) and (2,3): r = sqrt(-2 ln(((wa >> 8) + 1) 2^-24)), angle 2 pi (wb >> 8) 2^-24,
+ *            outputs r cos, r sin in that order (accurate logf / sqrtf, sincospif on the exact argument 2 u2).
+ * A segment is one destination buffer: n_outer x B_local x inner elements at `offset` (floats from base_f32; bytes from
+ * base_u8 for a keep mask), laid out (B_local, n_outer, inner) or, with outer_major, (n_outer, B_local, inner).  One thread per
+ * group of four; group0 = number of groups (n_outer B_local ceil(inner / 4)) of the segments in front.  Elements between
+ * segments (alignment padding) are not written.
+ * `segs` is a HOST table (tacorl_noise_table with n_seg rows, like the library's pointer arrays): it is checked on the host and
+ * travels to the kernel as a launch argument, so the call stays asynchronous and a bad table is refused before anything is
+ * launched.  Refused with TACORL_EINVAL: n_seg outside 1..TACORL_NOISE_MAX_SEGS, an unknown kind, draw_id or n_outer outside
+ * 16 bits (n_outer >= 1), B_local / inner < 1, a segment that ends past n_f32 / n_u8 (the buffers' sizes in elements), keep_p
+ * outside [0, 1], group0 / n_groups that are not the prefix sums, sample0 < 0, base_f32 not 16-byte aligned, a NULL base that
+ * a segment needs. */
+#define TACORL_NOISE_MAX_SEGS 64
+enum { TACORL_NOISE_NORMAL = 0, TACORL_NOISE_UNIFORM = 1, TACORL_NOISE_KEEP = 2 };
+typedef struct {
+  int offset, kind, draw_id, n_outer, B_local, inner, outer_major;
+  float keep_p;
+  int group0, reserved;
+} tacorl_noise_seg;
+typedef struct {
+  int n_f32, n_u8, n_groups, reserved;
+  tacorl_noise_seg seg[1]; /* n_seg rows */
+} tacorl_noise_table;
+int tacorl_noise_fill(const void* segs, int n_seg, void* base_f32, void* base_u8, unsigned long long seed, unsigned int step,
+                      int sample0, tacorl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from . import blocks, ops
 from . import encoder_stage as stage
 from . import image_ingest as ingest
 from . import dist as D
+from . import noise as noise_mod
 from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, BF16, F32, LOG_SLOTS, call, ptr
 
 
@@ -296,36 +297,41 @@ class ACEngine:
         # the data action IS rows [0, B) of the Q networks' action column block (no copy in front of the Q forward):
         # load_transition / TACORL's plan-recognition sample write it in place
         self.action = self.acts_main[:B]
-        # all noise of a step in two flat buffers (normal | uniform): two generator launches per step
+        # all noise of a step in ONE flat buffer [normal | uniform]: two generator launches per step with torch's generator
+        # (one per part), one tacorl_noise_fill launch with a device-noise seed (self._noise_table, built here)
         shapes = dict(eps_pi=(B, self.Ac), eps_next=(B, self.Ac), eps_cur=(n, B, self.Ac), eps_nxt=(n, B, self.Ac))
         shapes.update(getattr(self, "extra_normal", {}))  # e.g. TACORL's plan-recognition eps
         ushapes = dict(u_rand=(n * B, self.A))
         if self.dg:
             ushapes.update(g_pi=(B, 2), g_next=(B, 2), g_cur=(n, B, 2), g_nxt=(n, B, 2))
-
-        def carve(sh):
-            import math
-            sizes = {k: _al4(math.prod(v)) for k, v in sh.items()}
-            flat = f(sum(sizes.values()))
-            out, off = {}, 0
+        import math
+        n_normal = sum(_al4(math.prod(v)) for v in shapes.values())
+        flat = self._noise_flat = f(n_normal + sum(_al4(math.prod(v)) for v in ushapes.values()))
+        self._noise_normal, self._noise_uniform = flat[:n_normal], flat[n_normal:]
+        views, entries, off = {}, [], 0
+        for kind, sh in (("normal", shapes), ("uniform", ushapes)):
             for k, v in sh.items():
-                out[k] = flat[off: off + math.prod(v)].view(*v)
-                off += sizes[k]
-            return flat, out
-
-        self._noise_normal, nn_ = carve(shapes)
-        self._noise_uniform, nu_ = carve(ushapes)
-        self.extra_noise = {k: nn_.pop(k) for k in getattr(self, "extra_normal", {})}
-        self.noise = dict(eps_pi=nn_["eps_pi"], eps_next=nn_["eps_next"], u_rand=nu_["u_rand"], eps_cur=nn_["eps_cur"],
-                          eps_nxt=nn_["eps_nxt"])
+                views[k] = flat[off: off + math.prod(v)].view(*v)
+                entries.append((k, kind, off, v))
+                off += _al4(math.prod(v))
+        self._noise_table = noise_mod.table_for(flat.numel(), entries, B)
+        self.extra_noise = {k: views[k] for k in getattr(self, "extra_normal", {})}
+        self.noise = {k: views[k] for k in ("eps_pi", "eps_next", "u_rand", "eps_cur", "eps_nxt")}
         if self.dg:
-            self.noise.update({k: nu_[k] for k in ("g_pi", "g_next", "g_cur", "g_nxt")})
+            self.noise.update({k: views[k] for k in ("g_pi", "g_next", "g_cur", "g_nxt")})
         self.logs = f(32)
         self.cql_ws = torch.empty(max(256, ops.L.lib().tacorl_cql_ws_bytes(B)), dtype=torch.uint8, device=dev)
 
     # ------------------------------------------------------------------- inputs
+    device_noise = None  # a noise.DeviceNoise: the step's noise from the counter-based generator (ModuleMixin.set_device_noise)
+
     def set_noise(self, noise=None):
-        """Copy injected noise, or draw fresh noise with torch's device generator (two launches)."""
+        """Copy injected noise; or, with a device-noise seed (self.device_noise), fill every buffer for this rank's samples of
+        the current step in one launch and advance the step; or draw with torch's device generator (two launches)."""
+        if noise is None and self.device_noise is not None:
+            self.device_noise.fill(self._noise_table, self._noise_flat, None, noise_mod.rank_sample0(self.B, self.world))
+            self.device_noise.advance()
+            return
         if noise is None:
             self._noise_normal.normal_()
             self._noise_uniform.uniform_()

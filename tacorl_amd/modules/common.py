@@ -128,6 +128,49 @@ def broadcast_blocks(blocks, src=0):
                 dist.broadcast(t, src)
 
 
+def carve_plan_noise(mod, B, A):
+    """PlayLMP's two draws (posterior sample eps_plan, random plan u_plan) in one flat buffer, with the entries of its
+    device-noise segment table (the table itself is built at the first seeded draw: draw_plan_noise)."""
+    n = (B * A + 3) // 4 * 4
+    flat = mod._noise_flat = torch.zeros(2 * n, device=mod.dev)
+    mod.noise = dict(eps_plan=flat[:B * A].view(B, A), u_plan=flat[n: n + B * A].view(B, A))
+    mod._noise_entries = [("eps_plan", "normal", 0, (B, A)), ("u_plan", "uniform", n, (B, A))]
+    mod._noise_tables = {}
+
+
+def draw_plan_noise(mod, noise, B, T):
+    """The noise of a PlayLMP step, staged eagerly in front of its graph: the injected tape; or, with a device-noise seed, ONE
+    tacorl_noise_fill launch for eps_plan, u_plan and - in train mode with dropout - the plan recognition's keep masks (the
+    second destination base of that launch), after which the step counter advances; or torch's device generator."""
+    pr = mod.pr
+    # plan-recognition dropout is live in train mode (reference transformer.yaml:9, nn.Module.training): its keep masks
+    # are drawn (or injected: noise["dropout"]) here, with the step's other noise
+    mod._pr_train = bool(mod.training and pr.dropout_p > 0)
+    dn = mod.__dict__.get("_device_noise")
+    if noise is None and dn is not None:
+        from ..noise import rank_sample0, table_for
+
+        if mod._pr_train:
+            pr._ensure(B, T)
+        tab = mod._noise_tables.get(mod._pr_train)
+        if tab is None:
+            tab = mod._noise_tables[mod._pr_train] = table_for(
+                mod._noise_flat.numel(), mod._noise_entries, B, pr.keep_flat.numel() if mod._pr_train else 0,
+                pr.keep_entries if mod._pr_train else ())
+        dn.fill(tab, mod._noise_flat, pr.keep_flat if mod._pr_train else None, rank_sample0(B, getattr(mod, "world_size", 1)))
+        dn.advance()
+        return
+    for k, buf in mod.noise.items():
+        if noise is not None:
+            buf.copy_(noise[k].reshape(buf.shape))
+        elif k.startswith("eps"):
+            buf.normal_()
+        else:
+            buf.uniform_()
+    if mod._pr_train:
+        pr.stage_dropout(B, T, noise.get("dropout") if noise is not None else None)
+
+
 class ModuleMixin:
     """What the three module classes share on top of LightningModuleBase (pl.LightningModule when
     pytorch_lightning is importable, tacorl_amd.lightning._MiniLightningModule otherwise): the parameter
@@ -218,6 +261,29 @@ class ModuleMixin:
         self._graphs = {}
         if ws > 1:
             self.sync_from_rank0()
+
+    # -- the step's noise from the counter-based generator (tacorl_amd/noise.py); None: torch's device generator, as before
+    DEVICE_NOISE_KEY = "tacorl_device_noise"  # checkpoint key (beside state_dict, whose layout does not change)
+
+    def set_device_noise(self, seed, step=0):
+        """Draw every stochastic term of the step with tacorl_noise_fill from (seed, step): rank-count invariant, resumable.
+        seed None switches back to torch's generator.  An injected `noise=` tape still wins."""
+        from ..noise import DeviceNoise
+
+        dn = None if seed is None else DeviceNoise(seed, step)
+        self.__dict__["_device_noise"] = dn
+        if getattr(self, "engine", None) is not None:
+            self.engine.device_noise = dn
+
+    def on_save_checkpoint(self, checkpoint):
+        dn = self.__dict__.get("_device_noise")
+        if dn is not None:
+            checkpoint[self.DEVICE_NOISE_KEY] = dn.state()
+
+    def on_load_checkpoint(self, checkpoint):
+        st = checkpoint.get(self.DEVICE_NOISE_KEY)
+        if st is not None:
+            self.set_device_noise(st["seed"], st["step"])
 
     def _make_adam(self, name, entries, lr):
         from ..lightning import BlockAdam

@@ -27,7 +27,7 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
                  dr3_coefficient: float = 0.03, with_vib: bool = False, vib_coefficient: float = 0.01,
                  real_world: bool = False, obs_modalities: List[str] = [], goal_modalities: List[str] = [],
                  action_dim: int = 7, *args, device=None, compute_dtype="f32", image_dtype="f32", world_size=1,
-                 **kwargs):
+                 device_noise_seed=None, **kwargs):
         super().__init__()
         if with_dr3 or with_vib:
             raise NotImplementedError("DR3 / VIB regularisers are off in every in-scope config (SURVEY 8a A9)")
@@ -61,6 +61,7 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         # target entropy: -action_dim (real world, :93-94) or -prod(env.action_space.shape) = -7 (:96-98)
         self.target_entropy = -float(action_dim) if real_world else -7.0
         self.build_networks()
+        self.set_device_noise(device_noise_seed)
         if _D.collectives_on(world_size):
             self.sync_from_rank0()
 

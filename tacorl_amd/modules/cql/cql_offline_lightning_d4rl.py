@@ -24,7 +24,8 @@ class CQL_Offline(_ImageCQL):
                  conservative_weight: float = 1.0, lagrange_thresh: float = 5.0, n_action_samples: int = 10,
                  temp: float = 1.0, with_lagrange: bool = False, with_dr3: bool = False, dr3_coefficient: float = 0.03,
                  with_vib: bool = False, vib_coefficient: float = 0.01, d4rl_env: str = "antmaze-large-diverse-v0", *args,
-                 state_dim=None, action_dim=None, device=None, compute_dtype="f32", world_size=1, **kwargs):
+                 state_dim=None, action_dim=None, device=None, compute_dtype="f32", world_size=1, device_noise_seed=None,
+                 **kwargs):
         LightningModuleBase.__init__(self)
         if with_dr3 or with_vib:
             raise NotImplementedError("DR3 / VIB regularisers are off in every in-scope config (SURVEY 8a A9)")
@@ -49,6 +50,7 @@ class CQL_Offline(_ImageCQL):
         self.obs_modalities, self.goal_modalities = [], []
         self.target_entropy = -float(self.env_action_dim)  # -prod(env.action_space.shape) (:76-78)
         self.build_networks()
+        self.set_device_noise(device_noise_seed)
         if _D.collectives_on(world_size):
             self.sync_from_rank0()
 

@@ -19,7 +19,7 @@ from ...networks.action_decoder import ActionDecoderLogistic
 from ...networks.plan_recognition import PlanRecognition
 from ...vec_engine import HeadBlock
 from .. import cfgcheck
-from ..common import GraphMixin, ModuleMixin, broadcast_blocks, register_views, to_plain
+from ..common import GraphMixin, ModuleMixin, broadcast_blocks, carve_plan_noise, draw_plan_noise, register_views, to_plain
 from ..d4rl_env import GOAL_DIM, env_dims
 
 LOG_NAMES = ["kl_loss", "kl_loss_scaled", "action_loss", None, "random_plan_action_loss"]  # slots of self.logs
@@ -29,7 +29,7 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
     def __init__(self, actor={}, plan_proposal={}, plan_recognition={}, action_decoder={}, transform_manager={}, dataloader={},
                  kl_beta: float = 1e-3, kl_balancing: bool = True, add_random_plan_loss: bool = False, kl_alpha: float = 0.8,
                  lr: float = 1e-4, d4rl_env: str = "antmaze-large-diverse-v0", *args, state_dim=None, action_dim=None,
-                 device=None, compute_dtype="f32", world_size=1, **kwargs):
+                 device=None, compute_dtype="f32", world_size=1, device_noise_seed=None, **kwargs):
         super().__init__()
         self._init_runtime(device, compute_dtype, "f32", world_size)
         self.automatic_optimization = False  # forward, backward and the fused Adam are one kernel sequence in training_step
@@ -41,6 +41,7 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self.lr, self.kl_beta, self.kl_balancing, self.kl_alpha = lr, kl_beta, kl_balancing, kl_alpha
         self.pp_cfg, self.pr_cfg, self.ad_cfg = to_plain(plan_proposal), to_plain(plan_recognition), to_plain(action_decoder)
         self.build_networks()
+        self.set_device_noise(device_noise_seed)
         if _D.collectives_on(self.world_size):
             self.sync_from_rank0()
 
@@ -113,7 +114,7 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self.d_head_pp, self.d_head_pr = f(B, 2 * A), f(B, 2 * A)
         self.plan, self.rplan, self.d_plan = f(B, A), f(B, A), f(B, A)
         self.d_obs = f(B * T, self.state_dim)  # the decoder's gradient w.r.t. the observations: written, read by nothing
-        self.noise = dict(eps_plan=f(B, A), u_plan=f(B, A))
+        carve_plan_noise(self, B, A)
         self.logs = f(16)  # 0 kl, 1 kl_scaled, 2 action_loss, 4 random-plan action_loss (3, 5: the decoder's second output)
         self._shape = (B, T)
 
@@ -195,16 +196,7 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self._ensure(B, T)
         gs = 1.0 / self.world_size
         # the step's draws, in the reference's order: dropout masks, rsample, one uniform_(-1, 1) random plan (:114,130,133)
-        for k, buf in self.noise.items():
-            if noise is not None:
-                buf.copy_(noise[k].reshape(buf.shape))
-            elif k.startswith("eps"):
-                buf.normal_()
-            else:
-                buf.uniform_()
-        self._pr_train = bool(self.training and pr.dropout_p > 0)
-        if self._pr_train:
-            pr.stage_dropout(B, T, noise.get("dropout") if noise is not None else None)
+        draw_plan_noise(self, noise, B, T)
         if rb is not None:
             rb["replay"].sample_into(rb["draws"], obs=self.obs, actions=self.acts)
             self.goal.copy_(self.obs[:, -1, :self.goal_dim])

@@ -20,7 +20,7 @@ from ...networks.plan_recognition import PlanRecognition
 from ...networks.plan_recognition_birnn import PlanRecognitionBiRNN
 from ...lightning import LightningModuleBase
 from .. import cfgcheck
-from ..common import GraphMixin, ModuleMixin, register_views, to_plain
+from ..common import GraphMixin, ModuleMixin, carve_plan_noise, draw_plan_noise, register_views, to_plain
 
 
 class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
@@ -30,7 +30,7 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
                  lr: float = 1e-4, plan_proposal_obs_modalities: List[str] = [],
                  plan_proposal_goal_modalities: List[str] = [], plan_recognition_modalities: List[str] = [],
                  action_decoder_modalities: List[str] = [], real_world: bool = False, *args, device=None,
-                 compute_dtype="f32", image_dtype="f32", world_size=1, **kwargs):
+                 compute_dtype="f32", image_dtype="f32", world_size=1, device_noise_seed=None, **kwargs):
         super().__init__()
         self._init_runtime(device, compute_dtype, image_dtype, world_size)
         # The reference leaves optimisation to PL (one Adam over everything, :362-368).  Here forward, backward and
@@ -52,6 +52,7 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self.pp_cfg, self.pr_cfg, self.ad_cfg = to_plain(plan_proposal), to_plain(plan_recognition), to_plain(action_decoder)
         self.pe_cfg, self.ge_cfg = to_plain(perceptual_encoder), to_plain(goal_encoder)
         self.build_networks()
+        self.set_device_noise(device_noise_seed)
         if _D.collectives_on(self.world_size):
             self.sync_from_rank0()
 
@@ -209,7 +210,7 @@ def _playlmp_ensure(self, B, T, hw):
     A = self.pr.A
     self.d_head_pp, self.d_head_pr = f(B, 2 * A), f(B, 2 * A)
     self.plan, self.rplan, self.d_plan = f(B, A), f(B, A), f(B, A)
-    self.noise = dict(eps_plan=f(B, A), u_plan=f(B, A))
+    carve_plan_noise(self, B, A)
     self.logs = f(16)  # 0 kl, 1 kl_scaled, 2 action_loss, 3 gripper_acc, 4 rand action_loss, 5 rand gripper_acc
     self._shape = key
 
@@ -230,18 +231,7 @@ def _playlmp_step(self, batch, noise=None, optimize=True, log_type="train", nchw
     _playlmp_ensure(self, B, T, hw)
     R = B * T
     gs = 1.0 / getattr(self, "world_size", 1)
-    for k, buf in self.noise.items():
-        if noise is not None:
-            buf.copy_(noise[k].reshape(buf.shape))
-        elif k.startswith("eps"):
-            buf.normal_()
-        else:
-            buf.uniform_()
-    # plan-recognition dropout is live in train mode (reference transformer.yaml:9, nn.Module.training): its keep masks
-    # are drawn (or injected: noise["dropout"]) here, with the step's other noise
-    self._pr_train = bool(self.training and pr.dropout_p > 0)
-    if self._pr_train:
-        pr.stage_dropout(B, T, noise.get("dropout") if noise is not None else None)
+    draw_plan_noise(self, noise, B, T)
     # ---- eager staging: frames into the fixed NHWC buffers, actions into a fixed buffer
     for c in cams:  # the job: the window into self.frames[c] (by index straight out of the dataset: gather + pack in one pass)
         v = f.frames[c].to(self.dev)

@@ -63,18 +63,28 @@ class PlanRecognition:
         self.ff2 = [f(R, D) for _ in range(self.L)]
         self.stats = [f(R, 2) for _ in range(2 * self.L)]
         self.pooled, self.fc_out, self.head = f(B, D), f(B, self.FC), f(B, 2 * self.A)
-        self.keep = None
+        self.keep = self.keep_flat = self.keep_entries = None
         if self.dropout_p > 0:  # keep masks (uint8): [embedding] + per layer [attention probs, dropout1, ffn, dropout2]
-            u8 = lambda n: torch.ones(n, dtype=torch.uint8, device=self.dev)  # noqa: E731
-            self.keep = [u8(R * D)]
+            # carved from ONE flat buffer (every mask on a multiple of 4 bytes), so that a device-noise fill reaches all of them
+            # as the second destination of the step's one launch: keep_entries = (draw id, offset, elements per sample, keep p)
+            from ..noise import dropout_id
+            per = [T * D]
             for _ in range(self.L):
-                self.keep += [u8(B * self.H * T * T), u8(R * D), u8(R * self.FF), u8(R * D)]
+                per += [self.H * T * T, T * D, T * self.FF, T * D]
+            offs, o = [], 0
+            for n_ in per:
+                offs.append(o)
+                o += (B * n_ + 3) // 4 * 4
+            self.keep_flat = torch.ones(o, dtype=torch.uint8, device=self.dev)
+            self.keep = [self.keep_flat[o_: o_ + B * n_] for o_, n_ in zip(offs, per)]
+            self.keep_entries = [(dropout_id(i), o_, n_, 1.0 - self.dropout_p) for i, (o_, n_) in enumerate(zip(offs, per))]
         self._shape = (B, T)
 
     def stage_dropout(self, B, T, masks=None):
         """Fill the keep masks of the next train-mode forward (eager, before a graph replay - like the step's other
         noise).  masks: the reference's draws in its order and layouts (sequence-major (T,B,*) for the activations,
-        (B,H,T,T) for the attention probabilities); None: fresh Bernoulli(1 - p) draws from torch's device generator."""
+        (B,H,T,T) for the attention probabilities); None: fresh Bernoulli(1 - p) draws from torch's device generator.
+        (With a device-noise seed the owning step fills keep_flat itself, with its other noise: modules/common.draw_plan_noise.)"""
         self._ensure(B, T)
         if self.keep is None:
             return
