@@ -128,49 +128,6 @@ def broadcast_blocks(blocks, src=0):
                 dist.broadcast(t, src)
 
 
-def carve_plan_noise(mod, B, A):
-    """PlayLMP's two draws (posterior sample eps_plan, random plan u_plan) in one flat buffer, with the entries of its
-    device-noise segment table (the table itself is built at the first seeded draw: draw_plan_noise)."""
-    n = (B * A + 3) // 4 * 4
-    flat = mod._noise_flat = torch.zeros(2 * n, device=mod.dev)
-    mod.noise = dict(eps_plan=flat[:B * A].view(B, A), u_plan=flat[n: n + B * A].view(B, A))
-    mod._noise_entries = [("eps_plan", "normal", 0, (B, A)), ("u_plan", "uniform", n, (B, A))]
-    mod._noise_tables = {}
-
-
-def draw_plan_noise(mod, noise, B, T):
-    """The noise of a PlayLMP step, staged eagerly in front of its graph: the injected tape; or, with a device-noise seed, ONE
-    tacorl_noise_fill launch for eps_plan, u_plan and - in train mode with dropout - the plan recognition's keep masks (the
-    second destination base of that launch), after which the step counter advances; or torch's device generator."""
-    pr = mod.pr
-    # plan-recognition dropout is live in train mode (reference transformer.yaml:9, nn.Module.training): its keep masks
-    # are drawn (or injected: noise["dropout"]) here, with the step's other noise
-    mod._pr_train = bool(mod.training and pr.dropout_p > 0)
-    dn = mod.__dict__.get("_device_noise")
-    if noise is None and dn is not None:
-        from ..noise import rank_sample0, table_for
-
-        if mod._pr_train:
-            pr._ensure(B, T)
-        tab = mod._noise_tables.get(mod._pr_train)
-        if tab is None:
-            tab = mod._noise_tables[mod._pr_train] = table_for(
-                mod._noise_flat.numel(), mod._noise_entries, B, pr.keep_flat.numel() if mod._pr_train else 0,
-                pr.keep_entries if mod._pr_train else ())
-        dn.fill(tab, mod._noise_flat, pr.keep_flat if mod._pr_train else None, rank_sample0(B, getattr(mod, "world_size", 1)))
-        dn.advance()
-        return
-    for k, buf in mod.noise.items():
-        if noise is not None:
-            buf.copy_(noise[k].reshape(buf.shape))
-        elif k.startswith("eps"):
-            buf.normal_()
-        else:
-            buf.uniform_()
-    if mod._pr_train:
-        pr.stage_dropout(B, T, noise.get("dropout") if noise is not None else None)
-
-
 class ModuleMixin:
     """What the three module classes share on top of LightningModuleBase (pl.LightningModule when
     pytorch_lightning is importable, tacorl_amd.lightning._MiniLightningModule otherwise): the parameter
@@ -234,6 +191,15 @@ class ModuleMixin:
                 "(device=..., default cuda:$LOCAL_RANK) and select precision with compute_dtype / image_dtype; "
                 f".to({probe.device}, {probe.dtype}) cannot move or cast it")
         return self
+
+    def sync_from_rank0(self):
+        """Broadcast rank 0's parameters and optimiser state (PL's DDP wrap does this for the reference module): every block of
+        `self._blocks()`, and the writes announced to torch's version counters."""
+        from .. import ops
+
+        blocks = self._blocks()
+        broadcast_blocks(blocks)
+        ops.touched(*[b.param for b in blocks])
 
     def _tick_optimizers(self):
         """Under a pytorch_lightning Trainer: one `.step()` per optimizer per training_step, as the reference's manual

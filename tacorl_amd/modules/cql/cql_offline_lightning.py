@@ -14,7 +14,7 @@ from ... import dist as _D
 from ... import image_ingest as ingest
 from ...engine import ACEngine
 from ...lightning import LightningModuleBase
-from ..common import GraphMixin, ModuleMixin, broadcast_blocks, register_views, to_plain
+from ..common import GraphMixin, ModuleMixin, register_views, to_plain
 
 
 class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
@@ -125,7 +125,7 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
         attach_rollout_surface(self, e.actor, e.cams, self.goal_modalities, self.action_dim, e.dg,
                                critics={"q1": e.q1, "q2": e.q2, "target_q1": e.tq1, "target_q2": e.tq2})
 
-    def _all_blocks(self):
+    def _blocks(self):
         e = self.engine
         out = [e.actor, e.q1, e.q2, e.tq1, e.tq2, e.log_alpha, e.log_alpha_prime]
         for extra in ("lmp_net",):
@@ -136,20 +136,10 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
                 out.append(getattr(self, extra).blk)
         return out
 
-    def sync_from_rank0(self):
-        """Broadcast rank 0's parameters and optimiser state (PL's DDP wrap does this for the reference module)."""
-        broadcast_blocks(self._all_blocks())
-        from ... import ops
-        ops.touched(*[b.param for b in self._all_blocks()])
-
     def sync_targets(self):
         """target.load_state_dict(q.state_dict()) (reference :226-227)."""
         e = self.engine
         e.tq1.param.copy_(e.q1.param); e.tq2.param.copy_(e.q2.param)
-
-    @property
-    def device(self):
-        return self.dev
 
     def _stepped_blocks(self):
         """Parameter blocks the step's optimiser kernels write (see ops.touched / GraphMixin._run_segments)."""

@@ -19,13 +19,16 @@ from ...networks.action_decoder import ActionDecoderLogistic
 from ...networks.plan_recognition import PlanRecognition
 from ...vec_engine import HeadBlock
 from .. import cfgcheck
-from ..common import GraphMixin, ModuleMixin, broadcast_blocks, carve_plan_noise, draw_plan_noise, register_views, to_plain
+from ..common import GraphMixin, ModuleMixin, register_views, to_plain
 from ..d4rl_env import GOAL_DIM, env_dims
+from .shell import PlayLMPShell
 
-LOG_NAMES = ["kl_loss", "kl_loss_scaled", "action_loss", None, "random_plan_action_loss"]  # slots of self.logs
 
+class PlayLMP(PlayLMPShell, GraphMixin, ModuleMixin, LightningModuleBase):
+    GRAPH_KEY = "playlmp_d4rl"
+    OPT_ORDER = ("pr", "pp", "ad")
+    LOG_NAMES = ["kl_loss", "kl_loss_scaled", "action_loss", None, "random_plan_action_loss"]  # slots of self.logs
 
-class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
     def __init__(self, actor={}, plan_proposal={}, plan_recognition={}, action_decoder={}, transform_manager={}, dataloader={},
                  kl_beta: float = 1e-3, kl_balancing: bool = True, add_random_plan_loss: bool = False, kl_alpha: float = 0.8,
                  lr: float = 1e-4, d4rl_env: str = "antmaze-large-diverse-v0", *args, state_dim=None, action_dim=None,
@@ -82,22 +85,8 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
 
         attach_vec_rollout_surface(self, A, plan_proposal_net=self.pp, ad=self.ad)
 
-    def _blocks(self):
-        return [self.pp, self.pr.blk, self.ad.blk]
-
-    def sync_from_rank0(self):
-        broadcast_blocks(self._blocks())
-        ops.touched(*[b.param for b in self._blocks()])
-
-    def set_kl_beta(self, kl_beta):
-        """reference :190-192."""
-        self.kl_beta = kl_beta
-
-    def named_gradients(self):
-        out = {f"plan_proposal.{k}": v for k, v in self.pp.grad_views.items()}
-        out.update({f"plan_recognition.{k}": v for k, v in self.pr.blk.grad_views.items()})
-        out.update({f"action_decoder.{k}": v for k, v in self.ad.blk.grad_views.items()})
-        return out
+    def _parts(self):
+        return [("pp", self.pp, "plan_proposal."), ("pr", self.pr.blk, "plan_recognition."), ("ad", self.ad.blk, "action_decoder.")]
 
     # --------------------------------------------------------------------------- training step
     def _ensure(self, B, T):
@@ -114,22 +103,9 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self.d_head_pp, self.d_head_pr = f(B, 2 * A), f(B, 2 * A)
         self.plan, self.rplan, self.d_plan = f(B, A), f(B, A), f(B, A)
         self.d_obs = f(B * T, self.state_dim)  # the decoder's gradient w.r.t. the observations: written, read by nothing
-        carve_plan_noise(self, B, A)
+        self.carve_plan_noise(B, A)
         self.logs = f(16)  # 0 kl, 1 kl_scaled, 2 action_loss, 4 random-plan action_loss (3, 5: the decoder's second output)
         self._shape = (B, T)
-
-    def _grad_arena(self):
-        """The three blocks' gradients as slices of one allocation (made on first use, i.e. only with several ranks)."""
-        a = self.__dict__.get("_grad_arena_t")
-        if a is None:
-            ops.note_alloc()
-            a = torch.zeros(sum(b.size for b in self._blocks()), device=self.dev)
-            o = 0
-            for b in self._blocks():
-                b.rebind_grad(a[o: o + b.size])
-                o += b.size
-            self.__dict__["_grad_arena_t"] = a
-        return a
 
     def _fwd_bwd(self, B, T, gs):
         """Device side of the step up to the gradients (fixed buffers only: hipGraph-capturable).  reference :108-144."""
@@ -178,75 +154,29 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
              float(pr.min_std), ops.stream())
         pr.backward(self.d_head_pr, B, T, cd)
 
-    def _step(self, batch, noise=None, optimize=True, log_type="train"):
+    def _open(self, batch):
         rb = batch.get("replay")  # a fused replay batch (data/d4rl_replay.py): the sampler writes self.obs / self.acts itself
         if rb is not None:
             rp = rb["replay"]
             if rb.get("kind") != "d4rl_window" or rp.S != self.state_dim or rp.A != self.env_action_dim:
                 raise ValueError(f"the replay batch ({rb.get('kind')}: S {rp.S}, A {rp.A}) does not fit this module "
                                  f"({self.state_dim}, {self.env_action_dim})")
-            obs, (B, T) = None, (rb["B"], rb["T"])
+            B, T = rb["B"], rb["T"]
         else:
-            obs = batch["observations"]
-            B, T = obs.shape[:2]
-        pr = self.pr
-        opts = getattr(self, "_optimizers", None)
-        if opts and opts[0].lr != self.lr:  # lr edited on the optimiser (scheduler): a launch argument -> new captures
-            self.lr, self._graphs = opts[0].lr, {}
+            B, T = batch["observations"].shape[:2]
         self._ensure(B, T)
-        gs = 1.0 / self.world_size
-        # the step's draws, in the reference's order: dropout masks, rsample, one uniform_(-1, 1) random plan (:114,130,133)
-        draw_plan_noise(self, noise, B, T)
+        return B, T, (), rb
+
+    def _stage(self, batch, rb):
         if rb is not None:
             rb["replay"].sample_into(rb["draws"], obs=self.obs, actions=self.acts)
             self.goal.copy_(self.obs[:, -1, :self.goal_dim])
         else:
+            obs = batch["observations"]
             self.obs.copy_(obs)
             self.goal.copy_(obs[:, -1, :self.goal_dim])  # pp_goal = observations[:, -1, :2] (:111)
             self.acts.copy_(batch["actions"])
-        reduce_on = optimize and _D.collectives_on(self.world_size)
-        if reduce_on:
-            self._grad_arena()  # (before anything is captured: the backward kernels write into the arena's slices)
-
-        def opt():
-            if optimize:
-                ops.adam_step_batch([(blk.param, blk.grad, blk.m, blk.v, self.lr, 0.0, blk.step, None, 0.0) for blk in self._blocks()])
-
-        def reduce_grads():
-            if reduce_on:
-                _D.all_reduce_sum_(self._grad_arena())  # ONE collective: [plan proposal | plan recognition | action decoder]
-
-        self._stepped_blocks = (lambda: [b.param for b in self._blocks()]) if optimize else None
-        self._run_segments(("playlmp_d4rl", B, T, optimize, self._pr_train), [lambda: self._fwd_bwd(B, T, gs), opt], [reduce_grads])
-        self._step_count += 1
-        if (optimize and self.log_every_n_steps > 1 and self._step_count % self.log_every_n_steps
-                and self.__dict__.get("_last_total") is not None):
-            return self.__dict__["_last_total"]
-        logs, div = _D.reduce_logs_(self.logs, self.world_size)
-        lg = [x / div for x in logs.cpu().tolist()]
-        for k, v in zip(LOG_NAMES, lg):
-            if k is not None:
-                self.log(f"{log_type}/{k}", v, on_step=True, on_epoch=True, sync_dist=True)
-        total = lg[1] + lg[2]
-        self.log(f"{log_type}/total_loss", total, on_step=True, on_epoch=True, sync_dist=True)
-        self.__dict__["_last_total"] = total
-        return total
-
-    def training_step(self, batch, batch_idx=0, noise=None):
-        """reference :194-204 (returns the total loss; the optimiser step has already run - manual optimisation)."""
-        out = self._step(batch, noise, True, "train")
-        self._tick_optimizers()
-        return out
-
-    def validation_step(self, batch, batch_idx=0, noise=None):
-        return self._step(batch, noise, False, "validation")
-
-    def configure_optimizers(self):
-        """reference :235-241: ONE Adam over every parameter.  A BlockAdam spanning the three flat blocks."""
-        ent = [(blk, self._pv[k], blk.views_of(blk.m), blk.views_of(blk.v))
-               for k, blk in (("pr", self.pr.blk), ("pp", self.pp), ("ad", self.ad.blk))]
-        self._optimizers = [self._make_adam("adam", ent, self.lr)]
-        return self._optimizers[0]
+        return ()
 
 
 def load_play_lmp(play_lmp_dir, epoch=-1, overwrite_cfg=None, device=None, compute_dtype="f32", unsafe_pickle=False):

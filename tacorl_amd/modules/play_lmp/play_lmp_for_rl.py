@@ -7,12 +7,12 @@ from pathlib import Path
 from typing import List
 
 import torch
-import torch.nn as nn
 
-from ... import _lib
 from ... import dist as _D
 from ... import encoder_stage as stage
-from ..._lib import ACT_NONE, ACT_SILU
+from ... import image_ingest as ingest
+from ... import ops
+from ..._lib import ACT_NONE, ACT_SILU, BF16, call, ptr
 from ...engine import NetBlock
 from ...init import init_views_
 from ...networks.action_decoder import ActionDecoderLogistic
@@ -20,10 +20,26 @@ from ...networks.plan_recognition import PlanRecognition
 from ...networks.plan_recognition_birnn import PlanRecognitionBiRNN
 from ...lightning import LightningModuleBase
 from .. import cfgcheck
-from ..common import GraphMixin, ModuleMixin, carve_plan_noise, draw_plan_noise, register_views, to_plain
+from ..common import GraphMixin, ModuleMixin, register_views, to_plain
+from .shell import PlayLMPShell
+
+# the net block's view names -> the reference's state-dict names (the block is laid out as an actor-critic network's)
+REF_PREFIX = (("encoder.", "perceptual_encoder."), ("actor.policy.", "plan_proposal.policy."))
 
 
-class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
+class PlayLMP(PlayLMPShell, GraphMixin, ModuleMixin, LightningModuleBase):
+    GRAPH_KEY = "playlmp"
+    OPT_ORDER = ("net", "pr", "ad")
+    LOG_NAMES = ["kl_loss", "kl_loss_scaled", "action_loss", "gripper_accuracy", "random_plan_action_loss",
+                 "random_plan_gripper_accuracy"]  # slots of self.logs
+    # test switches (tests set them on instances)
+    fused_mlps = True         # bf16: goal encoder and policy head as the single-launch MLP kernels
+    pp_gather = True          # ... which gather their inputs where the producers left them
+    branches = True           # independent chains of the step on side streams (branches of the captured graph)
+    early_prepare = True      # weights-only preparation beside the encoder's tail
+    pp_forward_side = False   # the plan proposal's forward on a branch of its own (slower: _fwd_bwd)
+    demb_one_launch = True    # the four shares of d_emb and the cameras' slices in one launch
+
     def __init__(self, env={}, actor={}, plan_proposal={}, plan_recognition={}, perceptual_encoder={},
                  goal_encoder={}, action_decoder={}, transform_manager={}, dataloader={}, kl_beta: float = 1e-3,
                  kl_balancing: bool = True, add_random_plan_loss: bool = False, kl_alpha: float = 0.8,
@@ -85,17 +101,8 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         init_views_(self.net.views)
         init_views_(self.pr.blk.views)
         init_views_(self.ad.blk.views, rnn_hidden=self.ad.hidden)
-        ren = {}
-        for k, v in self.net.views.items():
-            if k.startswith("encoder."):
-                ren["perceptual_encoder." + k[len("encoder."):]] = v
-            elif k.startswith("actor.policy."):
-                ren["plan_proposal.policy." + k[len("actor.policy."):]] = v
-            else:
-                ren[k] = v
-        pv = register_views(self, "", ren)
-        back = {v_: k_ for k_, v_ in zip(self.net.views, ren)}  # renamed -> block view name
-        self._pv = {"net": {back[k]: p for k, p in pv.items()},
+        pv = register_views(self, "", {self._ref_name(k): v for k, v in self.net.views.items()})
+        self._pv = {"net": {k: pv[self._ref_name(k)] for k in self.net.views},
                     "pr": register_views(self, "plan_recognition.", self.pr.blk.views),
                     "ad": register_views(self, "action_decoder.", self.ad.blk.views)}
         for k, v in self.ad.buffers.items():
@@ -123,18 +130,240 @@ class PlayLMP(GraphMixin, ModuleMixin, LightningModuleBase):
         self.action_decoder.act = lambda latent_plan, perceptual_emb, latent_goal=None, noise=None: self.ad.act(
             latent_plan, perceptual_emb, latent_goal, noise=noise, compute=self.compute)
 
-    def sync_from_rank0(self):
-        """Broadcast rank 0's parameters and optimiser state (PL's DDP wrap does this for the reference module)."""
-        from ... import ops
-        from ..common import broadcast_blocks
+    def _parts(self):
+        return [("net", self.net, ""), ("pr", self.pr.blk, "plan_recognition."), ("ad", self.ad.blk, "action_decoder.")]
 
-        blocks = [self.net, self.pr.blk, self.ad.blk]
-        broadcast_blocks(blocks)
-        ops.touched(*[b.param for b in blocks])
+    def _ref_name(self, name):
+        for ours, ref in REF_PREFIX:
+            if name.startswith(ours):
+                return ref + name[len(ours):]
+        return name
 
-    def set_kl_beta(self, kl_beta):
-        """reference :303-305."""
-        self.kl_beta = kl_beta
+    # --------------------------------------------------------------------------- training step
+    def _ensure(self, B, T, hw):
+        key = (B, T, tuple(sorted(hw.items())))
+        if getattr(self, "_shape", None) == key:
+            return
+        ops.note_alloc()
+        dev, cams, net = self.dev, self.plan_proposal_obs_modalities, self.net
+        f = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
+        R, Ec = B * T, 32 * len(cams)
+        self.frames = {c: torch.zeros(R, *hw[c], 3, device=dev, dtype=self.img_dtype) for c in cams}
+        self.f_out = {c: f(R, 32) for c in cams}
+        self.f_act = {c: f(ops.encoder_act_layout(R, *hw[c])[1]) for c in cams}
+        self.f_dout = {c: f(R, 32) for c in cams}
+        self.emb, self.d_emb = f(R, Ec), f(R, Ec)
+        self.gin, self.dgin = f(B, Ec), f(B, Ec)
+        self.gact = f(ops.mlp_act_layout(B, net.genc_dims, net.genc_acts)[2])
+        self.g_yoff = ops.mlp_act_layout(B, net.genc_dims, net.genc_acts)[1][-1]
+        self.S, self.dS = f(B, 2 * Ec), f(B, 2 * Ec)
+        self.pact = f(ops.mlp_act_layout(B, net.head_dims, net.head_acts)[2])
+        self.p_yoff = ops.mlp_act_layout(B, net.head_dims, net.head_acts)[1][-1]
+        A = self.pr.A
+        self.d_head_pp, self.d_head_pr = f(B, 2 * A), f(B, 2 * A)
+        self.plan, self.rplan, self.d_plan = f(B, A), f(B, A), f(B, A)
+        self.carve_plan_noise(B, A)
+        self.logs = f(16)  # 0 kl, 1 kl_scaled, 2 action_loss, 3 gripper_acc, 4 rand action_loss, 5 rand gripper_acc
+        self._shape = key
+
+    def _open(self, batch, nchw=True):
+        from ...data.replay import wait_ready
+
+        wait_ready(batch)  # a replay batch's small tables travel on the feeder's copy stream
+        f = ingest.window_form(batch, nchw)
+        self._ensure(f.B, f.T, f.hw)
+        return f.B, f.T, (tuple(sorted(f.hw.items())),), f
+
+    def _stage(self, batch, f):
+        """Eager staging: frames into the fixed NHWC buffers, actions into a fixed buffer."""
+        R = f.B * f.T
+        for c in self.plan_proposal_obs_modalities:  # the job: the window into self.frames[c] (by index straight out of the dataset: gather + pack in one pass)
+            v = f.frames[c].to(self.dev)
+            if not v.is_contiguous():
+                raise ValueError("window frames must be contiguous")
+            job = ingest.PackJob(v.data_ptr(), 3 * f.src_hw[c][0] * f.src_hw[c][1], self.frames[c].data_ptr(), R,
+                                 None if f.ids is None else f.ids.data_ptr(), 1, **ingest.window_tables(f.aug, c, "window", f.T))
+            ingest.pack([job], f.form, self.img_dtype, f.src_hw[c], f.hw[c], f.aug["pad"][c] if f.aug is not None else None)
+        if getattr(self, "_acts", None) is None or self._acts.shape != batch["actions"].shape:
+            ops.note_alloc()
+            self._acts = torch.zeros(*batch["actions"].shape, device=self.dev)
+        self._acts.copy_(batch["actions"])
+        return f.hw, self._acts
+
+    def _pp_forward(self, B, T, Ec, A, cd):
+        """Plan proposal: goal encoder on emb[:, -1], policy head on [emb[:, 0] | goal]; returns the (B, 2A) head view."""
+        net = self.net
+        # round 5: both MLP inputs - emb[:, -1] for the goal encoder, [emb[:, 0] | goal_enc] for the policy head - are gathered by
+        # the fused forwards where their producers left them (ops.mlp_fwd_gather, as the actor-critic engine does): three copy
+        # launches off this chain; the assembled rows the weight gradients read are written from the forward's registers
+        gather = (cd == BF16 and self.fused_mlps and self.pp_gather
+                  and ops.mlp_fwd_gather_ok([B], net.genc_dims, net.genc_acts, Ec, cd, False)
+                  and ops.mlp_fwd_gather_ok([B], net.head_dims, net.head_acts, 2 * Ec, cd, False))
+        if not gather:
+            ops.copy_cols(self.emb, (T - 1) * Ec, T * Ec, self.gin, 0, Ec, B, Ec)  # pp_goal input = emb[:, -1]
+        # bf16 mode: the goal encoder and the plan proposal's policy head run as the single-launch MLP kernels (forward, input
+        # gradients, weight gradients) on a bf16 mirror of their weights, as in the actor-critic engine.  (Per layer they are 7
+        # generic GEMM launches on this chain: hidden behind the random-plan decoder pass while that was a pass of its own -
+        # no gain then -, on the critical path since it rides in the real pass.)
+        pb_g = pb_h = None
+        if cd == BF16 and self.fused_mlps:
+            import ctypes as C
+            call("tacorl_to_bf16_batch", 1, ops.ptr_array([net.genc()]), ops.ptr_array([net.genc_bf16()]),
+                 (C.c_long * 1)(net.size - net.genc_off), ops.stream())
+            pb_g, pb_h = [net.genc_bf16()], [net.head_bf16()]
+        self._pp_bf16 = pb_g
+        if gather:
+            ops.mlp_fwd_gather([[(self.emb, (T - 1) * Ec, T * Ec, 0, 0)]], [self.gin], Ec, [net.genc()], pb_g, [self.gact], [B],
+                               net.genc_dims, net.genc_acts)
+            ops.mlp_fwd_gather([[(self.emb, 0, T * Ec, 0, 0), (self.gact, self.g_yoff, Ec, Ec, 0)]], [self.S], 2 * Ec, [net.head()], pb_h,
+                               [self.pact], [B], net.head_dims, net.head_acts)
+            return self.pact[self.p_yoff: self.p_yoff + B * 2 * A]
+        ops.mlp_fwd([self.gin], Ec, [net.genc()], [self.gact], [B], net.genc_dims, net.genc_acts, cd, params_bf16=pb_g)
+        ops.copy_cols(self.emb, 0, T * Ec, self.S, 0, 2 * Ec, B, Ec)  # pp_state = emb[:, 0]
+        ops.copy_cols(self.gact, self.g_yoff, Ec, self.S, Ec, 2 * Ec, B, Ec)
+        ops.mlp_fwd([self.S], 2 * Ec, [net.head()], [self.pact], [B], net.head_dims, net.head_acts, cd, params_bf16=pb_h)
+        return self.pact[self.p_yoff: self.p_yoff + B * 2 * A]
+
+    def _fwd_bwd(self, B, T, gs, hw, acts):
+        """Device side of the PlayLMP step up to the gradients (fixed buffers only: hipGraph-capturable)."""
+        cams, net, pr, ad = self.plan_proposal_obs_modalities, self.net, self.pr, self.ad
+        R, Ec, A, cd = B * T, 32 * len(cams), pr.A, self.compute
+        xd = stage.image_flag(self.img_dtype)
+        ops.mark("start")
+        for j, c in enumerate(cams):
+            H, W = hw[c]
+            # (the fused forward only where the LDS-resident backward follows it: one predicate for forward and backward)
+            if stage.fused_bwd_ok((H, W), cd, self.img_dtype, [R]):
+                # one launch for the whole encoder, activations saved for the backward (encoder_fused.hip); the pack in front of
+                # it is unconditional - part of the captured step, whatever the version stamps say
+                self.enc_packs.pack([(net, c)])
+                call("tacorl_encoder_fwd_fused", 1, ops.ptr_array([self.frames[c]]), ops.ptr_array([self.enc_packs.buffer(net, c)]),
+                     ops.ptr_array([net.enc(c)]), ops.ptr_array([self.f_out[c]]), ops.ptr_array([self.f_act[c]]),
+                     ops.int_array([R]), H, W, ops.stream())
+            else:
+                call("tacorl_encoder_fwd", 1, ops.ptr_array([self.frames[c]]), ops.ptr_array([net.enc(c)]),
+                     ops.ptr_array([self.f_out[c]]), ops.ptr_array([self.f_act[c]]), ops.int_array([R]), H, W, xd, cd,
+                     ops.stream())
+            ops.copy_cols(self.f_out[c], 0, 32, self.emb, 32 * j, Ec, R, 32)
+        ops.mark("encoded")
+        # Branches (torch streams: branches of the captured graph).  The step is a long chain of small kernels; what does not
+        # depend on each other runs side by side: the logging-only random-plan decoder pass beside the plan proposal /
+        # recognition forward, the plan proposal's backward beside the decoder's, the decoder's and the plan recognition's
+        # weight gradients beside the BPTT / input-gradient chains and the encoder backward.  (Scratch buffers are per network - "ad_*" tags - so branches do not share any.)
+        if getattr(self, "_branch", None) is None:
+            self._branch = [torch.cuda.Stream(device=self.dev) for _ in range(3)]
+        main = torch.cuda.current_stream()
+        s_rand, s_pp, s_wg = self._branch if self.branches else [main] * 3  # tests switch the branches off
+        # logging-only pass with a uniform random plan (reference :243-252) - before the real pass, whose activations
+        # are the ones the backward sees (the decoder's buffers are shared: the real pass waits for this branch)
+        # Where the ring-GEMM path runs (bf16), the random-plan pass is not a pass of its own: its rows ride in the launches of
+        # the real pass (same weights, read once - ActionDecoderLogistic.twin_*); only its input projection and its loss
+        # stay on the branch.
+        twin, ad_prepared, pr_ready = None, False, None
+        s_rand.wait_stream(main)
+        with torch.cuda.stream(s_rand):
+            if cd == BF16 and not self._pr_train and self.early_prepare:
+                # weights only: the plan recognition's bf16 mirror and its composed posterior head, beside the encoder's tail
+                pr.prepare_inference()
+                pr_ready = torch.cuda.Event()
+                pr_ready.record(s_rand)
+                # (NOT pr.prepare_backward(): its transposes ride on the weight-gradient stream, behind the decoder's weight
+                # gradients - the plan recognition's backward then waits for those, and that serialisation is faster: see there)
+            call("tacorl_uniform_actions", ptr(self.noise["u_plan"]), ptr(self.rplan), A, B, A, 0, ops.stream())
+            if ad.twin_ok(B, cd):
+                twin = ad.twin_input_proj(self.rplan, self.emb, Ec, B, T, T - 1)
+                # weights-only preparation of the real pass and of the backward rides on this branch (joined before the pass)
+                ad.refresh_mirrors(B, T - 1)
+                ad_prepared = ad.prepare_backward(B, T - 1, cd) if self.early_prepare else False
+                ops.mark("rand:prepared")
+            else:
+                ad.forward(self.rplan, self.emb, Ec, B, T, T - 1, cd)
+                ad.loss(acts, ops._at(self.logs, 4), B, T, T - 1, want_grad=False)
+        # The plan proposal's forward (goal encoder -> policy head: a dependent chain of its own, ~55 us at B = 32) needs only the
+        # embeddings, like the plan recognition - but on its own branch beside the plan recognition's launch, joined at the KL,
+        # the step is SLOWER (1.252 -> 1.302 ms at B = 32, 2.365 -> 2.410 at B = 256, same-process A/B): a third concurrent
+        # branch at that point (the early preparation branch is still running) costs more than the 55 us it hides.  In line.
+        pp_side = s_pp if self.pp_forward_side else main
+        pp_side.wait_stream(main)
+        with torch.cuda.stream(pp_side):
+            head_pp = self._pp_forward(B, T, Ec, A, cd)
+        ops.mark("pp_fwd")
+        if pr_ready is not None:
+            main.wait_event(pr_ready)
+        head_pr = pr.forward(self.emb, Ec, B, T, cd, train=self._pr_train, prepared=pr_ready is not None,
+                             sample=(self.noise["eps_plan"], self.plan) if pr_ready is not None else None)
+        main.wait_stream(pp_side)
+        pb_g = self._pp_bf16
+        call("tacorl_gauss_kl_balanced", ptr(head_pr), ptr(head_pp), ptr(self.d_head_pr), ptr(self.d_head_pp), B, A,
+             float(self.kl_alpha), float(self.kl_beta), float(pr.min_std), int(self.kl_balancing), gs, ptr(self.logs),
+             ops.stream())
+        ops.mark("kl")
+        # plan proposal backward (needs only the KL's gradient): its own branch; d_emb gets its share after the join
+        s_pp.wait_stream(main)
+        with torch.cuda.stream(s_pp):
+            def mlp_backward(tag, x, ldx, par, act, d_out, ldo, grad, d_x, ldd, dims, acts):
+                if pb_g is not None and ops.mlp_bwd_fused_ok(1, dims, ldo, ldd, cd):
+                    ops.mlp_bwd_fused_dgrad([par], [act], [d_out], ldo, [d_x], ldd, [B], dims, acts, "plmp_" + tag)
+                    ops.mlp_bwd_fused_wgrad([x], ldx, [act], [d_out], ldo, [grad], [B], dims, acts, "plmp_" + tag)
+                else:
+                    ops.mlp_bwd([x], ldx, [par], [act], [d_out], ldo, [grad], [d_x], ldd, [B], dims, acts, cd, ws_tag="plmp_" + tag)
+
+            mlp_backward("pp", self.S, 2 * Ec, net.head(), self.pact, self.d_head_pp, 2 * A, net.head(net.grad), self.dS, 2 * Ec,
+                         net.head_dims, net.head_acts)
+            mlp_backward("genc", self.gin, Ec, net.genc(), self.gact, ops._at(self.dS, Ec), 2 * Ec, net.genc(net.grad), self.dgin, Ec,
+                         net.genc_dims, net.genc_acts)
+        if pr_ready is None:  # (otherwise pr.forward sampled the plan - inside its one launch where that path runs)
+            call("tacorl_pr_sample", ptr(head_pr), ptr(self.noise["eps_plan"]), ptr(self.plan), None, None, B, A,
+                 float(pr.min_std), ops.stream())
+        main.wait_stream(s_rand)
+        ops.mark("ad:start")
+        # (mirrors_current: the branch above has refreshed the bf16 mirrors of the weights - in the random-plan pass of its own, or explicitly)
+        ad.forward(self.plan, self.emb, Ec, B, T, T - 1, cd, mirrors_current=True, twin=twin)
+        if twin is not None:
+            s_rand.wait_stream(main)
+            with torch.cuda.stream(s_rand):
+                ad.twin_heads(twin, B, T - 1)  # (the random pass's heads and loss: off the real pass's chain)
+                ad.loss(acts, ops._at(self.logs, 4), B, T, T - 1, want_grad=False, twin=twin)
+        ad.loss(acts, ops._at(self.logs, 2), B, T, T - 1, want_grad=True, grad_scale=gs)
+        if self.add_random_plan_loss:
+            raise NotImplementedError("add_random_plan_loss=True is not used by any in-scope config")
+        ops.mark("ad:loss")
+        # ---- backward
+        ad.backward(B, T - 1, cd, need_input_grad=True, wgrad_stream=s_wg, join=False, prepared=ad_prepared)
+        if ad.E == Ec:  # (the decoder sees every camera's embedding: its share defines the whole block - no fill launch in front)
+            call("tacorl_ad_input_bwd", ptr(ad.dx_seq), ptr(self.d_plan), ptr(self.d_emb), Ec, B, T, T - 1, ad.P, ad.E, 2,
+                 ops.stream())
+        else:
+            self.d_emb.zero_()
+            call("tacorl_ad_input_bwd", ptr(ad.dx_seq), ptr(self.d_plan), ptr(self.d_emb), Ec, B, T, T - 1, ad.P, ad.E, 1,
+                 ops.stream())
+        ops.mark("ad:bwd")
+        call("tacorl_pr_sample_bwd", ptr(head_pr), ptr(self.noise["eps_plan"]), ptr(self.d_plan), ptr(self.d_head_pr), B, A,
+             float(pr.min_std), ops.stream())
+        dx = pr.backward(self.d_head_pr, B, T, cd, wgrad_stream=s_wg)
+        ops.mark("pr:bwd")
+        # round 5: the four shares of d_emb and the cameras' slices in ONE launch (three accumulating copies + a copy per camera
+        # before, between the plan recognition's backward and the encoders'); demb_one_launch = False: as before
+        one = self.demb_one_launch and pr.D_in % 4 == 0 and pr.D % 4 == 0 and Ec == 32 * len(cams)
+        if one:
+            main.wait_stream(s_pp)
+            call("tacorl_plmp_demb_finish", ptr(self.d_emb), ptr(dx), pr.D, pr.D_in, ptr(self.dS), 2 * Ec, ptr(self.dgin),
+                 ops.ptr_array([self.f_dout[c] for c in cams]), len(cams), B, T, Ec, ops.stream())
+        else:
+            ops.copy_cols(dx, 0, pr.D, self.d_emb, 0, Ec, R, pr.D_in, accumulate=True)
+            main.wait_stream(s_pp)
+            ops.copy_cols(self.dS, 0, 2 * Ec, self.d_emb, 0, T * Ec, B, Ec, accumulate=True)
+            ops.copy_cols(self.dgin, 0, Ec, self.d_emb, (T - 1) * Ec, T * Ec, B, Ec, accumulate=True)
+        for j, c in enumerate(cams):
+            H, W = hw[c]
+            if not one:
+                ops.copy_cols(self.d_emb, 32 * j, Ec, self.f_dout[c], 0, 32, R, 32)
+            ops.encoder_bwd([self.frames[c]], [net.enc(c)], [self.f_act[c]], [self.f_dout[c]], [net.enc(c, net.grad)], H, W, cd,
+                            fused=stage.fused_bwd_ok((H, W), cd, self.img_dtype, [R]))
+        ops.mark("enc:bwd")
+        main.wait_stream(s_wg)
+        main.wait_stream(s_rand)
+        ops.mark("joined")
 
 
 def load_play_lmp(play_lmp_dir, epoch=-1, overwrite_cfg=None, device=None, compute_dtype="f32", image_dtype="f32",
@@ -183,348 +412,3 @@ def load_play_lmp(play_lmp_dir, epoch=-1, overwrite_cfg=None, device=None, compu
         sd = torch.load(ckpt, map_location="cpu", weights_only=False)
     mod.load_state_dict(sd.get("state_dict", sd))
     return mod
-
-
-# --------------------------------------------------------------------------- training step
-def _playlmp_ensure(self, B, T, hw):
-    key = (B, T, tuple(sorted(hw.items())))
-    if getattr(self, "_shape", None) == key:
-        return
-    from ... import ops
-
-    ops.note_alloc()
-    dev, cams, net = self.dev, self.plan_proposal_obs_modalities, self.net
-    f = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
-    R, Ec = B * T, 32 * len(cams)
-    self.frames = {c: torch.zeros(R, *hw[c], 3, device=dev, dtype=self.img_dtype) for c in cams}
-    self.f_out = {c: f(R, 32) for c in cams}
-    self.f_act = {c: f(ops.encoder_act_layout(R, *hw[c])[1]) for c in cams}
-    self.f_dout = {c: f(R, 32) for c in cams}
-    self.emb, self.d_emb = f(R, Ec), f(R, Ec)
-    self.gin, self.dgin = f(B, Ec), f(B, Ec)
-    self.gact = f(ops.mlp_act_layout(B, net.genc_dims, net.genc_acts)[2])
-    self.g_yoff = ops.mlp_act_layout(B, net.genc_dims, net.genc_acts)[1][-1]
-    self.S, self.dS = f(B, 2 * Ec), f(B, 2 * Ec)
-    self.pact = f(ops.mlp_act_layout(B, net.head_dims, net.head_acts)[2])
-    self.p_yoff = ops.mlp_act_layout(B, net.head_dims, net.head_acts)[1][-1]
-    A = self.pr.A
-    self.d_head_pp, self.d_head_pr = f(B, 2 * A), f(B, 2 * A)
-    self.plan, self.rplan, self.d_plan = f(B, A), f(B, A), f(B, A)
-    carve_plan_noise(self, B, A)
-    self.logs = f(16)  # 0 kl, 1 kl_scaled, 2 action_loss, 3 gripper_acc, 4 rand action_loss, 5 rand gripper_acc
-    self._shape = key
-
-
-def _playlmp_step(self, batch, noise=None, optimize=True, log_type="train", nchw=True):
-    """PlayLMP.training_step + the single Adam (reference play_lmp_for_rl.py:200-257,307-317,362-368)."""
-    from ... import image_ingest as ingest
-    from ... import ops
-    from ...data.replay import wait_ready
-
-    wait_ready(batch)  # a replay batch's small tables travel on the feeder's copy stream
-    f = ingest.window_form(batch, nchw)
-    B, T, hw = f.B, f.T, f.hw
-    cams, net, pr, ad = self.plan_proposal_obs_modalities, self.net, self.pr, self.ad
-    opts = getattr(self, "_optimizers", None)
-    if opts and opts[0].lr != self.lr:  # lr edited on the optimiser (scheduler): a launch argument -> new captures
-        self.lr, self._graphs = opts[0].lr, {}
-    _playlmp_ensure(self, B, T, hw)
-    R = B * T
-    gs = 1.0 / getattr(self, "world_size", 1)
-    draw_plan_noise(self, noise, B, T)
-    # ---- eager staging: frames into the fixed NHWC buffers, actions into a fixed buffer
-    for c in cams:  # the job: the window into self.frames[c] (by index straight out of the dataset: gather + pack in one pass)
-        v = f.frames[c].to(self.dev)
-        if not v.is_contiguous():
-            raise ValueError("window frames must be contiguous")
-        job = ingest.PackJob(v.data_ptr(), 3 * f.src_hw[c][0] * f.src_hw[c][1], self.frames[c].data_ptr(), R,
-                             None if f.ids is None else f.ids.data_ptr(), 1, **ingest.window_tables(f.aug, c, "window", T))
-        ingest.pack([job], f.form, self.img_dtype, f.src_hw[c], hw[c], f.aug["pad"][c] if f.aug is not None else None)
-    if getattr(self, "_acts", None) is None or self._acts.shape != batch["actions"].shape:
-        ops.note_alloc()
-        self._acts = torch.zeros(*batch["actions"].shape, device=self.dev)
-    self._acts.copy_(batch["actions"])
-    acts = self._acts
-
-    from ... import dist as D
-
-    reduce_on = optimize and D.collectives_on(getattr(self, "world_size", 1))
-    if reduce_on:
-        _grad_arena(self)  # (before anything is captured: the backward kernels write into the arena's slices)
-
-    def fwd_bwd():
-        _playlmp_fwd_bwd(self, B, T, hw, acts, gs)
-
-    def opt():
-        if optimize:
-            ops.adam_step_batch([(blk.param, blk.grad, blk.m, blk.v, self.lr, 0.0, blk.step, None, 0.0)
-                                 for blk in (net, pr.blk, ad.blk)])
-        ops.mark("end")
-
-    def reduce_grads():
-        if reduce_on:
-            D.all_reduce_sum_(_grad_arena(self))  # ONE collective: [encoders + proposal | plan recognition | action decoder]
-
-    # (a graph replay runs no python: announce the optimiser's writes to torch's version counters - ops.touched)
-    self._stepped_blocks = (lambda: [net.param, pr.blk.param, ad.blk.param]) if optimize else None
-    self._run_segments(("playlmp", B, T, tuple(sorted(hw.items())), optimize, self._pr_train), [fwd_bwd, opt], [reduce_grads])
-    # metrics cross to the host (a device synchronisation) only on logging steps - Trainer(log_every_n_steps), as the
-    # other two modules do; in between the step returns the last total it read
-    self._step_count += 1
-    # Deviation from the reference (which logs and returns the total on every step, :307-317): with log_every_n_steps = k > 1
-    # the train/* values - and their on_epoch means - come from every k-th step, and the steps in between return the last
-    # total that was read (never None: the first step always reads).
-    if (optimize and self.log_every_n_steps > 1 and self._step_count % self.log_every_n_steps
-            and self.__dict__.get("_last_total") is not None):
-        return self.__dict__["_last_total"]
-    # (sync_dist=True in the reference, :162,183,292-339: the per-rank batch means are averaged over the ranks first)
-    logs, div = D.reduce_logs_(self.logs, getattr(self, "world_size", 1))
-    lg = [x / div for x in logs.cpu().tolist()]
-    names = ["kl_loss", "kl_loss_scaled", "action_loss", "gripper_accuracy", "random_plan_action_loss",
-             "random_plan_gripper_accuracy"]
-    for k, v in zip(names, lg):
-        self.log(f"{log_type}/{k}", v, on_step=True, on_epoch=True, sync_dist=True)
-    total = lg[1] + lg[2]
-    self.log(f"{log_type}/total_loss", total, on_step=True, on_epoch=True, sync_dist=True)
-    self.__dict__["_last_total"] = total
-    return total
-
-
-
-def _playlmp_pp_forward(self, B, T, Ec, A, cd):
-    """Plan proposal: goal encoder on emb[:, -1], policy head on [emb[:, 0] | goal]; returns the (B, 2A) head view."""
-    from ... import ops
-    from ..._lib import BF16, call
-
-    net = self.net
-    # round 5: both MLP inputs - emb[:, -1] for the goal encoder, [emb[:, 0] | goal_enc] for the policy head - are gathered by
-    # the fused forwards where their producers left them (ops.mlp_fwd_gather, as the actor-critic engine does): three copy
-    # launches off this chain; the assembled rows the weight gradients read are written from the forward's registers
-    gather = (cd == BF16 and getattr(self, "fused_mlps", True) and getattr(self, "pp_gather", True)
-              and ops.mlp_fwd_gather_ok([B], net.genc_dims, net.genc_acts, Ec, cd, False)
-              and ops.mlp_fwd_gather_ok([B], net.head_dims, net.head_acts, 2 * Ec, cd, False))
-    if not gather:
-        ops.copy_cols(self.emb, (T - 1) * Ec, T * Ec, self.gin, 0, Ec, B, Ec)  # pp_goal input = emb[:, -1]
-    # bf16 mode: the goal encoder and the plan proposal's policy head run as the single-launch MLP kernels (forward, input
-    # gradients, weight gradients) on a bf16 mirror of their weights, as in the actor-critic engine.  (Per layer they are 7
-    # generic GEMM launches on this chain: hidden behind the random-plan decoder pass while that was a pass of its own -
-    # no gain then -, on the critical path since it rides in the real pass.)
-    pb_g = pb_h = None
-    if cd == BF16 and getattr(self, "fused_mlps", True):
-        import ctypes as C
-        call("tacorl_to_bf16_batch", 1, ops.ptr_array([net.genc()]), ops.ptr_array([net.genc_bf16()]),
-             (C.c_long * 1)(net.size - net.genc_off), ops.stream())
-        pb_g, pb_h = [net.genc_bf16()], [net.head_bf16()]
-    self._pp_bf16 = pb_g
-    if gather:
-        ops.mlp_fwd_gather([[(self.emb, (T - 1) * Ec, T * Ec, 0, 0)]], [self.gin], Ec, [net.genc()], pb_g, [self.gact], [B],
-                           net.genc_dims, net.genc_acts)
-        ops.mlp_fwd_gather([[(self.emb, 0, T * Ec, 0, 0), (self.gact, self.g_yoff, Ec, Ec, 0)]], [self.S], 2 * Ec, [net.head()], pb_h,
-                           [self.pact], [B], net.head_dims, net.head_acts)
-        return self.pact[self.p_yoff: self.p_yoff + B * 2 * A]
-    ops.mlp_fwd([self.gin], Ec, [net.genc()], [self.gact], [B], net.genc_dims, net.genc_acts, cd, params_bf16=pb_g)
-    ops.copy_cols(self.emb, 0, T * Ec, self.S, 0, 2 * Ec, B, Ec)  # pp_state = emb[:, 0]
-    ops.copy_cols(self.gact, self.g_yoff, Ec, self.S, Ec, 2 * Ec, B, Ec)
-    ops.mlp_fwd([self.S], 2 * Ec, [net.head()], [self.pact], [B], net.head_dims, net.head_acts, cd, params_bf16=pb_h)
-    return self.pact[self.p_yoff: self.p_yoff + B * 2 * A]
-
-
-def _playlmp_fwd_bwd(self, B, T, hw, acts, gs):
-    """Device side of the PlayLMP step up to the gradients (fixed buffers only: hipGraph-capturable)."""
-    from ... import ops
-    from ..._lib import BF16, call, ptr
-
-    cams, net, pr, ad = self.plan_proposal_obs_modalities, self.net, self.pr, self.ad
-    R, Ec, A, cd = B * T, 32 * len(cams), pr.A, self.compute
-    xd = stage.image_flag(self.img_dtype)
-    ops.mark("start")
-    for j, c in enumerate(cams):
-        H, W = hw[c]
-        # (the fused forward only where the LDS-resident backward follows it: one predicate for forward and backward)
-        if stage.fused_bwd_ok((H, W), cd, self.img_dtype, [R]):
-            # one launch for the whole encoder, activations saved for the backward (encoder_fused.hip); the pack in front of
-            # it is unconditional - part of the captured step, whatever the version stamps say
-            self.enc_packs.pack([(net, c)])
-            call("tacorl_encoder_fwd_fused", 1, ops.ptr_array([self.frames[c]]), ops.ptr_array([self.enc_packs.buffer(net, c)]),
-                 ops.ptr_array([net.enc(c)]), ops.ptr_array([self.f_out[c]]), ops.ptr_array([self.f_act[c]]),
-                 ops.int_array([R]), H, W, ops.stream())
-        else:
-            call("tacorl_encoder_fwd", 1, ops.ptr_array([self.frames[c]]), ops.ptr_array([net.enc(c)]),
-                 ops.ptr_array([self.f_out[c]]), ops.ptr_array([self.f_act[c]]), ops.int_array([R]), H, W, xd, cd,
-                 ops.stream())
-        ops.copy_cols(self.f_out[c], 0, 32, self.emb, 32 * j, Ec, R, 32)
-    ops.mark("encoded")
-    # Branches (torch streams: branches of the captured graph).  The step is a long chain of small kernels; what does not
-    # depend on each other runs side by side: the logging-only random-plan decoder pass beside the plan proposal /
-    # recognition forward, the plan proposal's backward beside the decoder's, the decoder's and the plan recognition's
-    # weight gradients beside the BPTT / input-gradient chains and the encoder backward.  (Scratch buffers are per network - "ad_*" tags - so branches do not share any.)
-    if getattr(self, "_branch", None) is None:
-        self._branch = [torch.cuda.Stream(device=self.dev) for _ in range(3)]
-    main = torch.cuda.current_stream()
-    s_rand, s_pp, s_wg = self._branch if getattr(self, "branches", True) else [main] * 3  # tests switch the branches off
-    # logging-only pass with a uniform random plan (reference :243-252) - before the real pass, whose activations
-    # are the ones the backward sees (the decoder's buffers are shared: the real pass waits for this branch)
-    # Where the ring-GEMM path runs (bf16), the random-plan pass is not a pass of its own: its rows ride in the launches of
-    # the real pass (same weights, read once - ActionDecoderLogistic.twin_*); only its input projection and its loss
-    # stay on the branch.
-    twin, ad_prepared, pr_ready = None, False, None
-    s_rand.wait_stream(main)
-    with torch.cuda.stream(s_rand):
-        if cd == BF16 and not getattr(self, "_pr_train", False) and getattr(self, "early_prepare", True):
-            # weights only: the plan recognition's bf16 mirror and its composed posterior head, beside the encoder's tail
-            pr.prepare_inference()
-            pr_ready = torch.cuda.Event()
-            pr_ready.record(s_rand)
-            # (NOT pr.prepare_backward(): its transposes ride on the weight-gradient stream, behind the decoder's weight
-            # gradients - the plan recognition's backward then waits for those, and that serialisation is faster: see there)
-        call("tacorl_uniform_actions", ptr(self.noise["u_plan"]), ptr(self.rplan), A, B, A, 0, ops.stream())
-        if ad.twin_ok(B, cd):
-            twin = ad.twin_input_proj(self.rplan, self.emb, Ec, B, T, T - 1)
-            # weights-only preparation of the real pass and of the backward rides on this branch (joined before the pass)
-            ad.refresh_mirrors(B, T - 1)
-            ad_prepared = ad.prepare_backward(B, T - 1, cd) if getattr(self, "early_prepare", True) else False
-            ops.mark("rand:prepared")
-        else:
-            ad.forward(self.rplan, self.emb, Ec, B, T, T - 1, cd)
-            ad.loss(acts, ops._at(self.logs, 4), B, T, T - 1, want_grad=False)
-    # The plan proposal's forward (goal encoder -> policy head: a dependent chain of its own, ~55 us at B = 32) needs only the
-    # embeddings, like the plan recognition - but on its own branch beside the plan recognition's launch, joined at the KL,
-    # the step is SLOWER (1.252 -> 1.302 ms at B = 32, 2.365 -> 2.410 at B = 256, same-process A/B): a third concurrent
-    # branch at that point (the early preparation branch is still running) costs more than the 55 us it hides.  In line.
-    pp_side = s_pp if getattr(self, "pp_forward_side", False) else main
-    pp_side.wait_stream(main)
-    with torch.cuda.stream(pp_side):
-        head_pp = _playlmp_pp_forward(self, B, T, Ec, A, cd)
-    ops.mark("pp_fwd")
-    if pr_ready is not None:
-        main.wait_event(pr_ready)
-    head_pr = pr.forward(self.emb, Ec, B, T, cd, train=getattr(self, "_pr_train", False), prepared=pr_ready is not None,
-                         sample=(self.noise["eps_plan"], self.plan) if pr_ready is not None else None)
-    main.wait_stream(pp_side)
-    pb_g = self._pp_bf16
-    call("tacorl_gauss_kl_balanced", ptr(head_pr), ptr(head_pp), ptr(self.d_head_pr), ptr(self.d_head_pp), B, A,
-         float(self.kl_alpha), float(self.kl_beta), float(pr.min_std), int(self.kl_balancing), gs, ptr(self.logs),
-         ops.stream())
-    ops.mark("kl")
-    # plan proposal backward (needs only the KL's gradient): its own branch; d_emb gets its share after the join
-    s_pp.wait_stream(main)
-    with torch.cuda.stream(s_pp):
-        def mlp_backward(tag, x, ldx, par, act, d_out, ldo, grad, d_x, ldd, dims, acts):
-            if pb_g is not None and ops.mlp_bwd_fused_ok(1, dims, ldo, ldd, cd):
-                ops.mlp_bwd_fused_dgrad([par], [act], [d_out], ldo, [d_x], ldd, [B], dims, acts, "plmp_" + tag)
-                ops.mlp_bwd_fused_wgrad([x], ldx, [act], [d_out], ldo, [grad], [B], dims, acts, "plmp_" + tag)
-            else:
-                ops.mlp_bwd([x], ldx, [par], [act], [d_out], ldo, [grad], [d_x], ldd, [B], dims, acts, cd, ws_tag="plmp_" + tag)
-
-        mlp_backward("pp", self.S, 2 * Ec, net.head(), self.pact, self.d_head_pp, 2 * A, net.head(net.grad), self.dS, 2 * Ec,
-                     net.head_dims, net.head_acts)
-        mlp_backward("genc", self.gin, Ec, net.genc(), self.gact, ops._at(self.dS, Ec), 2 * Ec, net.genc(net.grad), self.dgin, Ec,
-                     net.genc_dims, net.genc_acts)
-    if pr_ready is None:  # (otherwise pr.forward sampled the plan - inside its one launch where that path runs)
-        call("tacorl_pr_sample", ptr(head_pr), ptr(self.noise["eps_plan"]), ptr(self.plan), None, None, B, A,
-             float(pr.min_std), ops.stream())
-    main.wait_stream(s_rand)
-    ops.mark("ad:start")
-    # (mirrors_current: the branch above has refreshed the bf16 mirrors of the weights - in the random-plan pass of its own, or explicitly)
-    ad.forward(self.plan, self.emb, Ec, B, T, T - 1, cd, mirrors_current=True, twin=twin)
-    if twin is not None:
-        s_rand.wait_stream(main)
-        with torch.cuda.stream(s_rand):
-            ad.twin_heads(twin, B, T - 1)  # (the random pass's heads and loss: off the real pass's chain)
-            ad.loss(acts, ops._at(self.logs, 4), B, T, T - 1, want_grad=False, twin=twin)
-    ad.loss(acts, ops._at(self.logs, 2), B, T, T - 1, want_grad=True, grad_scale=gs)
-    if self.add_random_plan_loss:
-        raise NotImplementedError("add_random_plan_loss=True is not used by any in-scope config")
-    ops.mark("ad:loss")
-    # ---- backward
-    ad.backward(B, T - 1, cd, need_input_grad=True, wgrad_stream=s_wg, join=False, prepared=ad_prepared)
-    if ad.E == Ec:  # (the decoder sees every camera's embedding: its share defines the whole block - no fill launch in front)
-        call("tacorl_ad_input_bwd", ptr(ad.dx_seq), ptr(self.d_plan), ptr(self.d_emb), Ec, B, T, T - 1, ad.P, ad.E, 2,
-             ops.stream())
-    else:
-        self.d_emb.zero_()
-        call("tacorl_ad_input_bwd", ptr(ad.dx_seq), ptr(self.d_plan), ptr(self.d_emb), Ec, B, T, T - 1, ad.P, ad.E, 1,
-             ops.stream())
-    ops.mark("ad:bwd")
-    call("tacorl_pr_sample_bwd", ptr(head_pr), ptr(self.noise["eps_plan"]), ptr(self.d_plan), ptr(self.d_head_pr), B, A,
-         float(pr.min_std), ops.stream())
-    dx = pr.backward(self.d_head_pr, B, T, cd, wgrad_stream=s_wg)
-    ops.mark("pr:bwd")
-    # round 5: the four shares of d_emb and the cameras' slices in ONE launch (three accumulating copies + a copy per camera
-    # before, between the plan recognition's backward and the encoders'); demb_one_launch = False: as before
-    one = getattr(self, "demb_one_launch", True) and pr.D_in % 4 == 0 and pr.D % 4 == 0 and Ec == 32 * len(cams)
-    if one:
-        main.wait_stream(s_pp)
-        call("tacorl_plmp_demb_finish", ptr(self.d_emb), ptr(dx), pr.D, pr.D_in, ptr(self.dS), 2 * Ec, ptr(self.dgin),
-             ops.ptr_array([self.f_dout[c] for c in cams]), len(cams), B, T, Ec, ops.stream())
-    else:
-        ops.copy_cols(dx, 0, pr.D, self.d_emb, 0, Ec, R, pr.D_in, accumulate=True)
-        main.wait_stream(s_pp)
-        ops.copy_cols(self.dS, 0, 2 * Ec, self.d_emb, 0, T * Ec, B, Ec, accumulate=True)
-        ops.copy_cols(self.dgin, 0, Ec, self.d_emb, (T - 1) * Ec, T * Ec, B, Ec, accumulate=True)
-    for j, c in enumerate(cams):
-        H, W = hw[c]
-        if not one:
-            ops.copy_cols(self.d_emb, 32 * j, Ec, self.f_dout[c], 0, 32, R, 32)
-        ops.encoder_bwd([self.frames[c]], [net.enc(c)], [self.f_act[c]], [self.f_dout[c]], [net.enc(c, net.grad)], H, W, cd,
-                        fused=stage.fused_bwd_ok((H, W), cd, self.img_dtype, [R]))
-    ops.mark("enc:bwd")
-    main.wait_stream(s_wg)
-    main.wait_stream(s_rand)
-    ops.mark("joined")
-
-
-def _named_gradients(self):
-    out = {}
-    for k, v in self.net.grad_views.items():
-        if k.startswith("encoder."):
-            out["perceptual_encoder." + k[len("encoder."):]] = v
-        elif k.startswith("actor.policy."):
-            out["plan_proposal.policy." + k[len("actor.policy."):]] = v
-        else:
-            out[k] = v
-    out.update({f"plan_recognition.{k}": v for k, v in self.pr.blk.grad_views.items()})
-    out.update({f"action_decoder.{k}": v for k, v in self.ad.blk.grad_views.items()})
-    return out
-
-
-def _grad_arena(self):
-    """The three blocks' gradients as slices of one allocation (made on first use, i.e. only with several ranks)."""
-    a = self.__dict__.get("_grad_arena_t")
-    if a is None:
-        from ... import ops
-
-        blks = (self.net, self.pr.blk, self.ad.blk)
-        ops.note_alloc()
-        a = torch.zeros(sum(b.size for b in blks), device=self.dev)
-        o = 0
-        for b in blks:
-            b.rebind_grad(a[o: o + b.size])
-            o += b.size
-        self.__dict__["_grad_arena_t"] = a
-    return a
-
-
-def _training_step(self, batch, batch_idx=0, noise=None):
-    """reference :307-317 (returns the total loss; the optimiser step has already run - manual optimisation)."""
-    out = _playlmp_step(self, batch, noise, True, "train")
-    self._tick_optimizers()
-    return out
-
-
-def _validation_step(self, batch, batch_idx=0, noise=None):
-    return _playlmp_step(self, batch, noise, False, "validation")
-
-
-def _configure_optimizers(self):
-    """reference :362-368: ONE Adam over every parameter.  A BlockAdam spanning the three flat blocks."""
-    ent = [(blk, self._pv[k], blk.views_of(blk.m), blk.views_of(blk.v))
-           for k, blk in (("net", self.net), ("pr", self.pr.blk), ("ad", self.ad.blk))]
-    self._optimizers = [self._make_adam("adam", ent, self.lr)]
-    return self._optimizers[0]
-
-
-PlayLMP.training_step = _training_step
-PlayLMP.validation_step = _validation_step
-PlayLMP.named_gradients = _named_gradients
-PlayLMP.configure_optimizers = _configure_optimizers

@@ -17,7 +17,7 @@ import torch
 from ... import dist as _D
 from ... import image_ingest as ingest
 from ...lightning import LightningModuleBase
-from ..common import GraphMixin, ModuleMixin, broadcast_blocks, register_views, to_plain
+from ..common import GraphMixin, ModuleMixin, register_views, to_plain
 from .engine import SLOTS, RILEngine
 
 
@@ -71,12 +71,8 @@ class RelayImitationLearning(GraphMixin, ModuleMixin, LightningModuleBase):
 
         attach_ril_rollout_surface(self, self.engine)
 
-    def sync_from_rank0(self):
-        """Broadcast rank 0's parameters and optimiser state (PL's DDP wrap does this for the reference module)."""
-        from ... import ops
-
-        broadcast_blocks([self.engine.blk])
-        ops.touched(self.engine.blk.param)
+    def _blocks(self):
+        return [self.engine.blk]
 
     def _stepped_blocks(self):
         return [self.engine.blk.param]

@@ -8,29 +8,15 @@ mirror its layers and hidden size.  The batch: `observations` (B,T,29), `actions
 or a fused replay batch `{"replay": ...}` (data/d4rl_replay.py), whose sampler launch writes the step's buffers itself.
 Select with `module._target_=tacorl_amd.modules.tacorl.tacorl_d4rl.TACORL`.
 """
-from pathlib import Path
-
 import torch
 
-from ... import dist as D
 from ... import ops
 from ..common import register_views
 from ..cql.cql_offline_lightning_d4rl import CQL_Offline
+from .latent_plan import LatentPlanShell
 
 
-class TACORL(CQL_Offline):
-    def __init__(self, play_lmp_dir: str = "~/tacorl/models/play_lmp", lmp_epoch_to_load: int = -1,
-                 overwrite_lmp_cfg: dict = {}, finetune_action_decoder: bool = False, action_decoder_lr: float = 1e-4, *args,
-                 play_lmp=None, **kwargs):
-        self.play_lmp_dir = Path(play_lmp_dir).expanduser()
-        self.lmp_epoch_to_load = lmp_epoch_to_load
-        self.overwrite_lmp_cfg = overwrite_lmp_cfg
-        self.finetune_action_decoder = finetune_action_decoder
-        self.action_decoder_lr = action_decoder_lr
-        self.lmp_unsafe_pickle = bool(kwargs.pop("lmp_unsafe_pickle", False))
-        self.__dict__["_play_lmp"] = play_lmp  # nn.Module: must not be registered as a sub-module
-        super().__init__(*args, **kwargs)
-
+class TACORL(LatentPlanShell, CQL_Offline):
     # ------------------------------------------------------------------ construction
     def build_networks(self):
         """reference :40-66."""
@@ -47,34 +33,20 @@ class TACORL(CQL_Offline):
             raise ValueError(f"the LMP was built for state_dim {lmp.state_dim}, this module for {self.state_dim}")
         cfgcheck.check_critic(self.critic_cfg, "critic")  # layers / hidden mirror the actor's (:53-54)
         self.pr, self.ad = lmp.pr, lmp.ad
-        # (registered in the reference's order: action_decoder, plan_recognition, actor, q1, q2, targets)
-        ad_pv = register_views(self, "action_decoder.", self.ad.blk.views)
-        for k, v in self.ad.buffers.items():
-            self.action_decoder.register_buffer(k, v)
-        register_views(self, "plan_recognition.", self.pr.blk.views, requires_grad=False)  # :66
         self.action_dim = lmp.pr.latent_plan_dim  # the RL action is the latent plan (:57)
         a = dict(policy_layers=lmp.policy_layers, q_layers=lmp.policy_layers, hidden=lmp.hidden, discrete_gripper=False)
         self._make_vec_engine(self.state_dim, self.goal_dim, self.action_dim, a)
         e = self.engine
+        # (registered in the reference's order: action_decoder, plan_recognition, actor, q1, q2, targets)
+        self._adopt_decoder()
+        register_views(self, "plan_recognition.", self.pr.blk.views, requires_grad=False)  # :66
         e.actor.param.copy_(lmp.pp.param)  # actor = the LMP's plan proposal (:51)
         for q in (e.q1, e.q2):
             init_views_(q.views)
         self.sync_targets()
         self._register()
         self._attach_rollout(ad=self.ad)
-        self._pv["action_decoder"] = ad_pv
-        e.pre_metrics = [self.ad.finish_loss]  # (the decoder loss leaves its partial sums on the device: loss(lazy=True))
-        if self.finetune_action_decoder:
-            # the decoder's gradients join [actor | q1 | q2 | log_alpha'] in the engine's arena: with several GPUs the step's
-            # second all-reduce covers them
-            e.extend_arena(self.ad.blk)
         self._acts = None
-
-    def named_gradients(self):
-        out = super().named_gradients()
-        if self.finetune_action_decoder:
-            out.update({f"action_decoder.{k}": v for k, v in self.ad.blk.grad_views.items()})
-        return out
 
     # ---------------------------------------------------------------------- stepping
     def _stage_replay(self, rb, noise):
@@ -115,16 +87,6 @@ class TACORL(CQL_Offline):
         e.set_noise(noise)
         return B, T
 
-    def _defer_ad_update(self):
-        """More than one rank (or the split-graph test mode): the fine-tuned decoder's Adam step waits for the arena's
-        all-reduce.  On one GPU it stays on the decoder's own branch of the step's graph."""
-        return D.collectives_on(self.world_size) or getattr(self, "_force_graph_split", False)
-
-    def _join_ad(self):
-        if getattr(self, "_ad_join", None) is not None:
-            torch.cuda.current_stream().wait_stream(self._ad_join)
-            self._ad_join = None
-
     def _device_front(self, B, T, optimize):
         """Graph-capturable: plan recognition -> plan; the decoder's loss (and backward) as a branch beside the first phase of
         the CQL update, which does not need the plan."""
@@ -151,13 +113,6 @@ class TACORL(CQL_Offline):
         self.pr.forward(e.obs, self.state_dim, B, T, self.compute, inference=True, sample=(self.eps_pr, e.action), frozen=True)
         return e.action
 
-    def training_step(self, batch, batch_idx=0, noise=None):
-        self._step(batch, noise, optimize=True, log_type="train")
-        self._tick_optimizers()
-
-    def validation_step(self, batch, *args, noise=None, **kwargs):
-        self._step(batch, noise, optimize=False, log_type="validation")
-
     def _step(self, batch, noise, optimize, log_type):
         self._sync_lrs()
         B, T = self._stage(batch, noise)
@@ -179,11 +134,3 @@ class TACORL(CQL_Offline):
                            [lambda: self._device_front(B, T, optimize), lambda: e.phase_b(bc, optimize), tail],
                            [e.allreduce_alpha, allreduce_grads])
         self._publish_logs(log_type, extra=("action_loss",))
-
-    def configure_optimizers(self):
-        o = super().configure_optimizers()
-        if self.finetune_action_decoder:  # reference :162-173
-            blk = self.ad.blk
-            o.append(self._make_adam("action_decoder", [(blk, self._pv["action_decoder"], blk.views_of(blk.m),
-                                                         blk.views_of(blk.v))], self.action_decoder_lr))
-        return o

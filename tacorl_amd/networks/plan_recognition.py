@@ -84,7 +84,8 @@ class PlanRecognition:
         """Fill the keep masks of the next train-mode forward (eager, before a graph replay - like the step's other
         noise).  masks: the reference's draws in its order and layouts (sequence-major (T,B,*) for the activations,
         (B,H,T,T) for the attention probabilities); None: fresh Bernoulli(1 - p) draws from torch's device generator.
-        (With a device-noise seed the owning step fills keep_flat itself, with its other noise: modules/common.draw_plan_noise.)"""
+        (With a device-noise seed the owning step fills keep_flat itself, with its other noise: modules/play_lmp/shell.py
+        PlayLMPShell.draw_plan_noise.)"""
         self._ensure(B, T)
         if self.keep is None:
             return
