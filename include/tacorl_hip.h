@@ -627,6 +627,16 @@ int tacorl_pr_encoder_fused_sample(const float* emb, int ld_emb, const float* pa
                                    const long* offsets, float* pooled, int B, int D, int T, int H, int FF, int L,
                                    const float* Wc, const float* bc, const float* eps, float* head, float* plan,
                                    int A, float min_std, tacorl_stream_t stream);
+/* tacorl_pr_encoder_fused_sample that also writes the action decoder's bf16 input rows behind each sequence's plan sample -
+ * bit for bit what tacorl_build_ad_input_bf16(plan, emb_ad, ld_ad, xb_seq, B, T, Tm, P, E) writes in a launch of its own
+ * behind this one: xb_seq[(t B + b)][0..127] = bf16([plan_b | emb_ad[b T + t][0..E) | 0 ...]) for t < Tm; rows t >= Tm are not
+ * touched.  d_model 32; P == A, P % 8 == 0, P + E <= 128, 1 <= Tm <= T, ld_ad >= E, xb_seq 16-byte aligned - TACORL_EINVAL
+ * otherwise, nothing launched. */
+int tacorl_pr_encoder_fused_sample_rows(const float* emb, int ld_emb, const float* params, const void* params_bf16,
+                                        const long* offsets, float* pooled, int B, int D, int T, int H, int FF, int L,
+                                        const float* Wc, const float* bc, const float* eps, float* head, float* plan,
+                                        int A, float min_std, void* xb_seq, int Tm, int P, int E, const float* emb_ad,
+                                        int ld_ad, tacorl_stream_t stream);
 /* Train mode of the same launch (PlayLMP.training_step with plan-recognition dropout 0): additionally writes, per layer, the
  * tensors the per-op backward reads, in the per-op forward's layouts (fp32, batch-major rows).  save[9 l + k], k = 0..8: layer
  * input [B T][32], q|k|v [B T][96], attention output [B T][32], out-projection [B T][32], LayerNorm-1 output [B T][32],

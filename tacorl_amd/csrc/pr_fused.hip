@@ -7,10 +7,11 @@
 // split-K FFN2 + reduce, add+LayerNorm) of a few microseconds of work each: ~180 us for two layers on the
 // step's longest dependent chain.  With d_model 32 and T = 16 a whole sequence is one 16-row MFMA tile, so
 // here one WORKGROUP owns one sequence for all layers: activations stay in registers (MFMA D layout: lane =
-// row, 4 consecutive features) and wave-private LDS scratch.  The four waves run the attention half of a
-// layer redundantly (no synchronisation) and split the FFN by hidden chunks; their partial outputs meet in
-// LDS behind the only workgroup barrier of a layer.  Weights are the MFMA A operand, streamed from global
-// memory (FFN matrices from a bf16 mirror of the parameter block, one phase ahead of their use).
+// row, 4 consecutive features) and wave-private LDS scratch.  The four waves split the attention by heads
+// (wave w: heads 2 w, 2 w + 1; their results meet in a shared out-projection operand behind one workgroup
+// barrier) and the FFN by hidden chunks; the partial FFN outputs meet in LDS behind the layer's second barrier.
+// Weights are the MFMA A operand, streamed from global memory (FFN matrices from a bf16 mirror of the parameter
+// block, one phase ahead of their use).
 // Optionally the posterior head (fc -> mean_fc composed into one 2A x 32 affine map) and the plan sample
 // ride in the same launch.  B = 256: 34 us (one wave per sequence on a quarter of the CUs: 81 us).
 #include <hip/hip_runtime.h>
@@ -21,9 +22,6 @@
 
 namespace {
 
-#ifndef PR_W2TOP
-#define PR_W2TOP 0  // 1: 510 registers - nothing else fits on a CU beside a plan-recognition workgroup (see DESIGN, round 5)
-#endif
 constexpr int PR_D = 32, PR_T = 16, PR_H = 8, PR_HD = 4, PR_MAXL = 4, PR_CH = 256;
 constexpr int XB_P = 40;    // bf16 row pitch of the 32-wide MFMA B operand (80 B: conflict-free b128 reads)
 constexpr int HB_P = 264;   // bf16 row pitch of one FFN hidden chunk
@@ -53,6 +51,11 @@ struct PrArgs {
   float min_std;
   PrSaveL sv[PR_MAXL];
   int save;
+  // optional: the action decoder's bf16 input rows of this sequence, written behind the plan sample (null when unused):
+  // xrow[(t B + b)][0..127] = bf16([plan_b | xemb[b T + t][0..x_E) | 0 ...]) for t < x_Tm  (tacorl_build_ad_input_bf16's rows)
+  __bf16* xrow;
+  const float* xemb;
+  int x_ld, x_Tm, x_P, x_E;
 };
 
 __device__ __forceinline__ bf16x8 cvt8(const float* p) {
@@ -141,10 +144,14 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
   __shared__ __attribute__((aligned(16))) __bf16 xb_s[4][T * XB_P];
   __shared__ __attribute__((aligned(16))) unsigned char big_s[4][T * HB_P * 2];  // q|k|v (fp32) or FFN hidden chunk (bf16)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
-  // One workgroup per sequence.  Its four waves each run the (cheap) attention half of a layer redundantly on
-  // private scratch and split the FFN - two thirds of the work, 256 KB of weights per layer - by hidden chunks
-  // (wave w: chunks w, w + 4, ...); the partial FFN outputs meet in LDS once per layer.  B workgroups instead
-  // of B / 4: at B = 256 the launch covers every CU instead of a quarter of them.
+  // One workgroup per sequence.  Its four waves split the attention by heads - wave w owns heads 2 w and 2 w + 1: the
+  // q / k / v column tiles that hold them, 2 T (head, query) pairs, one per lane (T = 16: the upper half of the wave
+  // repeats the lower one and does not store) - and write their 8 columns of the result into xatt, the shared operand of
+  // the out-projection (as pr_encoder_fused64_kernel; redundant on the four waves before: every lane read k and v of every
+  // key as broadcast ds_read_b128, four waves at once).  The FFN - two thirds of the work, 256 KB of weights per layer -
+  // is split by hidden chunks (wave w: chunks w, w + 4, ...); the partial FFN outputs meet in LDS once per layer.
+  // B workgroups instead of B / 4: at B = 256 the launch covers every CU instead of a quarter of them.
+  __shared__ __attribute__((aligned(16))) __bf16 xatt[T * XB_P];
   __shared__ __attribute__((aligned(16))) float ypart[2][4][T * PR_D];  // [layer parity][wave]
   // this wave's FFN1 biases of the layer (its chunks w, w + 4: up to PR_B1C chunks of 256), fetched with the layer's other
   // operands and parked here: read where the 16 column tiles of a chunk need them, they were one more exposed global
@@ -187,7 +194,9 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
             bf16x4{(__bf16)v[rt][nt][0], (__bf16)v[rt][nt][1], (__bf16)v[rt][nt][2], (__bf16)v[rt][nt][3]};
   };
   const int nchunk = a.FF / PR_CH;
-  const bool sv0 = a.save && w == 0;  // (the attention half runs redundantly on all four waves: wave 0 writes the saves)
+  const bool sv0 = a.save && w == 0;  // (what every wave holds alike, wave 0 saves; q|k|v and the attention: each wave its heads)
+  const int qt = w >> 1;              // this wave's heads sit in column tile qt of each of q, k, v ...
+  const bool svq = a.save && (g >> 1) == (w & 1);  // ... in the column groups g = 2 (w & 1), 2 (w & 1) + 1 of that tile
   long rrow[RT];                      // this lane's batch-major rows
 #pragma unroll
   for (int rt = 0; rt < RT; rt++) rrow[rt] = (long)b * T + 16 * rt + i;
@@ -199,12 +208,13 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
     // W1 fragments.  Each used to be fetched where it is consumed, behind an LDS wait that also fences memory: five
     // dependent round trips per layer on a kernel that is nothing but latency (~1.5 us each with 1 024 waves asking for
     // the same lines) - and this launch is on the critical path of BOTH chains of the training step.
-    bf16x8 inw[6], outw[2];
-    f32x4 inb[6], outb[2], n1w[2], n1b[2], n2w[2], n2b[2], b2v[2];
+    bf16x8 inw[3], outw[2];
+    f32x4 inb[3], outb[2], n1w[2], n1b[2], n2w[2], n2b[2], b2v[2];
 #pragma unroll
-    for (int nt = 0; nt < 6; nt++) {
-      inw[nt] = *reinterpret_cast<const bf16x8*>(a.Pb + o.in_w + (long)(16 * nt + i) * PR_D + 8 * g);
-      inb[nt] = *reinterpret_cast<const f32x4*>(a.P + o.in_b + 16 * nt + 4 * g);
+    for (int k3 = 0; k3 < 3; k3++) {
+      const int nt = 2 * k3 + qt;
+      inw[k3] = *reinterpret_cast<const bf16x8*>(a.Pb + o.in_w + (long)(16 * nt + i) * PR_D + 8 * g);
+      inb[k3] = *reinterpret_cast<const f32x4*>(a.P + o.in_b + 16 * nt + 4 * g);
     }
 #pragma unroll
     for (int nt = 0; nt < 2; nt++) {
@@ -231,13 +241,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
         b1pre[j] = *reinterpret_cast<const f32x4*>(a.P + o.b1 + PR_CH * (c < nchunk ? c : c0) + 4 * lane);
       }
     }
-    if (RT == 1 && PR_W2TOP) {  // (window 16: 64 more registers fit - the first chunk's W2 fragments travel with the rest)
-#pragma unroll
-      for (int ks = 0; ks < 8; ks++)
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++)
-          w2f[ks][nt] = *reinterpret_cast<const bf16x8*>(W2 + (long)(16 * nt + i) * a.FF + PR_CH * c0 + 32 * ks + 8 * g);
-    }
     if (sv0) {
 #pragma unroll
       for (int rt = 0; rt < RT; rt++)
@@ -245,7 +248,7 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
         for (int nt = 0; nt < 2; nt++) *reinterpret_cast<f32x4*>(S.xin + rrow[rt] * PR_D + 16 * nt + 4 * g) = x[rt][nt];
     }
     PR_STAMP(0);
-    // ---- q|k|v = x Win^T + b  (6 N tiles, K = 32)
+    // ---- q|k|v = x Win^T + b  (this wave's 3 of the 6 N tiles, K = 32)
     put_xb(x);
     lds_sync();
     {
@@ -253,24 +256,24 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
 #pragma unroll
       for (int rt = 0; rt < RT; rt++) xf[rt] = *reinterpret_cast<const bf16x8*>(xb + (16 * rt + i) * XB_P + 8 * g);
 #pragma unroll
-      for (int nt = 0; nt < 6; nt++) {
-        const bf16x8 wf = inw[nt];
-        const f32x4 bias = inb[nt];
+      for (int k3 = 0; k3 < 3; k3++) {
+        const int nt = 2 * k3 + qt;
+        const bf16x8 wf = inw[k3];
+        const f32x4 bias = inb[k3];
 #pragma unroll
         for (int rt = 0; rt < RT; rt++) {
           f32x4 acc = bias;
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, xf[rt], acc, 0, 0, 0);
           *reinterpret_cast<f32x4*>(qkv + (16 * rt + i) * QKV_P + 16 * nt + 4 * g) = acc;
-          if (sv0) *reinterpret_cast<f32x4*>(S.qkv + rrow[rt] * 3 * PR_D + 16 * nt + 4 * g) = acc;
+          if (svq) *reinterpret_cast<f32x4*>(S.qkv + rrow[rt] * 3 * PR_D + 16 * nt + 4 * g) = acc;
         }
       }
     }
     lds_sync();
     PR_STAMP(1);
-    // ---- attention: 8 heads x T queries = 8 T (head, query) pairs, 2 RT per lane; result -> xb (bf16)
-#pragma unroll
-    for (int j = 0; j < 2 * RT; j++) {
-      const int p = lane + 64 * j, h = p / T, qi = p % T;
+    // ---- attention: this wave's 2 heads x T queries = 2 T (head, query) pairs, one per lane; result -> xatt (bf16)
+    {
+      const int p = lane & (2 * T - 1), h = 2 * w + p / T, qi = p % T;
       f32x4 q = *reinterpret_cast<const f32x4*>(qkv + qi * QKV_P + PR_HD * h);
       // 1 / sqrt(head_dim) and log2(e) in one factor: softmax(s) = 2^(s' - max s') / sum, s' = s log2 e (v_exp_f32 is 2^x;
       // expf was ~15 instructions and the 16 IEEE divisions by the sum ~11 each, per (head, query) pair, on all four waves)
@@ -295,16 +298,19 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; e++) ov[e] += pr * vv[e];
       }
-      *reinterpret_cast<bf16x4*>(xb + qi * XB_P + PR_HD * h) = bf16x4{(__bf16)ov[0], (__bf16)ov[1], (__bf16)ov[2], (__bf16)ov[3]};
-      if (sv0) *reinterpret_cast<f32x4*>(S.att + ((long)b * T + qi) * PR_D + PR_HD * h) = ov;
+      if (lane < 2 * T) {
+        *reinterpret_cast<bf16x4*>(xatt + qi * XB_P + PR_HD * h) = bf16x4{(__bf16)ov[0], (__bf16)ov[1], (__bf16)ov[2], (__bf16)ov[3]};
+        if (a.save) *reinterpret_cast<f32x4*>(S.att + ((long)b * T + qi) * PR_D + PR_HD * h) = ov;
+      }
     }
-    lds_sync();
+    __syncthreads();  // the four waves' columns of the attention result (the previous layer's readers of xatt passed the
+                      // barrier of its FFN exchange)
     PR_STAMP(2);
     // ---- out-projection + residual + LayerNorm 1
     {
       bf16x8 af[RT];
 #pragma unroll
-      for (int rt = 0; rt < RT; rt++) af[rt] = *reinterpret_cast<const bf16x8*>(xb + (16 * rt + i) * XB_P + 8 * g);
+      for (int rt = 0; rt < RT; rt++) af[rt] = *reinterpret_cast<const bf16x8*>(xatt + (16 * rt + i) * XB_P + 8 * g);
 #pragma unroll
       for (int nt = 0; nt < 2; nt++) {
         const bf16x8 wf = outw[nt];
@@ -326,8 +332,7 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
         }
       }
     }
-    lds_sync();  // every lane has read its out-projection operand before xb is overwritten
-    put_xb(x);
+    put_xb(x);  // (the out-projection read xatt, not xb)
     lds_sync();
     PR_STAMP(3);
     // ---- FFN: relu(x W1^T + b1) W2^T + b2, hidden processed in chunks of 256 kept in LDS as bf16
@@ -345,15 +350,17 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
 #pragma unroll
       for (int nt = 0; nt < 2; nt++)
         y[rt][nt] = w == 0 ? b2v[nt] : f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int c = w; c < nchunk; c += 4) {
-      // this chunk's W2 fragments travel while FFN1 runs (window 16: the first chunk's came with the layer's other operands)
-      if (RT != 1 || !PR_W2TOP || c != w) {
+    // One hidden chunk: its W2 fragments travel while FFN1 runs, the wave's next chunk's W1 fragments while FFN2 runs (single
+    // buffers, filled where they fall free).  Refilling every fragment register right behind the MFMA that read it - each
+    // fragment in flight for a whole FFN half and more, the MFMAs under the wave's own loads - made the launch alone 1.8 us
+    // faster and the training step 7 us slower (profiles/pr_forward_stream.md): the launch shares the chip with the step's
+    // main chain, and its FFN phase already runs at the rate at which 256 workgroups can read the same weights.
+    auto ffn_chunk = [&](const int c, const bool more) {
 #pragma unroll
-        for (int ks = 0; ks < 8; ks++)
+      for (int ks = 0; ks < 8; ks++)
 #pragma unroll
-          for (int nt = 0; nt < 2; nt++)
-            w2f[ks][nt] = *reinterpret_cast<const bf16x8*>(W2 + (long)(16 * nt + i) * a.FF + PR_CH * c + 32 * ks + 8 * g);
-      }
+        for (int nt = 0; nt < 2; nt++)
+          w2f[ks][nt] = *reinterpret_cast<const bf16x8*>(W2 + (long)(16 * nt + i) * a.FF + PR_CH * c + 32 * ks + 8 * g);
 #pragma unroll
       for (int nt = 0; nt < 16; nt++) {
         const f32x4 bias = b1_staged ? *reinterpret_cast<const f32x4*>(b1_s[w] + PR_CH * ((c - w) >> 2) + 16 * nt + 4 * g)
@@ -368,8 +375,7 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
         }
       }
       lds_sync();
-      // the next chunk's W1 fragments travel while FFN2 runs
-      if (c + 4 < nchunk) {
+      if (more) {
 #pragma unroll
         for (int nt = 0; nt < 16; nt++)
           w1f[nt] = *reinterpret_cast<const bf16x8*>(W1 + (long)(PR_CH * (c + 4) + 16 * nt + i) * PR_D + 8 * g);
@@ -384,11 +390,12 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
         }
       }
       lds_sync();  // hidden chunk consumed before the next one overwrites it
-    }
+    };
+    for (int c = w; c < nchunk; c += 4) ffn_chunk(c, c + 4 < nchunk);
     PR_STAMP(4);
     // the four partial FFN outputs meet in LDS (fixed summation order: every wave ends with the same bits).
-    // One barrier per layer: the buffer alternates with the layer, and a wave can only reach layer l + 2's write
-    // after every wave has passed layer l + 1's barrier, i.e. finished reading layer l's partials.
+    // One barrier for it per layer: the buffer alternates with the layer, and a wave can only reach layer l + 2's write
+    // after every wave has passed layer l + 1's barriers, i.e. finished reading layer l's partials.
     {
       float* yp = ypart[l & 1][w];
 #pragma unroll
@@ -411,7 +418,22 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
     for (int rt = 0; rt < RT; rt++) layer_norm32_r(x[rt], n2w, n2b, g, sv0 ? S.st2 + 2 * rrow[rt] : nullptr);
     PR_STAMP(5);
   }
-  if (w != 0) return;  // every wave holds the same result: wave 0 writes it
+  if (w != 0) {  // every wave holds the same result: wave 0 writes it
+    // ... while waves 1 - 3 write the columns of this sequence's decoder input rows that do not wait for the plan: bf16 of
+    // the frame embeddings and the zero pad, 16 bytes per lane and piece (x_P % 8 == 0: no piece holds both)
+    if (a.xrow) {
+      const int u0 = a.x_P >> 3, nu = 16 - u0, K = a.x_P + a.x_E;
+      for (int e = (int)threadIdx.x - 64; e < a.x_Tm * nu; e += 192) {
+        const int t = e / nu, c = 8 * (u0 + e - t * nu);
+        const float* er = a.xemb + ((long)b * T + t) * a.x_ld;
+        bf16x8 v;
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = (__bf16)(c + j < K ? er[c + j - a.x_P] : 0.f);
+        *reinterpret_cast<bf16x8*>(a.xrow + ((long)t * a.B + b) * 128 + c) = v;
+      }
+    }
+    return;
+  }
   // ---- mean over the T time steps (row tiles in order, then lanes i = 0..15 of each g)
 #pragma unroll
   for (int nt = 0; nt < 2; nt++) {
@@ -442,9 +464,20 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
   }
   if (lane < 2 * A) a.head[(long)b * 2 * A + lane] = h;
   const float vr = __shfl(h, (lane + A) & 63, 64);
+  float pl = 0.f;
   if (lane < A) {
     const float sd = (vr > 20.f ? vr : log1pf(expf(vr))) + a.min_std;
-    a.plan[(long)b * A + lane] = tanhf(h + heps * sd);
+    pl = tanhf(h + heps * sd);
+    a.plan[(long)b * A + lane] = pl;
+  }
+  if (!a.xrow) return;
+  // ---- the plan columns of the decoder's input rows (x_P == A): bf16 of the very floats written above, x_Tm times
+  if (lane < A) xb[lane] = (__bf16)pl;
+  lds_sync();
+  const int u0 = a.x_P >> 3;
+  for (int e = lane; e < a.x_Tm * u0; e += 64) {
+    const int t = e / u0, c = 8 * (e - t * u0);
+    *reinterpret_cast<bf16x8*>(a.xrow + ((long)t * a.B + b) * 128 + c) = *reinterpret_cast<const bf16x8*>(xb + c);
   }
 }
 
@@ -1128,10 +1161,12 @@ extern "C" int tacorl_pr_encoder_fused_train_supported(int D, int T, int H, int 
 // offsets: [position_embeddings, then per layer: in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias,
 // linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm1.weight, norm1.bias, norm2.weight, norm2.bias]
 // (element offsets into params / params_bf16, each a multiple of 4).
+struct PrRows { void* out; const float* emb; int ld, Tm, P, E; };
 static int pr_encoder_fused_launch(const float* emb, int ld_emb, const float* params, const void* params_bf16,
                                    const long* offsets, float* pooled, int B, int D, int T, int H, int FF, int L,
                                    const float* Wc, const float* bc, const float* eps, float* head, float* plan, int A,
-                                   float min_std, tacorl_stream_t stream, float* const* save = nullptr) {
+                                   float min_std, tacorl_stream_t stream, float* const* save = nullptr,
+                                   const PrRows* rows = nullptr) {
   if (!tacorl_pr_encoder_fused_supported(D, T, H, FF, L) || ld_emb % 4 || B < 1) return TACORL_EINVAL;
   if (((uintptr_t)emb | (uintptr_t)params | (uintptr_t)params_bf16 | (uintptr_t)pooled) & 15) return TACORL_EINVAL;
   PrArgs a{};
@@ -1147,6 +1182,13 @@ static int pr_encoder_fused_launch(const float* emb, int ld_emb, const float* pa
   if (Wc) {
     if (!bc || !eps || !head || !plan || A < 1 || 2 * A > 64 || ((uintptr_t)Wc & 15)) return TACORL_EINVAL;
     a.Wc = Wc; a.bc = bc; a.eps = eps; a.head = head; a.plan = plan; a.A = A; a.min_std = min_std;
+  }
+  if (rows) {
+    // (the plan columns are the sampled plan's, held by the lanes that wrote it: x_P == A, in whole 16-byte pieces; d_model 32)
+    if (!Wc || D != PR_D || !rows->out || ((uintptr_t)rows->out & 15) || !rows->emb || rows->Tm < 1 || rows->Tm > T ||
+        rows->P != A || rows->P % 8 || rows->E < 1 || rows->P + rows->E > 128 || rows->ld < rows->E)
+      return TACORL_EINVAL;
+    a.xrow = (__bf16*)rows->out; a.xemb = rows->emb; a.x_ld = rows->ld; a.x_Tm = rows->Tm; a.x_P = rows->P; a.x_E = rows->E;
   }
   if (save) {
     for (int l = 0; l < L; l++) {
@@ -1202,6 +1244,20 @@ extern "C" int tacorl_pr_encoder_fused_sample(const float* emb, int ld_emb, cons
   if (!Wc) return TACORL_EINVAL;
   return pr_encoder_fused_launch(emb, ld_emb, params, params_bf16, offsets, pooled, B, D, T, H, FF, L, Wc, bc, eps, head,
                                  plan, A, min_std, stream);
+}
+/* tacorl_pr_encoder_fused_sample that also writes the action decoder's bf16 input rows of every sequence behind its plan
+ * sample - what tacorl_build_ad_input_bf16(plan, emb_ad, ld_ad, xb_seq, B, T, Tm, P, E) would write in a launch of its own
+ * behind this one: xb_seq[(t B + b)][0..127] = bf16([plan_b | emb_ad[b T + t][0..E) | 0 ...]), t < Tm <= T; rows t >= Tm are
+ * not touched.  d_model 32, P == A, P % 8 == 0, P + E <= 128, ld_ad >= E, xb_seq 16-byte aligned: TACORL_EINVAL otherwise. */
+extern "C" int tacorl_pr_encoder_fused_sample_rows(const float* emb, int ld_emb, const float* params, const void* params_bf16,
+                                                   const long* offsets, float* pooled, int B, int D, int T, int H, int FF,
+                                                   int L, const float* Wc, const float* bc, const float* eps, float* head,
+                                                   float* plan, int A, float min_std, void* xb_seq, int Tm, int P, int E,
+                                                   const float* emb_ad, int ld_ad, tacorl_stream_t stream) {
+  if (!Wc) return TACORL_EINVAL;
+  const PrRows rows{xb_seq, emb_ad, ld_ad, Tm, P, E};
+  return pr_encoder_fused_launch(emb, ld_emb, params, params_bf16, offsets, pooled, B, D, T, H, FF, L, Wc, bc, eps, head,
+                                 plan, A, min_std, stream, nullptr, &rows);
 }
 extern "C" int tacorl_pr_head_compose(const float* w_fc, const float* b_fc, const float* w_head, const float* b_head,
                                       float* Wc, float* bc, int D, int FC, int A2, tacorl_stream_t stream) {

@@ -297,8 +297,18 @@ class TACORL(LatentPlanShell, CQL_Offline):
             if len(mods) > 1:
                 for j, c in enumerate(mods):
                     ops.copy_cols(self.f_out[c], 0, 32, self.pr_in, 32 * j, self.pr_in.shape[1], B * T, 32)
+            # the frozen decoder pass on the ring route reads bf16 rows [plan | frame embedding | 0]: the launch that samples
+            # the plan writes them (one launch less at the head of the decoder branch, which ends the step)
+            ad_rows = None
+            if (ad_on_side and not self.finetune_action_decoder and getattr(self, "pr_writes_ad_rows", True)
+                    and getattr(self.pr, "writes_ad_rows", False)):
+                xb_seq, ad_emb = self.ad.ring_rows(B, T - 1, self.compute), self.ad.module_emb(self, B, T, gather=False)
+                if xb_seq is not None and ad_emb is not None:
+                    ad_rows = (xb_seq, T - 1, self.ad.P, self.ad.E, ad_emb[0], ad_emb[1])
             # the LMP networks are frozen in TACORL (tacorl.py:52-66): their weight-only preparation is cached
-            self.pr.forward(emb, ld, B, T, self.compute, inference=True, sample=(self.eps_pr, self.plan), frozen=True)
+            self.pr.forward(emb, ld, B, T, self.compute, inference=True, sample=(self.eps_pr, self.plan), frozen=True,
+                            **({} if ad_rows is None else {"ad_rows": ad_rows}))
+            rows_current = bool(getattr(self.pr, "rows_written", False))
             ops.mark("pr:plan")
             ready = torch.cuda.Event()
             ready.record(self._pr_stream)
@@ -317,7 +327,8 @@ class TACORL(LatentPlanShell, CQL_Offline):
             self._side_stream.wait_event(ready)
             with torch.cuda.stream(self._side_stream):
                 ops.mark("ad:start")
-                self.ad.loss_step(self, self.acts, self.plan, B, T, False, frozen=not self.finetune_action_decoder)
+                self.ad.loss_step(self, self.acts, self.plan, B, T, False, frozen=not self.finetune_action_decoder,
+                                  rows_current=rows_current)
                 ops.mark("ad:end")
             self._ad_join = self._side_stream
         return ready, ad_on_side

@@ -374,8 +374,47 @@ class ActionDecoderLogistic:
              ops.ptr_array([y]), N if ldy is None else ldy, ops.int_array([M]), K, N, act, compute, ptr(ws), ws.numel(),
              ops.stream())
 
-    def forward(self, plan, emb, ld_emb, B, T, Tm, compute, frozen=False, mirrors_current=False, twin=None):
+    def _route(self, B, compute, twin=None):
+        """(fast, proj_fused, ring) of forward(): the ring-GEMM path, layer 0's projection as a launch of its own or as the
+        ring GEMM's K extension."""
+        H, K = self.hidden, self.P + self.E
+        fast = compute == ops.BF16 and bool(ops.L.lib().tacorl_rnn_linear_supported(B, H, H))
+        # (the fused projection exists only on the ring-GEMM path: with a hidden size that path does not take - H % 128 != 0 -
+        # the generic per-step path below reads x_seq, so it must be built; 32 <= K: the kernel's first k-step is unmasked)
+        proj_fused = (fast and 32 <= K <= 64 and K % 8 == 0 and H % 16 == 0 and getattr(self, "fused_input_proj", True))
+        # (the K extension of the ring GEMM takes input widths up to 128: two cameras + a 32-wide plan = 96 at C4, where the
+        # separate projection was a generic GEMM launch at the head of the step's critical branch)
+        ring = fast and self._ring_proj() and getattr(self, "fused_input_proj", True) and (proj_fused or twin is None)
+        return fast, proj_fused, ring
+
+    def ring_rows(self, B, Tm, compute):
+        """The bf16 input rows forward(frozen=True) reads on the ring route (None on every other route): a caller whose
+        plan-sampling launch writes them (PlanRecognition.forward(ad_rows=...)) passes rows_current=True to forward()."""
+        if not self._route(B, compute)[2]:
+            return None
+        self._ensure(B, Tm)
+        return self.xb_seq
+
+    def module_emb(self, module, B, T, gather=True):
+        """(rows [B*T][ld], ld): the decoder's per-frame input from the module's camera embeddings.  gather=False: None where
+        that takes launches (cameras that are not the plan recognition's)."""
+        cams = module.action_decoder_modalities
+        if len(cams) == 1:  # one camera: the frame embeddings as the encoder wrote them
+            return module.f_out[cams[0]], 32
+        if cams == module.plan_recognition_modalities:  # already concatenated for the plan recognition
+            return module.pr_in, module.pr_in.shape[1]
+        if not gather:
+            return None
+        if getattr(module, "_ad_in", None) is None or module._ad_in.shape[0] != B * T:
+            ops.note_alloc()
+            module._ad_in = torch.zeros(B * T, 32 * len(cams), device=self.dev)
+        for j, c in enumerate(cams):
+            ops.copy_cols(module.f_out[c], 0, 32, module._ad_in, 32 * j, module._ad_in.shape[1], B * T, 32)
+        return module._ad_in, module._ad_in.shape[1]
+
+    def forward(self, plan, emb, ld_emb, B, T, Tm, compute, frozen=False, mirrors_current=False, twin=None, rows_current=False):
         """plan (B,P); emb [B*T][ld_emb] batch-major frame embeddings; uses steps t < Tm.  Fills self.heads.
+        rows_current=True (frozen ring route only, see ring_rows): xb_seq already holds this plan's and these frames' rows.
         frozen=True: the caller never steps these weights with the library's optimiser kernels, so the bf16
         copies of the weight matrices are refreshed only when the block's torch version counter moved
         (load_state_dict / copy_).
@@ -388,13 +427,8 @@ class ActionDecoderLogistic:
         # weight-gradient operand of a backward that follows (not built for the frozen, logging-only pass)
         # bf16 mode: the recurrent step runs as ONE launch (LDS-DMA ring GEMM, rnn_ops.hip) on bf16 copies of
         # W_hh (refreshed here: the weights may have been stepped) and of the previous hidden state
-        fast = compute == ops.BF16 and bool(ops.L.lib().tacorl_rnn_linear_supported(B, H, H))
-        # (the fused projection exists only on the ring-GEMM path: with a hidden size that path does not take - H % 128 != 0 -
-        # the generic per-step path below reads x_seq, so it must be built; 32 <= K: the kernel's first k-step is unmasked)
-        proj_fused = (fast and 32 <= K <= 64 and K % 8 == 0 and H % 16 == 0 and getattr(self, "fused_input_proj", True))
-        # (the K extension of the ring GEMM takes input widths up to 128: two cameras + a 32-wide plan = 96 at C4, where the
-        # separate projection was a generic GEMM launch at the head of the step's critical branch)
-        ring = fast and self._ring_proj() and getattr(self, "fused_input_proj", True) and (proj_fused or twin is None)
+        fast, proj_fused, ring = self._route(B, compute, twin)
+        assert not rows_current or (ring and frozen), "rows_current: the frozen ring route only (ring_rows)"
         if not ((proj_fused or ring) and frozen):
             call("tacorl_build_ad_input", ptr(plan), ptr(emb), ld_emb, ptr(self.x_seq), B, T, Tm, self.P, self.E,
                  ops.stream())
@@ -415,7 +449,8 @@ class ActionDecoderLogistic:
             # independent problems of ONE batched ring-GEMM launch whose workgroups are co-resident:
             # T + 2(L-1) dependent launches instead of L*T + (L-1).
             if ring:
-                call("tacorl_build_ad_input_bf16", ptr(plan), ptr(emb), ld_emb, ptr(self.xb_seq), B, T, Tm, self.P, self.E, ops.stream())
+                if not rows_current:
+                    call("tacorl_build_ad_input_bf16", ptr(plan), ptr(emb), ld_emb, ptr(self.xb_seq), B, T, Tm, self.P, self.E, ops.stream())
             elif proj_fused:
                 call("tacorl_ad_input_proj", ptr(plan), ptr(emb), ld_emb, blk.p("rnn.weight_ih_l0"), blk.p("rnn.bias_ih_l0"),
                      ptr(self.xin[0]), B, T, Tm, self.P, self.E, H, ops.stream())
@@ -517,29 +552,18 @@ class ActionDecoderLogistic:
                  ws.numel(), B, Tm, self.Da, loss_out, ops.stream())
 
     def loss_step(self, module, actions, plan, B, T, optimize, frozen=False, defer_update=False, mirrors_current=False,
-                  prepared=False, emb=None):
+                  prepared=False, emb=None, rows_current=False):
         """TACORL.compute_action_decoder_update (reference tacorl.py:206-233): loss on emb[:, :-1],
         actions[:, :-1]; logged always, Adam step when fine-tuning.  emb = (rows [B*T][ld], ld): the decoder's per-frame
         input as the caller has it (vector observations); default: the module's camera embeddings."""
         from .._lib import LOG_SLOTS
 
         acts = actions
-        cams = module.action_decoder_modalities if emb is None else None
-        if emb is not None:
-            emb, ld = emb
-        elif len(cams) == 1:  # one camera: the frame embeddings as the encoder wrote them
-            emb, ld = module.f_out[cams[0]], 32
-        elif cams == module.plan_recognition_modalities:  # already concatenated for the plan recognition
-            emb, ld = module.pr_in, module.pr_in.shape[1]
-        else:
-            if getattr(module, "_ad_in", None) is None or module._ad_in.shape[0] != B * T:
-                ops.note_alloc()
-                module._ad_in = torch.zeros(B * T, 32 * len(cams), device=self.dev)
-            for j, c in enumerate(cams):
-                ops.copy_cols(module.f_out[c], 0, 32, module._ad_in, 32 * j, module._ad_in.shape[1], B * T, 32)
-            emb, ld = module._ad_in, module._ad_in.shape[1]
-        # (mirrors_current / prepared: the caller has issued refresh_mirrors() / prepare_backward() for the current weights)
-        self.forward(plan, emb, ld, B, T, T - 1, module.compute, frozen=frozen and not optimize, mirrors_current=mirrors_current)
+        emb, ld = emb if emb is not None else self.module_emb(module, B, T)
+        # (mirrors_current / prepared: the caller has issued refresh_mirrors() / prepare_backward() for the current weights;
+        # rows_current: its plan-sampling launch has written xb_seq - ring_rows)
+        self.forward(plan, emb, ld, B, T, T - 1, module.compute, frozen=frozen and not optimize, mirrors_current=mirrors_current,
+                     rows_current=rows_current)
         slot = ops._at(module.engine.logs, LOG_SLOTS.index("action_loss"))
         self.loss(acts, slot, B, T, T - 1, want_grad=optimize, grad_scale=1.0 / module.world_size, lazy=True)
         if optimize:

@@ -21,6 +21,8 @@ from ..blocks import TensorBlock
 
 
 class PlanRecognition:
+    writes_ad_rows = True  # forward(ad_rows=...): the sampling launch can write the action decoder's bf16 input rows
+
     def __init__(self, state_dim, latent_plan_dim, device, num_heads=8, num_layers=2, encoder_hidden_size=2048,
                  fc_hidden_size=4096, max_position_embeddings=16, min_std=1e-4, dropout_p=0.0, trainable=True,
                  **unused):
@@ -141,7 +143,8 @@ class PlanRecognition:
         call("tacorl_pr_head_compose", blk.p("fc.weight"), blk.p("fc.bias"), blk.p("mean_fc.weight"), blk.p("mean_fc.bias"),
              ptr(self._Wc), ptr(self._bc), self.D, self.FC, 2 * self.A, ops.stream())
 
-    def forward(self, emb, ld_emb, B, T, compute, inference=False, sample=None, prepared=False, frozen=False, train=False):
+    def forward(self, emb, ld_emb, B, T, compute, inference=False, sample=None, prepared=False, frozen=False, train=False,
+                ad_rows=None):
         """emb: device tensor/pointer of [B*T][ld_emb] per-frame embeddings (first D_in columns used).
         Returns the (B, 2A) head buffer [mean | var_raw].  inference=True (frozen network, no backward
         follows): the encoder layers + time pooling run as one launch when the shape qualifies; with
@@ -149,7 +152,11 @@ class PlanRecognition:
         (prepared=True: prepare_inference() was already issued for the current weights; frozen=True: the caller
         never steps these weights with the library's optimiser kernels, so they only change through torch in-place
         ops - load_state_dict, copy_ - which bump the parameter block's version counter: the preparation is then
-        re-issued only when that counter moved)."""
+        re-issued only when that counter moved).
+        ad_rows=(xb_seq, Tm, P, E, emb_ad, ld_ad): the action decoder's bf16 input rows (ActionDecoder.ring_rows) are written
+        by the sampling launch where it can (self.rows_written says whether it did: the caller's decoder pass then skips
+        its own tacorl_build_ad_input_bf16 launch)."""
+        self.rows_written = False
         self._ensure(B, T)
         blk, D, R = self.blk, self.D, B * T
         drop = self._dropping = bool(train and not inference and self.dropout_p > 0)
@@ -161,6 +168,15 @@ class PlanRecognition:
                 self._prep_version = ver if frozen else None
             if sample is not None:
                 eps, plan = sample
+                if ad_rows is not None and D == 32 and ad_rows[2] == self.A and self.A % 8 == 0 and ad_rows[1] <= T \
+                        and ad_rows[2] + ad_rows[3] <= 128 and ad_rows[5] >= ad_rows[3]:
+                    xb_seq, Tm, P, E, emb_ad, ld_ad = ad_rows
+                    call("tacorl_pr_encoder_fused_sample_rows", ptr(emb), ld_emb, ptr(blk.param), ptr(self._pb), self._foff,
+                         ptr(self.pooled), B, D, T, self.H, self.FF, self.L, ptr(self._Wc), ptr(self._bc), ptr(eps),
+                         ptr(self.head), ptr(plan), self.A, float(self.min_std), ptr(xb_seq), Tm, P, E, ptr(emb_ad), ld_ad,
+                         ops.stream())
+                    self.rows_written = True
+                    return self.head
                 call("tacorl_pr_encoder_fused_sample", ptr(emb), ld_emb, ptr(blk.param), ptr(self._pb), self._foff,
                      ptr(self.pooled), B, D, T, self.H, self.FF, self.L, ptr(self._Wc), ptr(self._bc), ptr(eps),
                      ptr(self.head), ptr(plan), self.A, float(self.min_std), ops.stream())
