@@ -864,6 +864,52 @@ int tacorl_knn_l2(const float* points, long n_points, int D, long ld, long q0, l
 int tacorl_nn_margin_filter(const int* nbr_row, long n_queries, int k, long q0, const long* step_of_row, long n_points,
                             long margin, long* nn_steps, int* count, tacorl_stream_t stream);
 
+/* ---- exact t-SNE of latent plans (tsne_ops.hip) ----
+ * The embedding behind the reference's TSNEPlot callback (utils/callbacks/tsne_plot.py, "task_consistency").  The reference
+ * calls MulticoreTSNE there: a Barnes-Hut approximation with a sparse 3 * perplexity-neighbour P and its own random
+ * initialisation.  This is EXACT t-SNE with van der Maaten's optimiser constants and is not comparable with that library bit
+ * for bit; as for tacorl_knn_l2 the yardstick is the fp64 restatement of THIS definition (tests/tsne_ref.py).
+ *
+ * Input.  X: (N, D) fp32 at a row pitch of ld floats (ld >= D), 1 <= D <= 32.  mean_c = (sum of column c) / N; M = the largest
+ *   |x_rc - mean_c|; xn_rc = (x_rc - mean_c) / M, kept in ws as an (N, 32) table, zero beyond column D.  An all-equal table
+ *   (M == 0) sets status[1] = 1 (the host refuses it; xn is then all zero and nothing faults).
+ * Affinities.  d_ij = |xn_i - xn_j|^2 in the direct form of tacorl_knn_l2 (fp32, sequentially over the columns).  Per row i,
+ *   with m_i = min_{j != i} d_ij and t_j = d_ij - m_i (the shift cancels in p): e_j = expf(-(beta_i t_j)), S = sum_{j != i} e_j,
+ *   H_i = logf(S) + beta_i (sum_{j != i} e_j t_j) / S  - the entropy of p_{j|i} = e_j / S, p_{i|i} = 0.  beta_i is bisected: it
+ *   starts at 1; while H_i > log(perplexity) it moves to the midpoint with the upper bracket, or doubles (capped at 1e30) while
+ *   there is none; else to the midpoint with the lower bracket, or halves.  The search stops at the evaluation where
+ *   |H_i - log(perplexity)| < 1e-5, or after 200 evaluations (the row is then counted in status[0]).
+ *   P_ij = (p_{j|i} + p_{i|j}) / (2 N): dense (N, N) fp32, symmetric bit for bit, zero diagonal.  beta: (N), kept for inspection.
+ *   Sums over j: lane l of the row's wave adds j = l, l + 64, ... in order, then a 6-step xor butterfly (32, 16, .. 1).
+ * Forces.  For Y (N, 2), q_ij = |y_i - y_j|^2, w_ij = 1 / (1 + q_ij), w_ii = 0:
+ *   attr_i = sum_j P_ij w_ij (y_i - y_j);  rep_i = sum_j w_ij^2 (y_i - y_j);  Z_i = sum_j w_ij;  Z = sum_i Z_i;
+ *   grad_i = 4 (e attr_i - rep_i / Z) with exaggeration e.  Lane l of the row's wave adds j = 4 l + 256 k + {0, 1, 2, 3} in
+ *   order, then the same butterfly: a row's three sums depend on that row of P and on Y only, and a run repeats bit for bit.
+ * Update.  gains = gains + 0.2 where (grad > 0) != (u > 0), else gains * 0.8, floor 0.01;  u = momentum u - lr (gains grad);
+ *   Y = Y + u;  then Y = Y - (column mean of Y).  Z and the two column sums are one tree each: thread t of 1024 adds the
+ *   elements t, t + 1024, ... in order, then strides 512 .. 1 are folded in shared memory.
+ * Schedule (the caller's: tacorl_amd/evaluation/tsne.py).  1000 iterations, lr 200; e = 12 and momentum 0.5 for the first 250,
+ *   then e = 1 and momentum 0.8; Y0 = 1e-4 N(0, 1), u = 0, gains = 1.
+ * Cost.  KL = sum_{P_ij > 0} P_ij log(P_ij / (w_ij / Z)), evaluated as sum P_ij (logf P_ij + logf(1 + q_ij)) + logf(Z) sum P_ij.
+ *
+ * Supported: 4 <= N <= tacorl_tsne_max_n() = 8192 (the dense P is N^2 * 4 B = 256 MiB there and is read once per iteration;
+ * a row's distances take N * 4 B of LDS, four rows per workgroup), 1 <= D <= 32, 1 <= perplexity and 3 perplexity <= N - 1.
+ * Nothing is allocated: ws holds tacorl_tsne_workspace_bytes(N) bytes, 16-byte aligned, and is shared by the three calls;
+ * tacorl_tsne_workspace_offsets writes the byte offsets of {xn (N, 32), attr (N, 2), rep (N, 2), Z_i (N)} - what the last
+ * tacorl_tsne_affinities / tacorl_tsne_step left there.  status: int[2].  Device pointers; P 16-byte, Y 8-byte, the others
+ * 4-byte aligned.  A NULL or misaligned pointer, a short workspace, ld < D or a size, D or perplexity out of range is refused
+ * with TACORL_EINVAL before anything is launched.  Asynchronous on `stream`; no atomics but the integer count in status[0]. */
+int tacorl_tsne_supported(long N, int D);
+int tacorl_tsne_max_n(void);
+size_t tacorl_tsne_workspace_bytes(long N); /* 0: N not supported */
+int tacorl_tsne_workspace_offsets(long N, long* off4);
+int tacorl_tsne_affinities(const float* X, long N, int D, long ld, float perplexity, float* P, float* beta, int* status,
+                           void* ws, size_t ws_bytes, tacorl_stream_t stream);
+/* One iteration in place on Y, u, gains (each (N, 2)). */
+int tacorl_tsne_step(const float* P, long N, float* Y, float* u, float* gains, float exaggeration, float momentum, float lr,
+                     void* ws, size_t ws_bytes, tacorl_stream_t stream);
+int tacorl_tsne_kl(const float* P, const float* Y, long N, float* out, void* ws, size_t ws_bytes, tacorl_stream_t stream);
+
 /* ---- rollout (rollout_ops.hip) ------------------------------------------------------ */
 /* A linear layer with two inputs for a handful of rows, read from torch's row-major (N, K) fp32 masters as they lie:
  *   y[r][n] = act(b1[n] + b2[n] + sum_k w1[n][k] x1[r][k] + sum_k w2[n][k] x2[r][k]),   r < R, n < N.

@@ -180,6 +180,13 @@ _SIGS = {
     "tacorl_knn_l2_query_block": (_i, [_i]),
     "tacorl_knn_l2": (_i, [_p, _l, _i, _l, _l, _l, _i, _p, _p, _p]),
     "tacorl_nn_margin_filter": (_i, [_p, _l, _i, _l, _p, _l, _l, _p, _p, _p]),
+    "tacorl_tsne_supported": (_i, [_l, _i]),
+    "tacorl_tsne_max_n": (_i, []),
+    "tacorl_tsne_workspace_bytes": (_sz, [_l]),
+    "tacorl_tsne_workspace_offsets": (_i, [_l, _p]),
+    "tacorl_tsne_affinities": (_i, [_p, _l, _i, _l, _f, _p, _p, _p, _p, _sz, _p]),
+    "tacorl_tsne_step": (_i, [_p, _l, _p, _p, _p, _f, _f, _f, _p, _sz, _p]),
+    "tacorl_tsne_kl": (_i, [_p, _p, _l, _p, _p, _sz, _p]),
     "tacorl_rows_linear2_supported": (_i, [_i, _i, _i, _i]),
     "tacorl_rows_linear2_group": (_i, []),
     "tacorl_rows_linear2_fwd": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),

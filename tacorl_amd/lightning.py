@@ -129,6 +129,13 @@ class _MiniLightningModule(nn.Module):
 LightningModuleBase = pl.LightningModule if HAVE_PL else _MiniLightningModule
 
 
+class _MiniCallback:
+    """pl.Callback where pytorch_lightning is absent: a callback defines the hooks it wants, MiniTrainer calls those."""
+
+
+CallbackBase = pl.Callback if HAVE_PL else _MiniCallback
+
+
 def _as_list(x):
     return list(x) if isinstance(x, (list, tuple)) else [x]
 
@@ -225,10 +232,17 @@ def instantiate(cfg, *args, **kwargs):
 
 
 # ------------------------------------------------------------------------------------ trainer
+def _state_key(cb):
+    return getattr(cb, "state_key", None) or type(cb).__qualname__
+
+
 class MiniTrainer:
     """Minimal fit loop for boxes without pytorch_lightning (same call order as PL's: configure_optimizers,
     on_fit_start, per batch on_train_batch_start -> training_step(batch, batch_idx) -> on_train_batch_end,
-    validation at epoch end, checkpoints in PL's layout).  Enforces what PL enforces on the way in."""
+    validation at epoch end, checkpoints in PL's layout).  Enforces what PL enforces on the way in.
+    `callbacks`: each hook a callback defines is called as hook(trainer, pl_module, ...) - on_fit_start and the *_start hooks in
+    front of the module's own, the *_end hooks behind it; on_validation_batch_end gets validation_step's return value; a
+    callback's on_save_checkpoint return value travels in the checkpoint's "callbacks" entry.  An empty list calls nothing."""
 
     def __init__(self, max_epochs=1, max_steps=-1, log_every_n_steps=50, limit_val_batches=None, default_root_dir=None,
                  callbacks=None, logger=None, **unused):
@@ -245,6 +259,13 @@ class MiniTrainer:
 
     def _log(self, name, value, **kw):
         self.logged_metrics[name] = value
+
+    def _callbacks(self, hook, *args):
+        """Every callback that defines `hook`, in list order: hook(trainer, pl_module, *args) - PL's callback signature."""
+        for cb in self.callbacks:
+            fn = getattr(cb, hook, None)
+            if fn is not None:
+                fn(self, self.model, *args)
 
     @staticmethod
     def _validate(model):
@@ -276,30 +297,38 @@ class MiniTrainer:
         if ckpt_path is not None:
             self.load_checkpoint(ckpt_path)
         model.train()
+        self._callbacks("on_fit_start")
         model.on_fit_start()
         model.on_train_start()
         done = False
         while self.current_epoch < self.max_epochs and not done:
+            self._callbacks("on_train_epoch_start")
             model.on_train_epoch_start()
             for batch_idx, batch in enumerate(train_dataloaders):
                 batch = model.transfer_batch_to_device(batch, model.device, 0)
+                self._callbacks("on_train_batch_start", batch, batch_idx)
                 model.on_train_batch_start(batch, batch_idx)
                 out = model.training_step(batch, batch_idx)
                 if model.automatic_optimization:
                     raise RuntimeError("MiniTrainer drives manual-optimisation modules only (the in-scope ones all are)")
                 model.on_train_batch_end(out, batch, batch_idx)
+                self._callbacks("on_train_batch_end", out, batch, batch_idx)
                 self.global_step += 1
                 if 0 < self.max_steps <= self.global_step:
                     done = True
                     break
             model.on_train_epoch_end()
+            self._callbacks("on_train_epoch_end")
             if val_dataloaders is not None:
                 model.on_validation_epoch_start()
                 for batch_idx, batch in enumerate(val_dataloaders):
                     if self.limit_val_batches is not None and batch_idx >= self.limit_val_batches:
                         break
-                    model.validation_step(model.transfer_batch_to_device(batch, model.device, 0), batch_idx)
+                    batch = model.transfer_batch_to_device(batch, model.device, 0)
+                    out = model.validation_step(batch, batch_idx)
+                    self._callbacks("on_validation_batch_end", out, batch, batch_idx, 0)
                 model.on_validation_epoch_end()
+                self._callbacks("on_validation_epoch_end")
             self.current_epoch += 1
         model.on_fit_end()
 
@@ -309,6 +338,13 @@ class MiniTrainer:
         ck = {"epoch": self.current_epoch, "global_step": self.global_step, "state_dict": m.state_dict(),
               "optimizer_states": [o.state_dict() for o in self.optimizers], "lr_schedulers": [],
               "hyper_parameters": dict(getattr(m, "hparams", {}) or {})}
+        if self.callbacks:  # PL 1.6: {callback.state_key: what its on_save_checkpoint returned}
+            ck["callbacks"] = {}
+            for cb in self.callbacks:
+                fn = getattr(cb, "on_save_checkpoint", None)
+                state = fn(self, m, ck) if fn is not None else None
+                if state:
+                    ck["callbacks"][_state_key(cb)] = state
         m.on_save_checkpoint(ck)
         return ck
 
@@ -318,6 +354,11 @@ class MiniTrainer:
     def load_checkpoint(self, path):
         ck = torch.load(path, map_location="cpu", weights_only=False)
         self.model.on_load_checkpoint(ck)
+        for cb in self.callbacks:  # PL 1.6: on_load_checkpoint(trainer, pl_module, callback_state), only where a state was saved
+            state = ck.get("callbacks", {}).get(_state_key(cb))
+            fn = getattr(cb, "on_load_checkpoint", None)
+            if state and fn is not None:
+                fn(self, self.model, state)
         self.model.load_state_dict(ck["state_dict"])
         for o, s in zip(self.optimizers, ck.get("optimizer_states", [])):
             o.load_state_dict(s)

@@ -27,7 +27,20 @@ class PlayLMPShell:
 
     def set_kl_beta(self, kl_beta):
         """reference play_lmp_for_rl.py:303-305, play_lmp_d4rl.py:190-192."""
+        if kl_beta != self.kl_beta:  # a launch argument of the KL kernel (a captured graph holds the old value) -> new captures
+            self._graphs = {}
         self.kl_beta = kl_beta
+
+    def last_plan_proposal(self):
+        """The plan proposal of the most recent step as a distribution (what the reference's validation_step hands its
+        callbacks a sample of: `sampled_plan_pp`): a TanhNormalDist over the proposal head where the step left it.
+        Read-only: no launch is added to the step, and the head buffer is viewed, not copied - use it before the next step."""
+        from ..inference import TanhNormalDist
+
+        if getattr(self, "_shape", None) is None:
+            raise RuntimeError("last_plan_proposal(): no step has run yet")
+        B, A = self._shape[0], self.pr.A
+        return TanhNormalDist(self.pact[self.p_yoff: self.p_yoff + B * 2 * A].view(B, 2 * A), A)
 
     def named_gradients(self):
         return {self._ref_name(p + k): v for _, blk, p in self._parts() for k, v in blk.grad_views.items()}

@@ -445,6 +445,83 @@ def nn_margin_filter(nbr_row, step_of_row, margin, q0=0, nn_steps=None, count=No
     return nn_steps, count
 
 
+# ---- exact t-SNE (tsne_ops.hip; definition: include/tacorl_hip.h)
+TSNE_MAX_N, TSNE_MAX_D = 8192, 32
+
+
+def tsne_supported(N, D):
+    return bool(L.lib().tacorl_tsne_supported(int(N), int(D)))
+
+
+def tsne_workspace(N, device):
+    """A fresh workspace for the three t-SNE calls on an (N, .) table (uint8), or TacorlHipError."""
+    nbytes = int(L.lib().tacorl_tsne_workspace_bytes(int(N)))
+    if nbytes == 0:
+        raise L.TacorlHipError(f"tsne: N = {N} not supported (4..{TSNE_MAX_N})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def tsne_workspace_views(ws, N):
+    """{xn (N, 32), attr (N, 2), rep (N, 2), zrow (N)}: float views of what the last tsne_affinities / tsne_step left in ws."""
+    off = (C.c_long * 4)()
+    call("tacorl_tsne_workspace_offsets", int(N), off)
+    f = ws.view(torch.float32)
+    return {k: f[o // 4: o // 4 + N * w].view(N, w) if w > 1 else f[o // 4: o // 4 + N]
+            for k, o, w in zip(("xn", "attr", "rep", "zrow"), off, (32, 2, 2, 1))}
+
+
+def _tsne_ws(ws, N):
+    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous(), (ws.dtype, ws.device)
+    return ptr(ws), ws.numel()
+
+
+def tsne_affinities(X, perplexity, P=None, beta=None, status=None, ws=None):
+    """The symmetric affinity matrix of exact t-SNE.  X: (N, D) fp32 device tensor with dense rows (a column slice of a wider
+    table is fine).  Returns P (N, N) fp32, beta (N) fp32, status (2) int32 ([rows whose search hit the step cap, all-equal
+    table]) and the workspace; nothing is read back here."""
+    assert X.dim() == 2 and X.dtype == torch.float32 and X.is_cuda, (X.dtype, X.device, X.dim())
+    N, D = X.shape
+    assert N >= 1 and (N == 1 or X.stride(0) >= D) and (D == 1 or X.stride(1) == 1), (X.shape, X.stride())
+    ld = int(X.stride(0)) if N > 1 else D
+    if not tsne_supported(N, D):
+        raise L.TacorlHipError(f"tsne_affinities: N = {N} (4..{TSNE_MAX_N}) / D = {D} (1..{TSNE_MAX_D}) not supported")
+    dev = X.device
+    P = torch.empty(N, N, device=dev) if P is None else P
+    beta = torch.empty(N, device=dev) if beta is None else beta
+    status = torch.empty(2, dtype=torch.int32, device=dev) if status is None else status
+    ws = tsne_workspace(N, dev) if ws is None else ws
+    assert P.dtype == torch.float32 and P.is_cuda and P.is_contiguous() and P.numel() == N * N
+    assert beta.dtype == torch.float32 and beta.is_cuda and beta.is_contiguous() and beta.numel() == N
+    assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and status.numel() == 2
+    call("tacorl_tsne_affinities", ptr(X), N, D, ld, float(perplexity), ptr(P), ptr(beta), ptr(status), *_tsne_ws(ws, N), stream())
+    return P, beta, status, ws
+
+
+def _tsne_state(N, *ts):
+    for t in ts:
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and t.numel() == 2 * N, (t.dtype, t.device, t.shape)
+
+
+def tsne_step(P, Y, u, gains, exaggeration, momentum, lr, ws):
+    """One t-SNE iteration in place on Y, u, gains (each (N, 2) fp32); attr, rep and Z_i stay in ws (tsne_workspace_views)."""
+    assert P.dim() == 2 and P.shape[0] == P.shape[1] and P.dtype == torch.float32 and P.is_cuda and P.is_contiguous()
+    N = P.shape[0]
+    _tsne_state(N, Y, u, gains)
+    call("tacorl_tsne_step", ptr(P), N, ptr(Y), ptr(u), ptr(gains), float(exaggeration), float(momentum), float(lr),
+         *_tsne_ws(ws, N), stream())
+
+
+def tsne_kl(P, Y, ws, out=None):
+    """KL(P || Q(Y)) as a (1,) fp32 device tensor."""
+    assert P.dim() == 2 and P.shape[0] == P.shape[1] and P.dtype == torch.float32 and P.is_cuda and P.is_contiguous()
+    N = P.shape[0]
+    _tsne_state(N, Y)
+    out = torch.empty(1, device=P.device) if out is None else out
+    assert out.dtype == torch.float32 and out.is_cuda and out.numel() == 1
+    call("tacorl_tsne_kl", ptr(P), ptr(Y), N, ptr(out), *_tsne_ws(ws, N), stream())
+    return out
+
+
 def _at(t, off):
     return C.c_void_p(t.data_ptr() + 4 * off)
 
