@@ -433,6 +433,15 @@ int tacorl_pack_images_u8_resize_aug_gather_batch(int njobs, const void* const* 
                                                   const int* const* shift, const float* const* jitter, const int* n_img,
                                                   int dst_dtype, int src_H, int src_W, int H, int W, int pad,
                                                   tacorl_stream_t stream);
+/* The Resize stage alone, at store time (csrc/frame_ops.hip; the dataset key `store_size` of the frame datamodules): n uint8
+ * HWC frames of src_H x src_W, src_pitch_bytes apart -> n uint8 HWC frames of H x W, dst_pitch_bytes apart.  The same
+ * sampling arithmetic in the same order as the pack above (one device function, csrc/bilinear.h), then round to nearest
+ * even, clamp to 0..255, store.  src_H == H and src_W == W copies.  Bytes between a frame's end and the next frame are
+ * neither read into a result nor written.  TACORL_EINVAL before any launch: a null pointer, src or dst not 16-byte aligned,
+ * n or a size < 1, a pitch smaller than its frame, or a source so wide that the rows one band of 16 output rows samples
+ * exceed 48 KB of LDS ((15 * src_H / H + 4) * src_W * 3 bytes).  Never allocates. */
+int tacorl_resize_frames_u8(const void* src, long src_pitch_bytes, void* dst, long dst_pitch_bytes, long n, int src_H,
+                            int src_W, int H, int W, tacorl_stream_t stream);
 /* ... and the augmenting pack with the same optional frame-index tables (shift / jitter tables are per IMAGE i). */
 int tacorl_pack_images_u8_aug_gather_batch(int njobs, const void* const* src, const long* img_pitch_bytes,
                                            const long* const* index, const int* index_stride, void* const* dst,

@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 NAMES = ("dense_ops", "rl_ops", "seq_ops", "encoder_fused", "encoder_ring", "encoder_bwd_fused", "mlp_fused", "rnn_ops",
-         "pr_fused", "data_ops", "birnn_ops", "cem_ops", "knn_ops", "rollout_ops", "noise_ops", "tsne_ops")
+         "pr_fused", "data_ops", "birnn_ops", "cem_ops", "knn_ops", "rollout_ops", "noise_ops", "tsne_ops", "frame_ops")
 SRC = [os.path.join(CSRC, f + ".hip") for f in NAMES]
 OBJ_DIR = os.path.join(HERE, "lib", "obj")
 OUT = os.path.join(HERE, "lib", "libtacorl_hip.so")

@@ -6,6 +6,7 @@
 // explicit inputs (per-image tables), so the kernels are deterministic functions that goldens can pin.
 // Pure byte / elementwise work: HBM-bound, coalesced 16-byte accesses, no MFMA.
 #include "../../include/tacorl_hip.h"
+#include "bilinear.h"
 #include "common.h"
 
 #include <initializer_list>
@@ -76,20 +77,8 @@ struct AugTbl { AugJob j[AUG_MAXJ]; };
 // One workgroup per image.  RandomShiftsAug with integer shifts = a clamped (replicate-padded) translation; the
 // colour operations run in the drawn order; adjust_contrast needs the image's mean grey level AFTER the operations
 // that precede it, hence the first pass (a block reduction) when contrast is drawn.
-// torchvision.transforms.Resize on a float tensor = torch.nn.functional.interpolate(mode="bilinear", align_corners=False),
-// no antialias (the reference's torchvision generation; rl_train.yaml:3-4,16-17: 200x200 -> 128x128 static, -> 84x84
-// gripper, applied to the 0..255 float frame BEFORE RandomShiftsAug): ATen's upsample_bilinear2d,
-//   src = max(scale * (dst + 0.5) - 0.5, 0), scale = in / out (fp32); i0 = floor(src), i1 = i0 + (i0 < in - 1);
-//   l1 = src - i0, l0 = 1 - l1;  out = h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11)
-__device__ __forceinline__ void bilinear_axis(int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
-  const float src = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  i0 = (int)src;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
-
+// The Resize stage (rl_train.yaml:3-4,16-17: 200x200 -> 128x128 static, -> 84x84 gripper, applied to the 0..255 float frame
+// BEFORE RandomShiftsAug) samples by the rule of bilinear.h, which the store-time resize (frame_ops.hip) shares.
 template <typename OutT>
 __global__ __launch_bounds__(256) void pack_u8_aug_kernel(AugTbl t, int H, int W, int pad, int Hs, int Ws) {
   const AugJob jb = t.j[blockIdx.y];
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(256) void pack_u8_aug_kernel(AugTbl t, int H, int W
     float v[3];
 #pragma unroll
     for (int c = 0; c < 3; c++)
-      v[c] = h0 * (w0 * (float)p00[c] + w1 * (float)p01[c]) + h1 * (w0 * (float)p10[c] + w1 * (float)p11[c]);
+      v[c] = bilinear_mix(h0, h1, w0, w1, p00[c], p01[c], p10[c], p11[c]);
     r = v[0] / 255.0f; g = v[1] / 255.0f; b = v[2] / 255.0f;
   };
   float mean = 0.f;

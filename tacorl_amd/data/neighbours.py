@@ -118,8 +118,10 @@ class NeighbourTable:
             with open(path) as f:
                 doc = json.load(f)
         doc[data_type] = {str(k): v for k, v in self.to_dict().items()}
-        with open(path, "w") as f:
+        tmp = f"{path}.tmp{os.getpid()}"  # (renamed when complete: a process that starts meanwhile never reads half a file)
+        with open(tmp, "w") as f:
             json.dump(doc, f, indent=4)
+        os.replace(tmp, path)
 
     @classmethod
     def load_json(cls, path, data_type, n_frames, device="cpu"):

@@ -133,7 +133,12 @@ class PlayDataModule(FrameDataModule):
     """Drop-in for the reference's BasicDataModule with the PlayDataset configs (config/datamodule/{tacorl,play_lmp}.yaml with
     dataset/{tacorl,play_dataset}.yaml; data/resident.py FrameDataModule says what the two frame datamodules share).  `dataset`
     is the reference's dataset config (min_window_size, max_window_size, pad, include_goal, goal_sampling_prob,
-    goal_strategy_prob, goal_augmentation) plus `path` or `arrays`; n_frames is what the cameras and the action table hold.
+    goal_strategy_prob, goal_augmentation) plus `path`, `arrays` or `frame_dir`; n_frames is what the cameras and the action
+    table hold.  With `frame_dir` (the reference's directory; FrameDataModule says how) `action_type`, `n_digits`,
+    `num_nn` and the cameras of `modalities` are read (`real_world` stays without effect), and a neighbour table that is needed
+    comes from the reference's step-keyed JSON - the path given as nn_steps_from_step, the config's nn_steps_from_step_path,
+    nn_steps_from_step.json beside training/ or in the split's directory - remapped to rows, or is built from robot_obs and
+    written there; a NeighbourTable or dict given outright is in rows of the compacted arrays.
     include_goal false (PlayLMP's play_dataset.yaml): the batch has no `goal` and no `disp`, and no neighbour table is read.
     `nn_steps_from_step` (here or in `dataset`; `nn_steps_from_step_val` for the validation split): a NeighbourTable
     (data/neighbours.py), the reference's dict {step: [steps]}, or the path of the reference's JSON file, read with
@@ -141,8 +146,8 @@ class PlayDataModule(FrameDataModule):
     names an existing file and no table was given.  Without a table a similar_robot_obs goal is the reference's fallback, a
     random state.  pad must be true: the reference cannot collate unpadded windows of varying length either.  `_target_`,
     `modalities`, `action_type`, `n_digits`, `transf_type`, `num_nn`, `real_world`, `num_workers`, `pin_memory`, `shuffle_val`,
-    `data_dir` are accepted and unused: the dataset is resident and a batch is one kernel launch.
-    Validation batches are device draws like the training ones (as RILDataModule's): the reference chooses a validation
+    `data_dir` are accepted and unused (without `frame_dir`: all of them): the dataset is resident and a batch is one kernel
+    launch.  Validation batches are device draws like the training ones (as RILDataModule's): the reference chooses a validation
     window size with hash(str(idx)), which Python salts per process, so its validation set is not reproducible from run to
     run even there."""
 
@@ -175,13 +180,52 @@ class PlayDataModule(FrameDataModule):
     def _n_frames(self, frames, acts):
         return min([int(v.shape[0]) for v in frames.values()] + [int(acts.shape[0])])
 
+    def _wants_table(self):
+        """include_goal with a similar_robot_obs share (the reference's default strategy gives it one half)."""
+        gs = self.index_kwargs.get("goal_strategy_prob")
+        return self.include_goal and (gs is None or float(gs.get("similar_robot_obs", 0.0)) > 0.0)
+
+    def _nn_file(self, split):
+        """With `frame_dir`: (the file that holds - or will receive - the split's step-keyed table, whether it holds it), or
+        None where a table was given outright (a NeighbourTable or dict: those are in ROWS of the compacted arrays) or none
+        is wanted.  A path given as nn_steps_from_step(_val) and the config's nn_steps_from_step_path go first
+        (frame_dir.neighbour_file); the reference's JSON is keyed by step number and is remapped to rows when it is read."""
+        if not self._wants_table():
+            return None
+        nn = self._nn[split]
+        if nn is None and split == "validation" and isinstance(self._nn["train"], (str, os.PathLike)):
+            nn = self._nn["train"]  # the reference's file holds both splits
+        if nn is not None and not isinstance(nn, (str, os.PathLike)):
+            return None
+        from .frame_dir import neighbour_file
+
+        c = self.dataset_cfg
+        return neighbour_file(c["frame_dir"], self._dirs[split], split, (nn, c.get("nn_steps_from_step_path")))
+
+    def _want_robot_obs(self, split):
+        """With `frame_dir`: robot_obs is loaded where the split's neighbour table has to be built - none was given and no
+        file holds the split's."""
+        f = self._nn_file(split)
+        return f is not None and not f[1]
+
     def _neighbours(self, split, n_frames, dev):
-        """The split's nn_steps_from_step as PlayIndex takes it (a NeighbourTable or a dict), or None."""
+        """The split's nn_steps_from_step as PlayIndex takes it (a NeighbourTable or a dict), or None.  With `frame_dir`: the
+        step-keyed file _nn_file finds, or the table built from robot_obs and written there (frame_dir.split_neighbours),
+        remapped to rows; `num_nn` is then read.  A NeighbourTable or dict given outright is taken in rows, as without
+        `frame_dir`."""
         if not self.include_goal:
             return None
         from .neighbours import NeighbourTable
 
         nn = self._nn[split]
+        if "frame_dir" in self.dataset_cfg:
+            f = self._nn_file(split)
+            if f is not None:
+                from .frame_dir import split_neighbours
+
+                return split_neighbours(self.splits[split], dev, num_nn=int(self.dataset_cfg.get("num_nn", 32)), path=f[0])
+            if isinstance(nn, (str, os.PathLike)):
+                nn = None  # (no similar_robot_obs share: the file is not read)
         if nn is None:
             path = self.dataset_cfg.get("nn_steps_from_step_path")
             nn = path if path and os.path.isfile(os.path.expanduser(str(path))) else None

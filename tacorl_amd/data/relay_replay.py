@@ -138,12 +138,13 @@ class RelayLoader(ResidentLoader):
 class RILDataModule(FrameDataModule):
     """Drop-in for the reference's BasicDataModule with the RILDataset config (config/datamodule/relay_imitation_learning.yaml;
     data/resident.py FrameDataModule says what the two frame datamodules share).  `dataset` is the reference's dataset config
-    (max_low_level_window, max_high_level_window) plus `path` or `arrays`.  `_target_`, `modalities`, `action_type`,
-    `n_digits`, `transf_type`, `num_workers`, `pin_memory`, `shuffle_val` are accepted and unused: the dataset is resident and
-    a batch is one kernel launch.  n_frames is what the cameras hold; HbmRelayReplay refuses a shorter action table."""
+    (max_low_level_window, max_high_level_window) plus `path`, `arrays` or `frame_dir` (the reference's directory; with it
+    `modalities`, `action_type` and `n_digits` are read as FrameDataModule says).  `_target_`, `modalities`, `action_type`,
+    `n_digits`, `transf_type`, `real_world`, `num_workers`, `pin_memory`, `shuffle_val` are otherwise accepted and unused: the
+    dataset is resident and a batch is one kernel launch.  n_frames is what the cameras hold; HbmRelayReplay refuses a shorter action table."""
 
     DATASET_KEYS = ("max_low_level_window", "max_high_level_window")
-    DATASET_UNUSED = ("_target_", "_recursive_", "modalities", "action_type", "n_digits", "transf_type")
+    DATASET_UNUSED = ("_target_", "_recursive_", "modalities", "action_type", "n_digits", "transf_type", "real_world")
     LOADER = RelayLoader
 
     def __init__(self, dataset, batch_size=64, train_percentage=1.0, val_percentage=1.0, transform_manager=None,

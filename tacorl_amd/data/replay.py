@@ -11,6 +11,8 @@ frame stores that turn the ids into the module's uint8 batch:
 Every random draw is explicit (`PlayIndex.draw`), so the sampling is a deterministic function that
 tests/golden/play_sampler.npz (recorded from the reference class) pins.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -544,6 +546,35 @@ class HbmTransitionReplay(ResidentReplay):
                        "actions": acts, "n_frames": index.n_frames}
         self.A = int(acts.shape[1])
         self._grow(self.batch_size)
+
+    @classmethod
+    def from_frame_dir(cls, frame_dir, cameras, split="train", device=None, batch_size=256, slots=6, action_type="rel_actions_world",
+                       n_digits=None, real_world=False, store_size=None, cache_dir=None, num_nn=32, nn_steps_from_step=None,
+                       **index_kwargs):
+        """The replay over one split of the reference's dataset directory (data/frame_dir.py: a root holding training/ and
+        validation/, or one split directory): the frames loaded in chunks (store_size, cache_dir as the frame datamodules
+        take them), the episode table in rows, and - where goal_strategy_prob gives similar_robot_obs a share and no table
+        is given - the neighbour table read from the reference's step-keyed JSON (nn_steps_from_step as a path, else
+        nn_steps_from_step.json beside training/ or in the split's directory) and remapped to rows, or built and written
+        there.  nn_steps_from_step as a NeighbourTable or dict is taken in rows of the compacted arrays.
+        index_kwargs: TransitionIndex's (goal_strategy_prob, goal_sampling_prob, the horizons, ...)."""
+        from .frame_dir import load_split, neighbour_file, split_dirs, split_neighbours
+
+        dev = torch.device(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        root = split_dirs(frame_dir)[0][split]
+        if root is None:
+            raise FileNotFoundError(f"{frame_dir}: no {split} split")
+        gs = index_kwargs.get("goal_strategy_prob")
+        is_path = isinstance(nn_steps_from_step, (str, os.PathLike))
+        want = (nn_steps_from_step is None or is_path) and (gs is None or float(dict(gs).get("similar_robot_obs", 0.0)) > 0.0)
+        path, have = neighbour_file(frame_dir, root, split, (nn_steps_from_step,) if is_path else ()) if want else (None, False)
+        data = load_split(root, split, cameras, action_type, dev, n_digits=n_digits, real_world=real_world, store_size=store_size,
+                          cache_dir=cache_dir, want_robot_obs=want and not have)
+        nn = split_neighbours(data, dev, num_nn=num_nn, path=path) if want else (None if is_path else nn_steps_from_step)
+        index = TransitionIndex(data.ep, n_frames=data.n, nn_steps_from_step=nn, train=split == "train", **index_kwargs)
+        rp = cls(data.frames, data.actions, index, device=dev, batch_size=batch_size, slots=slots)
+        rp.split = data
+        return rp
 
     def _slot(self, B):
         f32 = torch.float32

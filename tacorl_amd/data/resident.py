@@ -7,6 +7,8 @@ replay's own ring of `slots` buffer sets.  Here, once:
 * `ResidentReplay`, the base of the four replays: the ring, the status word, the draw normaliser;
 * `ResidentLoader`, the loader `Trainer.fit` takes, and `FrameDataModule`, the datamodule of the uint8 frame datasets.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -201,7 +203,22 @@ class FrameDataModule:
     """The base of the datamodules over uint8 frame datasets (RILDataModule, PlayDataModule), drop-ins for the reference's
     BasicDataModule: `Trainer.fit(model, datamodule=dm)`.  `dataset` is the reference's dataset config plus where the data
     is: `path`, an .npz with `frames/<camera>` (N,H,W,3) uint8, `actions` (N,A) and the episode tables
-    `ep_start_end_ids_train` / `ep_start_end_ids_val` over those N frames, or `arrays`, a dict of the same.
+    `ep_start_end_ids_train` / `ep_start_end_ids_val` over those N frames, or `arrays`, a dict of the same, or `frame_dir`,
+    the reference's dataset directory (data/frame_dir.py): a root holding training/ and validation/ - what BasicDataModule
+    appends to data_dir, so the yaml line is `frame_dir: ${data_dir}`; each split then has its own frame arrays - or a single
+    split directory whose split.json supplies both tables over one shared array.  With `frame_dir` the reference's
+    `modalities` (its rgb_* entries are the cameras; absent: the first frame's rgb_* arrays), `action_type` and `n_digits`
+    are read; otherwise they stay accepted and unused.  `real_world` stays without effect either way: in the reference it
+    only drops scene_obs and state_info, which a replay never holds.  `workers` (8, at most 16), `chunk_frames` (256) and
+    `ring` (3) size the loader; `cache_dir` keeps the compacted arrays as .npy for later starts; beside `path` or
+    `arrays` these keys are refused.  A missing file, a missing key and a frame whose shape differs from the first frame's
+    are refused with the file name before anything is uploaded (every file's array headers are read first).  Under world_size > 1
+    every rank loads the same directory: frames are not sharded.
+    `store_size: [H, W]` (or {camera: [H, W]}; with `frame_dir` only; default none): every uploaded chunk passes
+    tacorl_resize_frames_u8 and the replay holds (N,H,W,3).  With store_size equal to what the train and validation lists
+    resize to, the Resize stage is no stage and validation loaders exist.  The one deviation: a batch is then the
+    reference's pipeline applied to frames that were resized and ROUNDED TO uint8 when they were stored (at most half a
+    grey level per value), not a resize of the float frame at sample time.  Without store_size nothing changes.
     train_percentage / val_percentage keep the first int(len * p) items (BasicDataModule's Subset); val_percentage 0: no
     validation loader.  transform_manager: the `rl` form (see augment.augment_specs); its train list becomes the train
     loader's augmentation, a Resize to the stored size is no stage, and validation batches carry no augmentation - the frames
@@ -212,6 +229,8 @@ class FrameDataModule:
 
     DATASET_KEYS = DATASET_UNUSED = ()
     LOADER = ResidentLoader
+    SOURCES = ("path", "arrays", "frame_dir")
+    FRAME_DIR_KEYS = ("store_size", "cache_dir", "workers", "chunk_frames", "ring")
 
     def __init__(self, dataset, batch_size, train_percentage, val_percentage, transform_manager, steps_per_epoch, val_steps,
                  device, fused, generator, slots, unused):
@@ -223,11 +242,18 @@ class FrameDataModule:
         self.train_percentage, self.val_percentage = float(train_percentage), float(val_percentage)
         self.transform_manager, self.steps_per_epoch, self.val_steps = transform_manager, steps_per_epoch, val_steps
         self.device, self.fused, self.generator, self.slots = device, fused, generator, slots
-        unknown = [k for k in self.dataset_cfg if k not in self.DATASET_KEYS + self.DATASET_UNUSED + ("path", "arrays")]
+        unknown = [k for k in self.dataset_cfg if k not in self.DATASET_KEYS + self.DATASET_UNUSED + self.SOURCES + self.FRAME_DIR_KEYS]
         if unknown:
             raise TypeError(f"{name}: unknown dataset settings {unknown}")
-        if ("path" in self.dataset_cfg) == ("arrays" in self.dataset_cfg):
+        if "frame_dir" in self.dataset_cfg:
+            if "path" in self.dataset_cfg or "arrays" in self.dataset_cfg:
+                raise ValueError(f"{name}: give exactly one of `path`, `arrays` and `frame_dir`")
+        elif ("path" in self.dataset_cfg) == ("arrays" in self.dataset_cfg):
             raise ValueError(f"{name}: give the dataset as `path` (an .npz) or as `arrays`")
+        stray = [k for k in self.FRAME_DIR_KEYS if k in self.dataset_cfg and "frame_dir" not in self.dataset_cfg]
+        if stray:
+            raise ValueError(f"{name}: {stray} belong to the `frame_dir` source (store_size resizes its frames as they are uploaded)")
+        self.load_stats = {}
         self.cams = self._cameras()
         self.aug_specs = augment_specs(self.transform_manager, self.cams, "train")  # (raises for what is not built)
         self._val_specs = augment_specs(self.transform_manager, self.cams, "validation")
@@ -235,6 +261,18 @@ class FrameDataModule:
 
     def _cameras(self):
         c = self.dataset_cfg
+        if "frame_dir" in c:
+            from .frame_dir import split_dirs
+
+            self._dirs, self._one_dir = split_dirs(c["frame_dir"])
+            cams = sorted(m for m in (c.get("modalities") or ()) if str(m).startswith("rgb_"))
+            if not cams:
+                first = min(e.name for e in os.scandir(self._dirs["train"]) if e.name.endswith(".npz"))
+                with np.load(os.path.join(self._dirs["train"], first)) as z:
+                    cams = sorted(k for k in z.files if k.startswith("rgb_"))
+            if not cams:
+                raise KeyError(f"{c['frame_dir']}: no rgb_* camera in `modalities` or in the first frame")
+            return cams
         if "arrays" in c:
             a = c["arrays"]
             fr = a["frames"] if "frames" in a else {k.split("/", 1)[1]: None for k in a if k.startswith("frames/")}
@@ -259,6 +297,54 @@ class FrameDataModule:
         """The frames the index tables may name: what every camera holds."""
         return min(int(v.shape[0]) for v in frames.values())
 
+    def _settle_resize(self, stored):
+        """stored {camera: (H, W)}: a train Resize to the stored size is no stage; a list that resizes away from it is
+        refused where a validation loader is asked for.  (With `frame_dir` this runs on the planned sizes, before the load.)"""
+        for c, hw in stored.items():
+            sp, vs = self.aug_specs[c], self._val_specs[c]
+            if sp is not None and sp.resize == hw:
+                sp.resize = None
+            resized = [s.resize for s in (sp, vs) if s is not None and s.resize not in (None, hw)]
+            if resized and self.val_percentage > 0:
+                raise NotImplementedError(f"{c}: validation batches carry no resize - store the frames at {resized[0]}, not {hw}")
+
+    def _frame_dir_splits(self, dev):
+        """The `frame_dir` source: (frames, actions, ep) in rows for the train split and (or None) for the validation split;
+        self.splits keeps each split's frame_dir.LoadedSplit (its compaction, its robot_obs where _want_robot_obs asks)."""
+        from .frame_dir import LoadedSplit, SplitPlan, episode_table
+
+        c = self.dataset_cfg
+        kw = dict(cameras=self.cams, action_type=c.get("action_type", "rel_actions_world"), n_digits=c.get("n_digits"),
+                  real_world=bool(c.get("real_world", False)), store_size=c.get("store_size"), cache_dir=c.get("cache_dir"),
+                  workers=c.get("workers", 8), chunk_frames=c.get("chunk_frames", 256), ring=c.get("ring", 3))
+        want_val = self.val_percentage > 0 and self._dirs["validation"] is not None
+        names = ("train", "validation") if want_val else ("train",)
+        self.splits = {}
+        if self._one_dir and want_val:
+            # one directory, one array: its rows are the steps either table covers, and each split's table is remapped to them
+            eps = {s: episode_table(self._dirs[s], s) for s in names}
+            ep = np.concatenate(list(eps.values()))
+            plan = SplitPlan(self._dirs["train"], "train", want_robot_obs=any(self._want_robot_obs(s) for s in names),
+                             episodes=ep[np.argsort(ep[:, 0], kind="stable")], **kw)
+            self._settle_resize(plan.stored)
+            whole = plan.load(dev)
+            self.load_stats["train"] = plan.stats
+            for s in names:
+                self.splits[s] = LoadedSplit(whole.frames, whole.actions, whole.rows(eps[s]), whole.step_of_row,
+                                             whole.robot_obs, whole.root, s)
+        else:
+            plans = {s: SplitPlan(self._dirs[s], s, want_robot_obs=self._want_robot_obs(s), **kw) for s in names}
+            self._settle_resize(plans["train"].stored)
+            for s, plan in plans.items():  # (every split's refusals came first)
+                self.splits[s] = plan.load(dev)
+                self.load_stats[s] = plan.stats
+        out = [(d.frames, d.actions, d.ep) for d in (self.splits["train"], self.splits.get("validation")) if d is not None]
+        return out[0], (out[1] if len(out) > 1 else None)
+
+    def _want_robot_obs(self, split):
+        """Whether the split's robot_obs is loaded beside its frames (a subclass that builds a neighbour table asks)."""
+        return False
+
     def prepare_data(self, *args, **kwargs):
         pass
 
@@ -268,27 +354,23 @@ class FrameDataModule:
         from ..lightning import default_device
 
         dev = torch.device(self.device if self.device is not None else default_device())  # one process per GPU
-        frames, actions, ep_train, ep_val = self._arrays()
-        frames = {c: torch.as_tensor(v).to(dev).contiguous() for c, v in frames.items()}  # both splits share the frames
-        acts = torch.as_tensor(np.asarray(actions, dtype=np.float32)).to(dev)
-        n = self._n_frames(frames, acts)
-        for c, v in frames.items():
-            stored = tuple(v.shape[1:3])
-            sp, vs = self.aug_specs[c], self._val_specs[c]
-            if sp is not None and sp.resize == stored:
-                sp.resize = None
-            resized = [s.resize for s in (sp, vs) if s is not None and s.resize not in (None, stored)]
-            if resized and self.val_percentage > 0:
-                raise NotImplementedError(f"{c}: validation batches carry no resize - store the frames at {resized[0]}, not {stored}")
+        if "frame_dir" in self.dataset_cfg:
+            tr, va = self._frame_dir_splits(dev)
+        else:
+            frames, actions, ep_train, ep_val = self._arrays()
+            frames = {c: torch.as_tensor(v).to(dev).contiguous() for c, v in frames.items()}  # both splits share the frames
+            acts = torch.as_tensor(np.asarray(actions, dtype=np.float32)).to(dev)
+            tr, va = (frames, acts, ep_train), (frames, acts, ep_val)
+        self._settle_resize({c: tuple(v.shape[1:3]) for c, v in tr[0].items()})
         specs = {c: s for c, s in self.aug_specs.items() if s is not None and (s.resize is not None or s.pad or s.prob)}
         self._train_specs = specs or None
-        self.index = ix = self._index(ep_train, self.train_percentage, "train", n, dev)
-        self.train_replay = self._replay(frames, acts, ix, dev)
+        self.index = ix = self._index(tr[2], self.train_percentage, "train", self._n_frames(tr[0], tr[1]), dev)
+        self.train_replay = self._replay(tr[0], tr[1], ix, dev)
         if self.val_percentage > 0:
-            if ep_val is None:
+            if va is None or va[2] is None:
                 raise KeyError(f"{type(self).__name__}: val_percentage > 0 needs `ep_start_end_ids_val`")
-            vix = self._index(ep_val, self.val_percentage, "validation", n, dev)
-            self.val_replay = self._replay(frames, acts, vix, dev)
+            vix = self._index(va[2], self.val_percentage, "validation", self._n_frames(va[0], va[1]), dev)
+            self.val_replay = self._replay(va[0], va[1], vix, dev)
             if self.val_steps is None:
                 self.val_steps = max(len(vix) // self.batch_size, 1)
         if self.steps_per_epoch is None:

@@ -297,6 +297,24 @@ def gather_frames_u8(frames, index, out):
     return out
 
 
+def resize_frames_u8(src, out, src_pitch=None):
+    """out[i] = Resize(out's H x W)(src[i]), rounded to nearest even and clamped: uint8 (n,Hs,Ws,3) -> uint8 (n,H,W,3) on the
+    device (tacorl_resize_frames_u8; the sampling rule of the augmenting pack's Resize stage).  src_pitch: (bytes between
+    source frames, Hs, Ws) where src is a flat uint8 buffer that holds them further apart than a frame."""
+    if src_pitch is not None:
+        pitch, Hs, Ws = (int(v) for v in src_pitch)
+    else:
+        assert src.dim() == 4 and src.shape[3] == 3 and src.shape[0] >= out.shape[0]
+        Hs, Ws = int(src.shape[1]), int(src.shape[2])
+        pitch = Hs * Ws * 3
+    assert src.dtype == torch.uint8 and src.is_cuda and src.is_contiguous()
+    assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.dim() == 4 and out.shape[3] == 3
+    n, H, W = (int(v) for v in out.shape[:3])
+    assert src.numel() >= (n - 1) * pitch + Hs * Ws * 3
+    call("tacorl_resize_frames_u8", ptr(src), pitch, ptr(out), H * W * 3, n, Hs, Ws, H, W, stream())
+    return out
+
+
 # ---- the samplers over resident tables (data/resident.py).  What their four wrappers check alike:
 def _all_dev(dtype, *ts):
     """Every tensor is of `dtype`, on the device and contiguous."""
