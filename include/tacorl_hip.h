@@ -452,6 +452,39 @@ int tacorl_pack_images_u8_aug_gather_batch(int njobs, const void* const* src, co
  * disp_dtype: 0 float32, 1 int64, 2 int32, 3 uint8 / bool. */
 int tacorl_stage_transition(const void* disp, int disp_dtype, float* reward, float* done, int B,
                             const float* acts_src, float* acts_dst, long n_acts, tacorl_stream_t stream);
+/* TACORL's step front on its fp32-source route as ONE launch over a device-resident table at a fixed address: per camera the
+ * fused encoder's source entries [window | next] (the layout of tacorl_encoder_src_fill's entries; camera i's are entries
+ * 2 i and 2 i + 1 at offsets[0] + k * tacorl_encoder_src_entry_bytes()), the pack jobs [obs; goal] of the engine cameras
+ * (fp32 CHW -> bf16 NHWC, bit-identical to tacorl_pack_images_batch) and tacorl_stage_transition's sources and destinations.
+ *   tacorl_step_front_table_bytes / _offsets: the table's size and the byte offsets of its TACORL_SF_NOFFSETS fields, in the
+ *     order src, pack_src, pack_dst, pack_pitch, pack_n, disp, reward, done, acts_src, acts_dst, n_acts, disp_dtype, B,
+ *     njobs, HW.
+ *   tacorl_step_front_supported (pure host): sources as tacorl_encoder_src_supported takes them (contiguous 84 x 84 images,
+ *     pitches in floats), pack jobs 16-byte aligned at both ends with pitch % 4 == 0 and n >= 1, H*W % 4 == 0, a disp dtype
+ *     code of tacorl_stage_transition, B >= 1, at most 2 * TACORL_SF_MAXCAM sources and TACORL_SF_MAXJOBS jobs.
+ *   tacorl_step_front_assemble (pure host): the table's bytes for these entries into host_table (unused entries and padding
+ *     zero, so equal entries give equal bytes: the caller keeps them as the shadow of the device table and skips the fill
+ *     while they do not change); TACORL_EINVAL, nothing written, for what _supported refuses.
+ *   tacorl_step_front_fill: one small launch writes assembled bytes (passed by value) over the device table.
+ *   tacorl_step_front: blockIdx.y < njobs packs job blockIdx.y, the last blockIdx.y stages the transition.  The table is read
+ *     when the kernel RUNS: a captured launch follows the batch tensors the last fill named.  njobs, max_images (the largest
+ *     job), B, n_acts, H, W size the grid and must be the filled table's. */
+#define TACORL_SF_MAXCAM 4
+#define TACORL_SF_MAXJOBS 8
+#define TACORL_SF_NOFFSETS 15
+long tacorl_step_front_table_bytes(void);
+int tacorl_step_front_offsets(long* offsets);
+int tacorl_step_front_supported(int nsrc, const float* const* src_base, const long* src_pitch, int njobs,
+                                const float* const* pack_src, const long* pack_pitch, void* const* pack_dst,
+                                const int* pack_n, const void* disp, int disp_dtype, const float* reward, int B,
+                                const float* acts_src, const float* acts_dst, long n_acts, int H, int W);
+int tacorl_step_front_assemble(void* host_table, int nsrc, const float* const* src_base, const long* src_pitch, int njobs,
+                               const float* const* pack_src, const long* pack_pitch, void* const* pack_dst,
+                               const int* pack_n, const void* disp, int disp_dtype, float* reward, float* done, int B,
+                               const float* acts_src, float* acts_dst, long n_acts, int H, int W);
+int tacorl_step_front_fill(void* table, const void* host_table, tacorl_stream_t stream);
+int tacorl_step_front(const void* table, int njobs, int max_images, int B, long n_acts, int H, int W,
+                      tacorl_stream_t stream);
 /* The transition sampler of CQL_Offline's dataset (reference datamodule/dataset/goal_cond_replay_buffer_dataset.py:
  * 145-299) over resident tables, one thread per sample b < B:
  *   step = possible_steps[idx[b]], end = ep_end[k] of the last episode with ep_start[k] <= step (binary search), and by

@@ -145,6 +145,12 @@ _SIGS = {
     "tacorl_resize_frames_u8": (_i, [_p, _l, _p, _l, _l, _i, _i, _i, _i, _p]),
     "tacorl_pack_images_u8_aug_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "tacorl_stage_transition": (_i, [_p, _i, _p, _p, _i, _p, _p, _l, _p]),
+    "tacorl_step_front_table_bytes": (_l, []),
+    "tacorl_step_front_offsets": (_i, [_p]),
+    "tacorl_step_front_supported": (_i, [_i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _l, _i, _i]),
+    "tacorl_step_front_assemble": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _l, _i, _i]),
+    "tacorl_step_front_fill": (_i, [_p, _p, _p]),
+    "tacorl_step_front": (_i, [_p, _i, _i, _i, _l, _i, _i, _p]),
     "tacorl_sample_transitions": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p]),
     "tacorl_sample_relay": (_i, [_p, _l, _p, _p, _i, _p, _l, _p, _p, _p, _l, _l, _i, _i, _p, _p, _p, _p]),
     "tacorl_sample_d4rl_windows": (_i, [_p, _l, _p, _p, _i, _p, _p, _l, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p,

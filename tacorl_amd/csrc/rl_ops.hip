@@ -1,10 +1,14 @@
 // HBM-/latency-bound kernels of the CQL / TACO-RL step: image packing, tanh-Gaussian
 // sampling + log-prob, the fused Bellman + CQL logsumexp loss (fwd+bwd in one pass, wave
 // shuffle reductions), the twin-Q min for the actor loss, and the fused clip+Adam+Polyak.
+#include <stddef.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "../../include/tacorl_hip.h"
 #include "common.h"
+#include "encoder_fused.h"  // EFSrc: the front table carries the fused encoder's source entries
+#include "step_front_table.h"
 
 #define LAUNCH_OK() (hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH)
 
@@ -239,6 +243,127 @@ extern "C" int tacorl_stage_transition(const void* disp, int disp_dtype, float* 
   const int blocks = (int)((work + 255) / 256 > 1024 ? 1024 : (work + 255) / 256);
   hipLaunchKernelGGL(stage_transition_kernel, dim3(blocks < (B + 255) / 256 ? (B + 255) / 256 : blocks), dim3(256), 0,
                      (hipStream_t)stream, disp, disp_dtype, reward, done, B, acts_src, acts_dst, n_acts);
+  return LAUNCH_OK();
+}
+
+// ===================================================================== step front (TACORL)
+// What TACORL's fp32-source step needs from the batch, as ONE device-resident table at a fixed address: the fused encoder's
+// EFSrc entries ([window | next] per camera), the pack jobs [obs; goal] per engine camera and the transition's sources.
+// step_front_kernel takes the table's address, so as a captured graph node it follows the batch tensors that the last
+// fill named; the fill (arguments by value, one small block) is only issued when an entry changed.
+static_assert(sizeof(SFSrc) == sizeof(EFSrc) && offsetof(SFSrc, base) == offsetof(EFSrc, base) &&
+                  offsetof(SFSrc, img_pitch) == offsetof(EFSrc, img_pitch) && offsetof(SFSrc, plane_pitch) == offsetof(EFSrc, plane_pitch) &&
+                  offsetof(SFSrc, row_pitch) == offsetof(EFSrc, row_pitch),
+              "the front table's source entries are the fused encoder's");
+__global__ void step_front_fill_kernel(SFTable* __restrict__ tbl, SFTable f) {
+  const long* s = reinterpret_cast<const long*>(&f);
+  long* d = reinterpret_cast<long*>(tbl);
+  for (int i = threadIdx.x; i < (int)(sizeof(SFTable) / 8); i += blockDim.x) d[i] = s[i];
+}
+// blockIdx.y < njobs: the pack of job blockIdx.y - pack_nchw3_batch_kernel<__bf16>'s arithmetic (four x-adjacent pixels per
+// thread, three 16-byte plane loads, the same cast); the last blockIdx.y: stage_transition_kernel's work.
+__global__ void step_front_kernel(const SFTable* __restrict__ t) {
+  const int j = blockIdx.y;
+  if (j < t->njobs) {
+    const int HW = t->HW, q4 = HW / 4;
+    const long total = (long)t->pack_n[j] * q4, pitch = t->pack_pitch[j];
+    const float* __restrict__ src = t->pack_src[j];
+    __bf16* __restrict__ dst = reinterpret_cast<__bf16*>(t->pack_dst[j]);
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
+      const long img = q / q4;
+      const int p = (int)(q - img * q4) * 4;
+      const float* s = src + img * pitch + p;
+      const f32x4 r = *reinterpret_cast<const f32x4*>(s), g = *reinterpret_cast<const f32x4*>(s + HW),
+                  b = *reinterpret_cast<const f32x4*>(s + 2 * HW);
+      const float v[12] = {r[0], g[0], b[0], r[1], g[1], b[1], r[2], g[2], b[2], r[3], g[3], b[3]};
+      __bf16* d = dst + (img * HW + p) * 3;
+#pragma unroll
+      for (int k = 0; k < 3; k++)
+        *reinterpret_cast<bf16x4*>(d + 4 * k) = bf16x4{(__bf16)v[4 * k], (__bf16)v[4 * k + 1], (__bf16)v[4 * k + 2], (__bf16)v[4 * k + 3]};
+    }
+    return;
+  }
+  if (j != (int)gridDim.y - 1) return;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int B = t->B, disp_dtype = t->disp_dtype;
+  const void* __restrict__ disp = t->disp;
+  if (i < B) {
+    bool one;
+    if (disp_dtype == 0) one = static_cast<const float*>(disp)[i] == 1.0f;
+    else if (disp_dtype == 1) one = static_cast<const long long*>(disp)[i] == 1;
+    else if (disp_dtype == 2) one = static_cast<const int*>(disp)[i] == 1;
+    else one = static_cast<const unsigned char*>(disp)[i] == 1;
+    const float r = one ? 1.0f : 0.0f;
+    t->reward[i] = r;
+    if (t->done) t->done[i] = r;
+  }
+  const long n_acts = t->n_acts;
+  const float* __restrict__ acts_src = t->acts_src;
+  float* __restrict__ acts_dst = t->acts_dst;
+  for (long k = i; k < n_acts; k += (long)gridDim.x * blockDim.x) acts_dst[k] = acts_src[k];
+}
+extern "C" long tacorl_step_front_table_bytes(void) { return (long)sizeof(SFTable); }
+extern "C" int tacorl_step_front_offsets(long* out) {
+  if (!out) return TACORL_EINVAL;
+  const long o[TACORL_SF_NOFFSETS] = {
+      (long)offsetof(SFTable, src),      (long)offsetof(SFTable, pack_src),   (long)offsetof(SFTable, pack_dst),
+      (long)offsetof(SFTable, pack_pitch), (long)offsetof(SFTable, pack_n),   (long)offsetof(SFTable, disp),
+      (long)offsetof(SFTable, reward),   (long)offsetof(SFTable, done),       (long)offsetof(SFTable, acts_src),
+      (long)offsetof(SFTable, acts_dst), (long)offsetof(SFTable, n_acts),     (long)offsetof(SFTable, disp_dtype),
+      (long)offsetof(SFTable, B),        (long)offsetof(SFTable, njobs),      (long)offsetof(SFTable, HW)};
+  for (int i = 0; i < TACORL_SF_NOFFSETS; i++) out[i] = o[i];
+  return TACORL_OK;
+}
+/* Pure host (step_front_table.h): would the table take these entries?  Sources also as tacorl_encoder_src_supported takes
+ * them (contiguous 84 x 84 images). */
+extern "C" int tacorl_step_front_supported(int nsrc, const float* const* src_base, const long* src_pitch, int njobs,
+                                           const float* const* pack_src, const long* pack_pitch, void* const* pack_dst,
+                                           const int* pack_n, const void* disp, int disp_dtype, const float* reward, int B,
+                                           const float* acts_src, const float* acts_dst, long n_acts, int H, int W) {
+  if (!sf_supported(nsrc, src_base, src_pitch, njobs, pack_src, pack_pitch, pack_dst, pack_n, disp, disp_dtype, reward, B, acts_src,
+                    acts_dst, n_acts, H, W))
+    return 0;
+  for (int i = 0; i < nsrc; i++)
+    if (!tacorl_encoder_src_supported(src_base[i], src_pitch[i], (long)H * W, W, H, W)) return 0;
+  return 1;
+}
+/* Pure host: the table's bytes (tacorl_step_front_table_bytes() of them) for these entries into host_table. */
+extern "C" int tacorl_step_front_assemble(void* host_table, int nsrc, const float* const* src_base, const long* src_pitch,
+                                          int njobs, const float* const* pack_src, const long* pack_pitch,
+                                          void* const* pack_dst, const int* pack_n, const void* disp, int disp_dtype,
+                                          float* reward, float* done, int B, const float* acts_src, float* acts_dst,
+                                          long n_acts, int H, int W) {
+  if (!host_table || !tacorl_step_front_supported(nsrc, src_base, src_pitch, njobs, pack_src, pack_pitch, pack_dst, pack_n, disp,
+                                                  disp_dtype, reward, B, acts_src, acts_dst, n_acts, H, W))
+    return TACORL_EINVAL;
+  sf_assemble(static_cast<SFTable*>(host_table), nsrc, src_base, src_pitch, njobs, pack_src, pack_pitch, pack_dst, pack_n, disp,
+              disp_dtype, reward, done, B, acts_src, acts_dst, n_acts, H, W);
+  return TACORL_OK;
+}
+/* One launch writes the assembled bytes (by value) over the device table. */
+extern "C" int tacorl_step_front_fill(void* table, const void* host_table, tacorl_stream_t stream) {
+  if (!table || !host_table || ((uintptr_t)table & 7)) return TACORL_EINVAL;
+  SFTable f;
+  memcpy(&f, host_table, sizeof(SFTable));
+  if (!sf_table_sane(f)) return TACORL_EINVAL;
+  hipLaunchKernelGGL(step_front_fill_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, static_cast<SFTable*>(table), f);
+  return LAUNCH_OK();
+}
+/* The step's front over the table as it stands when the kernel RUNS.  njobs, max_images (the largest pack_n), B, n_acts and
+ * H * W size the grid only and must be what the fill wrote: a captured launch stays valid while the shapes do. */
+extern "C" int tacorl_step_front(const void* table, int njobs, int max_images, int B, long n_acts, int H, int W,
+                                 tacorl_stream_t stream) {
+  if (!table || njobs < 0 || njobs > TACORL_SF_MAXJOBS || (njobs > 0 && max_images < 1) || B < 1 || n_acts < 0 || H < 1 || W < 1 ||
+      ((long)H * W) % 4)
+    return TACORL_EINVAL;
+  const long pack = njobs > 0 ? ((long)max_images * (H * W / 4) + 255) / 256 : 0;
+  const long work = n_acts > B ? n_acts : B;
+  long blocks = pack > 8192 ? 8192 : pack;  // (the pack's own grid: tacorl_pack_images_batch)
+  const long small = (work + 255) / 256 > 1024 ? 1024 : (work + 255) / 256;
+  if (njobs == 0) blocks = small;
+  if (blocks < ((long)B + 255) / 256) blocks = ((long)B + 255) / 256;  // every transition row has its thread
+  hipLaunchKernelGGL(step_front_kernel, dim3((unsigned)blocks, njobs + 1), dim3(256), 0, (hipStream_t)stream,
+                     static_cast<const SFTable*>(table));
   return LAUNCH_OK();
 }
 

@@ -138,6 +138,63 @@ class SourceTable:
              Lg(*[H * W] * n), Lg(*[W] * n), H, W, ops.stream())
 
 
+class FrontTable:
+    """TACORL's step front on the fp32-source route as one device table at a fixed address (tacorl_step_front): per camera
+    the SourceTable entries [window | next], the pack jobs [obs; goal] of the engine cameras, the transition's sources and
+    destinations.  A step's entries are a PLAN - (sources, jobs, disp, disp dtype code, reward, done, B, action window source,
+    destination, element count, (H, W)): sources [(base address, image pitch in floats)] with entry k = camera k // 2's
+    [window | next][k % 2], jobs image_ingest.PackJob (src, pitch, dst, n), every pointer a raw device address (None: absent).
+    `accept` validates and assembles a plan on the host, `commit` issues the ONE fill launch only when the assembled bytes
+    differ from the bytes last written (`shadow`; the owner drops it - `invalidate` - where it reallocates or changes route):
+    the table holds addresses, sources and destinations alike, and the contents behind them are read by `launch` - a
+    captured graph node - every step."""
+
+    def __init__(self, device):
+        L = ops.L.lib()
+        self.nbytes, self.esz = int(L.tacorl_step_front_table_bytes()), int(L.tacorl_encoder_src_entry_bytes())
+        offs = (ops.C.c_long * 15)()
+        call("tacorl_step_front_offsets", offs)
+        self.src_off = int(offs[0])
+        self.buf = torch.zeros(self.nbytes, dtype=torch.uint8, device=device)
+        self.host = ops.C.create_string_buffer(self.nbytes)
+        self.plan = self.bytes = self.shadow = self.grid = None
+
+    def entry(self, cam, which):
+        """Device address of camera number `cam`'s source entry: which = 0 the window's frames, 1 the next observations."""
+        return self.buf.data_ptr() + self.src_off + (2 * cam + which) * self.esz
+
+    def invalidate(self):
+        self.shadow = None
+
+    def accept(self, plan):
+        """Does the table take this plan (tacorl_step_front_supported's rules)?  Then its bytes are kept for `commit`.  Pure
+        host; a plan equal to the last accepted one costs a tuple comparison."""
+        if plan != self.plan:
+            sources, jobs, disp, disp_dtype, reward, done, B, acts_src, acts_dst, n_acts, hw = plan
+            Ls, Lj = ops.C.c_long * len(sources), ops.C.c_long * len(jobs)
+            if ops.L.lib().tacorl_step_front_assemble(
+                    self.host, len(sources), ops.ptr_array([b for b, _ in sources]), Ls(*[p for _, p in sources]), len(jobs),
+                    ops.ptr_array([j.src for j in jobs]), Lj(*[j.pitch for j in jobs]), ops.ptr_array([j.dst for j in jobs]),
+                    ops.int_array([j.n for j in jobs]), disp, disp_dtype, reward, done, B, acts_src, acts_dst, n_acts, *hw) != 0:
+                return False
+            self.plan, self.bytes = plan, self.host.raw
+            self.grid = (len(jobs), max([j.n for j in jobs], default=0), B, n_acts, *hw)
+        return True
+
+    def commit(self):
+        """The accepted plan onto the device table, on the current stream (behind the previous step's readers of the table).
+        Returns whether a fill was issued."""
+        if self.bytes == self.shadow:
+            return False
+        call("tacorl_step_front_fill", ops.ptr(self.buf), self.bytes, ops.stream())
+        self.shadow = self.bytes
+        return True
+
+    def launch(self):
+        """The front of the step over the table as it stands (graph-capturable)."""
+        call("tacorl_step_front", ops.ptr(self.buf), *self.grid, ops.stream())
+
+
 def launch_fused(pr, packs, hw, max_wg=0):
     """One fused encoder launch over the problems pr (each carries its camera: cameras of one geometry may share a launch)
     on at most max_wg workgroups (0: one per CU); activations are saved only for the problems a backward follows."""

@@ -97,16 +97,29 @@ class TACORL(LatentPlanShell, CQL_Offline):
                                       act=self.f_act[c], n=B * T) for c in self.all_modalities]
         # entries [window | next] per camera for the batches whose forward-only images the encoder reads as fp32 (_fold_ok)
         self.src_tbl = {c: stage.SourceTable(dev, 2) for c in sorted(set(self.all_modalities) | set(self.engine.cams))}
-        self._folded = None
+        # ... and, for _step's batches, the whole front - those entries, the [obs; goal] pack, reward / done / action window -
+        # as one table that the step's first graph node reads (_front_plan)
+        self.front_tbl = stage.FrontTable(dev)
+        self._folded = self._front = None
         self._T = (B, T, tuple(sorted(hw.items())))
 
-    def _stage_small(self, batch, noise, B, T):
-        e = self.engine
+    def _small_sources(self, batch, B):
+        """(disp, its dtype code, the action window or None) where the transition kernel takes the batch's small tensors as they
+        stand, else None."""
         disp, acts = batch["disp"], batch["actions"] if self.ad is not None else None
         dd = {torch.float32: 0, torch.int64: 1, torch.int32: 2, torch.uint8: 3, torch.bool: 3}.get(disp.dtype)
         if (dd is not None and disp.is_cuda and disp.is_contiguous() and disp.numel() == B
                 and (acts is None or (acts.is_cuda and acts.is_contiguous() and acts.dtype == torch.float32
                                       and acts.shape == self.acts.shape))):
+            return disp, dd, acts
+        return None
+
+    def _stage_small(self, batch, noise, B, T):
+        e = self.engine
+        disp, acts = batch["disp"], batch["actions"] if self.ad is not None else None
+        small = self._small_sources(batch, B)
+        if small is not None:
+            dd = small[1]
             # reward = done = (disp == 1) and the action window, one launch
             call("tacorl_stage_transition", ptr(disp), dd, ptr(self.reward), ptr(e.done), B,
                  ptr(acts) if acts is not None else None, ptr(self.acts) if acts is not None else None,
@@ -135,11 +148,35 @@ class TACORL(LatentPlanShell, CQL_Offline):
         v, simg = f.frames[c], 3 * hw[0] * hw[1]
         return stage.SourceTable.ok(v.data_ptr(), simg, hw) and stage.SourceTable.ok(v.data_ptr() + 4 * (T - 1) * simg, T * simg, hw)
 
-    def _stage_frames(self, batch, noise, nchw=True, fold=False):
+    def _front_plan(self, f, batch, B, T, cams_all, folded):
+        """_step's batch on the fp32-source route, every camera folded: what the front table takes - (source entries
+        [window | next] per camera of cams_all, pack jobs [obs; goal] per engine camera, the transition's arguments) - or None:
+        a camera on the pack route, two geometries, small tensors the transition kernel does not take, too many cameras."""
+        e, Job = self.engine, ingest.PackJob
+        small = self._small_sources(batch, B)
+        if not folded or folded != tuple(cams_all) or small is None or len({tuple(f.hw[c]) for c in cams_all}) != 1:
+            return None
+        disp, dd, acts = small
+        sources, jobs = [], []
+        for c in cams_all:
+            src, simg = f.frames[c].data_ptr(), 3 * f.hw[c][0] * f.hw[c][1]
+            sources += [(src, simg), (src + 4 * (T - 1) * simg, T * simg)]
+            if c in e.cams:
+                x3, slot = e.X3.raw(c).data_ptr(), B * simg * e.X3.raw(c).element_size()
+                jobs += [Job(src, T * simg, x3, B), Job(batch["goal"][c].data_ptr(), simg, x3 + slot, B)]
+        plan = (tuple(sources), tuple(jobs), disp.data_ptr(), dd, self.reward.data_ptr(), e.done.data_ptr(), B,
+                acts.data_ptr() if acts is not None else None, self.acts.data_ptr() if acts is not None else None,
+                acts.numel() if acts is not None else 0, tuple(f.hw[cams_all[0]]))
+        return plan if self.front_tbl.accept(plan) else None
+
+    def _stage_frames(self, batch, noise, nchw=True, fold=False, front=False):
         """Eager part of the step: pack the window frames (reference NCHW fp32 -> NHWC image dtype) into
         fixed buffers, copy the small tensors, draw / copy the noise.
         uint8 frames - the dataset's own format, (B, T, H, W, 3) with goal (B, H, W, 3) - are taken as they are
-        and normalised on the way (ToTensor + Normalize(0.5, 0.5), bit-identical to the transformed fp32 frames)."""
+        and normalised on the way (ToTensor + Normalize(0.5, 0.5), bit-identical to the transformed fp32 frames).
+        front (the caller runs _device_front next): where every camera takes the fp32-source route (fold), the [obs; goal]
+        pack and the small tensors leave this eager part too - _device_front's first launch does them from the front table
+        (_front_plan), and what stays here is the noise and, when an address moved, the table's fill."""
         from ...data.replay import wait_ready
 
         wait_ready(batch)  # a replay batch's small tables travel on the feeder's copy stream
@@ -158,37 +195,55 @@ class TACORL(LatentPlanShell, CQL_Offline):
         if getattr(self, "_stage_stream", None) is None:
             self._stage_stream = torch.cuda.Stream(device=self.dev)
         main = torch.cuda.current_stream()
-        side = self._stage_stream if getattr(self, "stage_side", True) else main
-        side.wait_stream(main)  # the previous step's graph read these buffers
-        with torch.cuda.stream(side):
-            self._stage_small(batch, noise, B, T)
         u8, Job, ip = f.form in ingest.U8_FORMS, ingest.PackJob, None if f.ids is None else f.ids.data_ptr()
         cams_all = sorted(set(self.all_modalities) | set(e.cams))
         for c in cams_all:
             v = f.frames[c]
             assert v.is_cuda and v.is_contiguous() and v.dtype == (torch.uint8 if u8 else torch.float32)
         folded = tuple(c for c in cams_all if fold and self._fold_ok(f, c, T, batch))
-        if folded != self._folded:  # (a captured step holds the route: a batch of another kind drops it)
+        plan = self._front_plan(f, batch, B, T, cams_all, folded) if front else None
+        if folded != self._folded or (plan is not None) != self._front:
+            # (a captured step holds the route: a batch of another kind drops it)
             ops.note_alloc()
-            self._folded = folded
+            self.front_tbl.invalidate()
+            self._folded, self._front = folded, plan is not None
+        side = self._stage_stream if getattr(self, "stage_side", True) else main
+        if plan is not None:
+            # the front table's route: the noise is all that is drawn here (torch's two generator launches), beside nothing -
+            # hence on this stream, without the wait_stream pair (measured, profiles/step_front.md: on the side stream the
+            # cross-queue join in front of the graph costs more than the pair of launches, 0.7686 against 0.7448 ms/step)
+            side = main
+            self.front_tbl.commit()  # (on main, behind the previous step's graph: it read the table)
+            self._front_keep = (batch["goal"], batch["disp"], batch.get("actions"))  # (the step's first node reads them)
+        if side is not main:
+            side.wait_stream(main)  # the previous step's graph read these buffers
+        with torch.cuda.stream(side):
+            if plan is not None:
+                e.set_noise(noise)
+            else:
+                self._stage_small(batch, noise, B, T)
         self.frames.drop()  # (what the previous batch left for a reader is superseded)
         e.X3.drop()
-        e.fp_src = {c: {"next": self.src_tbl[c].entry(1)} for c in folded if c in e.cams}
+        tbl_i = {c: i for i, c in enumerate(cams_all)}
+        entry = (lambda c, k: self.front_tbl.entry(tbl_i[c], k)) if plan is not None else (lambda c, k: self.src_tbl[c].entry(k))
+        e.fp_src = {c: {"next": entry(c, 1)} for c in folded if c in e.cams}
         for x in e.extra_enc:
-            x["src"] = self.src_tbl[x["cam"]].entry(0) if x["cam"] in folded else None
+            x["src"] = entry(x["cam"], 0) if x["cam"] in folded else None
         for c in cams_all:
             v = f.frames[c]
             src, simg = v.data_ptr(), 3 * f.src_hw[c][0] * f.src_hw[c][1]  # (simg: elements of a source frame)
             if c in folded:
                 # entries [window | next = window frame T - 1]; of the images only s = states[:, 0] and the goal are packed
-                self.src_tbl[c].fill([(src, simg), (src + 4 * (T - 1) * simg, T * simg)], hw[c])
+                if plan is None:
+                    self.src_tbl[c].fill([(src, simg), (src + 4 * (T - 1) * simg, T * simg)], hw[c])
                 form, shw = f.form, f.src_hw[c]
                 later = lambda jobs, c=c, keep=v, form=form, shw=shw: ingest.pack(jobs, form, self.img_dtype, shw, hw[c])  # noqa: E731 (keep: the batch tensor stays alive for a reader)
                 if c in self.all_modalities:
                     self.frames.defer(c, lambda c=c, later=later, src=src, simg=simg: later([Job(src, simg, self.frames.raw(c).data_ptr(), B * T)]))
                 if c in e.cams:
                     x3, slot = e.X3.raw(c).data_ptr(), B * 3 * hw[c][0] * hw[c][1] * e.X3.raw(c).element_size()
-                    ingest.pack([Job(src, T * simg, x3, B), Job(batch["goal"][c].data_ptr(), simg, x3 + slot, B)], form, self.img_dtype, shw, hw[c])
+                    if plan is None:  # (else: the front table's pack jobs, _device_front's first launch)
+                        ingest.pack([Job(src, T * simg, x3, B), Job(batch["goal"][c].data_ptr(), simg, x3 + slot, B)], form, self.img_dtype, shw, hw[c])
                     e.X3.defer(c, lambda later=later, src=src, simg=simg, x3=x3, slot=slot: later([Job(src + 4 * (T - 1) * simg, T * simg, x3 + 2 * slot, B)]))
                 continue
             jobs, roles = [], []
@@ -211,7 +266,8 @@ class TACORL(LatentPlanShell, CQL_Offline):
                 ingest.pack_window(jobs, T, self.img_dtype, hw[c])  # one read of the window for its frames, obs and next
             else:
                 ingest.pack(jobs, f.form, self.img_dtype, f.src_hw[c], hw[c], aug["pad"][c] if aug is not None else None)
-        main.wait_stream(side)
+        if side is not main:
+            main.wait_stream(side)
         return B, T, hw
 
     def _ad_due(self):
@@ -223,6 +279,8 @@ class TACORL(LatentPlanShell, CQL_Offline):
         AD loss -> first phase of the CQL update (up to the alpha gradient)."""
         e = self.engine
         ops.mark("front:start")
+        if self._front:  # [obs; goal] pack, reward / done, action window: one node that follows the batch through the table
+            self.front_tbl.launch()
         if getattr(self, "_pr_stream", None) is None:
             self._pr_stream, self._side_stream = torch.cuda.Stream(device=self.dev), torch.cuda.Stream(device=self.dev)
         main = torch.cuda.current_stream()
@@ -350,7 +408,10 @@ class TACORL(LatentPlanShell, CQL_Offline):
         return self.plan
 
     def _step(self, batch, noise, optimize, log_type, nchw=True):
-        B, T, hw = self._stage_frames(batch, noise, nchw, fold=getattr(self, "fp32_ingest", True))
+        # (the front table serves the step that is ONE graph, or eager.  The step split into graph segments with eager
+        # collectives between them keeps the eager front: with the table its logging-only decoder pass, a side graph, no
+        # longer ran beside the segments - 0.85 -> 1.11 ms at B = 256, profiles/step_front.md section 6)
+        B, T, hw = self._stage_frames(batch, noise, nchw, fold=getattr(self, "fp32_ingest", True), front=not self._segmented())
         with_ad = self._ad_due()
         key = ("tacorl", B, T, tuple(sorted(hw.items())), self.current_epoch < self.bc_epochs, optimize, with_ad)
         e, bc = self.engine, self.current_epoch < self.bc_epochs
