@@ -952,6 +952,66 @@ int tacorl_tsne_step(const float* P, long N, float* Y, float* u, float* gains, f
                      void* ws, size_t ws_bytes, tacorl_stream_t stream);
 int tacorl_tsne_kl(const float* P, const float* Y, long N, float* out, void* ws, size_t ws_bytes, tacorl_stream_t stream);
 
+/* ---- neighbour-sparse t-SNE of latent plans (tsne_ops.hip) ----
+ * The same embedding above the dense path's 8192 rows: the reference library's sparse P over the K = floor(3 perplexity)
+ * nearest neighbours (the product 3 perplexity in fp32), with the repulsion taken exactly over all pairs - Barnes-Hut at
+ * theta = 0.  Nothing of size N x N exists.  Everything not stated here is the dense definition above, by the same kernels:
+ * the input normalisation to xn, w_ij, the update, the centring, the schedule.  fp64 restatement: tests/tsne_nbr_ref.py.
+ *
+ * Neighbour lists.  N(i): the K rows j != i with the smallest (d_ij, j), ascending; d_ij in the direct form of tacorl_knn_l2
+ *   on xn.  The row itself is left out by index, not by distance: a duplicate of row i is a neighbour at d = 0; ties go to
+ *   the lower row.  nbr_row (N, K) int32, nbr_dist (N, K) fp32, every element written (K <= N - 1: no list has an absent
+ *   entry).  A NaN distance counts as +inf (+inf itself, an overflow, is a distance like any other): a table with non-finite
+ *   values still gives every row K valid rows - for a row whose distances are all NaN the K lowest other rows, at +inf - so
+ *   nothing downstream addresses memory by a bad index; the conditionals of such a row are NaN and the row is counted in
+ *   status[0].  tacorl_tsne_nbr_knn is that step alone on any (N, D) table at a row pitch of ld floats: one thread per query,
+ *   64 queries per workgroup, the table through LDS in tiles of tacorl_tsne_nbr_knn_tile() rows, the lists (up to 96 KiB) in LDS.
+ * Conditionals.  The dense bisection (start 1, tolerance 1e-5, 200 evaluations, capped rows counted in status[0]) over the K
+ *   listed distances: m_i = the first neighbour's distance, t_s = d_s - m_i, e_s = expf(-(beta_i t_s)), S = sum_s e_s,
+ *   H_i = logf(S) + beta_i (sum_s e_s t_s) / S; cond (N, K) fp32 = e_s / S in list order, beta (N) kept.  Sums over the list:
+ *   lane l of the row's wave adds the positions l, l + 64, l + 128 in order, then the xor butterfly 32 .. 1.
+ * Symmetric P as CSR.  Row i holds every column j with j in N(i) or i in N(j), ascending in j; the value is (a + b) / (2 N)
+ *   with a = p_{j|i} if j in N(i), else 0, and b = p_{i|j} if i in N(j), else 0 - one fp32 addition and one division by
+ *   2.f * (float)N, as the dense symmetrisation - so P is symmetric bit for bit.  row_ptr (N + 1) int32, col and val with the
+ *   caller's capacity >= 2 N K entries (a hub row's in-degree is unbounded, the total is not); row_ptr[N] stays on the
+ *   device.  A row's length is counted and its one-sided in-entries are appended with integer atomics, then every row is
+ *   sorted by column: the result does not depend on the order in which the atomics landed.
+ * Forces.  attr_i = sum over row i's stored entries e of P_e w (y_i - y_col(e)): lane l of the row's wave adds the entries
+ *   l, l + 64, ... of the row in order, then the butterfly.  rep_i = sum_{j != i} w_ij^2 (y_i - y_j) and Z_i = sum_{j != i} w_ij
+ *   over ALL j: the j range is cut into segments of L = tacorl_tsne_nbr_segment(N) = 256 ceil(N / 8192) rows (at most 32 of
+ *   them); one thread adds a segment's j in ascending order from 0 (Y streams through LDS in tiles of 256), and the segments'
+ *   partial sums are added in ascending segment order from 0.  No float atomics; a run repeats bit for bit.  Z and the update
+ *   are the dense ones.  The grid is ceil(N / 256) x ceil(N / L) workgroups: 1024 at N = 8192, 16384 at N = 131072.
+ * Cost.  Over the stored entries, in attr's order: sum P_e (logf P_e + logf(1 + q_e)) + logf(Z) sum P_e, Z as above.
+ * Cross-check.  With K = N - 1 every list is the whole table, P has every off-diagonal entry, and this is, in real
+ *   arithmetic, the dense definition (the entropy runs over the same N - 1 distances, m_i is their minimum); the two differ
+ *   by the order of their sums only.
+ *
+ * Supported: 4 <= N <= tacorl_tsne_nbr_max_n() = 131072, 1 <= D <= 32, perplexity >= 1, K <= N - 1 and
+ * K <= tacorl_tsne_nbr_max_k() = 192 (perplexity 40: K = 120).  Nothing is allocated: ws holds
+ * tacorl_tsne_nbr_workspace_bytes(N) bytes, 16-byte aligned, shared by the three calls (about 66 MiB at N = 131072: xn and the
+ * segments' partials); tacorl_tsne_nbr_workspace_offsets writes the byte offsets of {xn (N, 32), attr (N, 2), rep (N, 2),
+ * Z_i (N)}.  status: int[2] as above.  Device pointers; Y 8-byte, ws 16-byte, the others 4-byte aligned.  A NULL or misaligned
+ * pointer, a short workspace or capacity, ld < D or a size, D, K or perplexity out of range is refused with TACORL_EINVAL
+ * before anything is launched.  Asynchronous on `stream`. */
+int tacorl_tsne_nbr_supported(long N, int D, int K);
+int tacorl_tsne_nbr_max_n(void);
+int tacorl_tsne_nbr_max_k(void);
+int tacorl_tsne_nbr_knn_tile(void);
+int tacorl_tsne_nbr_segment(long N); /* 0: N not supported */
+size_t tacorl_tsne_nbr_workspace_bytes(long N); /* 0: N not supported */
+int tacorl_tsne_nbr_workspace_offsets(long N, long* off4);
+int tacorl_tsne_nbr_knn(const float* points, long N, int D, long ld, int K, int* nbr_row, float* nbr_dist,
+                        tacorl_stream_t stream);
+int tacorl_tsne_nbr_affinities(const float* X, long N, int D, long ld, float perplexity, int* nbr_row, float* nbr_dist,
+                               float* cond, float* beta, int* row_ptr, int* col, float* val, long capacity, int* status,
+                               void* ws, size_t ws_bytes, tacorl_stream_t stream);
+/* One iteration in place on Y, u, gains (each (N, 2)). */
+int tacorl_tsne_nbr_step(const int* row_ptr, const int* col, const float* val, long N, float* Y, float* u, float* gains,
+                         float exaggeration, float momentum, float lr, void* ws, size_t ws_bytes, tacorl_stream_t stream);
+int tacorl_tsne_nbr_kl(const int* row_ptr, const int* col, const float* val, const float* Y, long N, float* out, void* ws,
+                       size_t ws_bytes, tacorl_stream_t stream);
+
 /* ---- rollout (rollout_ops.hip) ------------------------------------------------------ */
 /* A linear layer with two inputs for a handful of rows, read from torch's row-major (N, K) fp32 masters as they lie:
  *   y[r][n] = act(b1[n] + b2[n] + sum_k w1[n][k] x1[r][k] + sum_k w2[n][k] x2[r][k]),   r < R, n < N.

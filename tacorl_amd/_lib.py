@@ -194,6 +194,17 @@ _SIGS = {
     "tacorl_tsne_affinities": (_i, [_p, _l, _i, _l, _f, _p, _p, _p, _p, _sz, _p]),
     "tacorl_tsne_step": (_i, [_p, _l, _p, _p, _p, _f, _f, _f, _p, _sz, _p]),
     "tacorl_tsne_kl": (_i, [_p, _p, _l, _p, _p, _sz, _p]),
+    "tacorl_tsne_nbr_supported": (_i, [_l, _i, _i]),
+    "tacorl_tsne_nbr_max_n": (_i, []),
+    "tacorl_tsne_nbr_max_k": (_i, []),
+    "tacorl_tsne_nbr_knn_tile": (_i, []),
+    "tacorl_tsne_nbr_segment": (_i, [_l]),
+    "tacorl_tsne_nbr_workspace_bytes": (_sz, [_l]),
+    "tacorl_tsne_nbr_workspace_offsets": (_i, [_l, _p]),
+    "tacorl_tsne_nbr_knn": (_i, [_p, _l, _i, _l, _i, _p, _p, _p]),
+    "tacorl_tsne_nbr_affinities": (_i, [_p, _l, _i, _l, _f, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _sz, _p]),
+    "tacorl_tsne_nbr_step": (_i, [_p, _p, _p, _l, _p, _p, _p, _f, _f, _f, _p, _sz, _p]),
+    "tacorl_tsne_nbr_kl": (_i, [_p, _p, _p, _p, _l, _p, _p, _sz, _p]),
     "tacorl_rows_linear2_supported": (_i, [_i, _i, _i, _i]),
     "tacorl_rows_linear2_group": (_i, []),
     "tacorl_rows_linear2_fwd": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),

@@ -540,6 +540,104 @@ def tsne_kl(P, Y, ws, out=None):
     return out
 
 
+# ---- neighbour-sparse t-SNE (tsne_ops.hip; definition: include/tacorl_hip.h)
+TSNE_NBR_MAX_N, TSNE_NBR_MAX_K = 131072, 192
+
+
+def tsne_nbr_k(perplexity):
+    """K = floor(3 perplexity), the product taken in fp32 as the library takes it."""
+    import numpy as np
+
+    return int(np.floor(np.float32(3.0) * np.float32(perplexity)))
+
+
+def tsne_nbr_supported(N, D, K):
+    return bool(L.lib().tacorl_tsne_nbr_supported(int(N), int(D), int(K)))
+
+
+def tsne_nbr_workspace(N, device):
+    """A fresh workspace for the neighbour-sparse t-SNE calls on an (N, .) table (uint8), or TacorlHipError."""
+    nbytes = int(L.lib().tacorl_tsne_nbr_workspace_bytes(int(N)))
+    if nbytes == 0:
+        raise L.TacorlHipError(f"tsne_nbr: N = {N} not supported (4..{TSNE_NBR_MAX_N})")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def tsne_nbr_workspace_views(ws, N):
+    """{xn (N, 32), attr (N, 2), rep (N, 2), zrow (N)}: float views of what the last tsne_nbr_affinities / tsne_nbr_step left."""
+    off = (C.c_long * 4)()
+    call("tacorl_tsne_nbr_workspace_offsets", int(N), off)
+    f = ws.view(torch.float32)
+    return {k: f[o // 4: o // 4 + N * w].view(N, w) if w > 1 else f[o // 4: o // 4 + N]
+            for k, o, w in zip(("xn", "attr", "rep", "zrow"), off, (32, 2, 2, 1))}
+
+
+def _dense_rows(X):
+    assert X.dim() == 2 and X.dtype == torch.float32 and X.is_cuda, (X.dtype, X.device, X.dim())
+    N, D = X.shape
+    assert N >= 1 and (N == 1 or X.stride(0) >= D) and (D == 1 or X.stride(1) == 1), (X.shape, X.stride())
+    return N, D, int(X.stride(0)) if N > 1 else D
+
+
+def tsne_nbr_knn(points, K):
+    """The K nearest other rows of every row of points (N, D), by the definition of include/tacorl_hip.h "neighbour-sparse
+    t-SNE": nbr_row (N, K) int32, nbr_dist (N, K) fp32."""
+    N, D, ld = _dense_rows(points)
+    if not tsne_nbr_supported(N, D, K):
+        raise L.TacorlHipError(f"tsne_nbr_knn: N = {N} (4..{TSNE_NBR_MAX_N}) / D = {D} (1..{TSNE_MAX_D}) / K = {K} "
+                               f"(1..min({TSNE_NBR_MAX_K}, N - 1)) not supported")
+    nbr_row = torch.empty(N, K, dtype=torch.int32, device=points.device)
+    nbr_dist = torch.empty(N, K, dtype=torch.float32, device=points.device)
+    call("tacorl_tsne_nbr_knn", ptr(points), N, D, ld, int(K), ptr(nbr_row), ptr(nbr_dist), stream())
+    return nbr_row, nbr_dist
+
+
+def tsne_nbr_affinities(X, perplexity, ws=None):
+    """The neighbour-sparse symmetric P.  X: (N, D) fp32 device tensor with dense rows.  Returns a dict: nbr_row, nbr_dist and
+    cond (N, K), beta (N), the CSR row_ptr (N + 1) int32 / col / val (capacity 2 N K; row_ptr[N] entries are in use),
+    status (2) int32 and ws; nothing is read back here."""
+    N, D, ld = _dense_rows(X)
+    K = tsne_nbr_k(perplexity) if perplexity >= 1.0 else 0
+    if not tsne_nbr_supported(N, D, K):
+        raise L.TacorlHipError(f"tsne_nbr_affinities: N = {N} (4..{TSNE_NBR_MAX_N}) / D = {D} (1..{TSNE_MAX_D}) / perplexity = "
+                               f"{perplexity} (K = floor(3 perplexity) in 3..min({TSNE_NBR_MAX_K}, N - 1)) not supported")
+    dev = X.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    out = dict(nbr_row=torch.empty(N, K, **i32), nbr_dist=torch.empty(N, K, device=dev), cond=torch.empty(N, K, device=dev),
+               beta=torch.empty(N, device=dev), row_ptr=torch.empty(N + 1, **i32), col=torch.empty(2 * N * K, **i32),
+               val=torch.empty(2 * N * K, device=dev), status=torch.empty(2, **i32),
+               ws=tsne_nbr_workspace(N, dev) if ws is None else ws)
+    call("tacorl_tsne_nbr_affinities", ptr(X), N, D, ld, float(perplexity), ptr(out["nbr_row"]), ptr(out["nbr_dist"]),
+         ptr(out["cond"]), ptr(out["beta"]), ptr(out["row_ptr"]), ptr(out["col"]), ptr(out["val"]), 2 * N * K, ptr(out["status"]),
+         *_tsne_ws(out["ws"], N), stream())
+    return out
+
+
+def _tsne_csr(row_ptr, col, val):
+    assert row_ptr.dtype == torch.int32 and row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dim() == 1
+    assert col.dtype == torch.int32 and col.is_cuda and col.is_contiguous() and val.dtype == torch.float32 and val.is_cuda
+    assert val.is_contiguous() and col.numel() == val.numel()
+    return row_ptr.numel() - 1
+
+
+def tsne_nbr_step(row_ptr, col, val, Y, u, gains, exaggeration, momentum, lr, ws):
+    """One neighbour-sparse t-SNE iteration in place on Y, u, gains (each (N, 2) fp32); attr, rep and Z_i stay in ws."""
+    N = _tsne_csr(row_ptr, col, val)
+    _tsne_state(N, Y, u, gains)
+    call("tacorl_tsne_nbr_step", ptr(row_ptr), ptr(col), ptr(val), N, ptr(Y), ptr(u), ptr(gains), float(exaggeration),
+         float(momentum), float(lr), *_tsne_ws(ws, N), stream())
+
+
+def tsne_nbr_kl(row_ptr, col, val, Y, ws, out=None):
+    """KL(P || Q(Y)) over the stored entries as a (1,) fp32 device tensor."""
+    N = _tsne_csr(row_ptr, col, val)
+    _tsne_state(N, Y)
+    out = torch.empty(1, device=Y.device) if out is None else out
+    assert out.dtype == torch.float32 and out.is_cuda and out.numel() == 1
+    call("tacorl_tsne_nbr_kl", ptr(row_ptr), ptr(col), ptr(val), ptr(Y), N, ptr(out), *_tsne_ws(ws, N), stream())
+    return out
+
+
 def _at(t, off):
     return C.c_void_p(t.data_ptr() + 4 * off)
 

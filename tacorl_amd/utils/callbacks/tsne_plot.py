@@ -2,9 +2,11 @@
 the plan proposal samples on the validation set, coloured by the task a sequence completed.
 
 The reference embeds with MulticoreTSNE on host cores and draws with plotly into wandb; none of the three is a dependency
-here.  The embedding is tacorl_amd.evaluation.tsne.tsne_embed (exact t-SNE on the GPU; n_jobs is accepted and unused), and
-the "figure" is the data of the reference's figure: `self.last` = {"x_tsne", "labels", "shown", "kl", "step"} as host
-arrays, also logged as a plain dict where the logger's experiment has `.log`."""
+here.  The embedding is tacorl_amd.evaluation.tsne.tsne_embed (exact t-SNE on the GPU; n_jobs is accepted and unused) up to
+ops.TSNE_MAX_N plans and tsne_embed_neighbours (the reference library's sparse neighbour P, exact repulsion) above that; an
+epoch with more than `max_points` plans is subsampled, so a whole validation set never ends the run.  The "figure" is the
+data of the reference's figure: `self.last` = {"x_tsne", "labels", "shown", "kl", "step"} as host arrays, also logged as a
+plain dict where the logger's experiment has `.log`."""
 import logging
 import math
 
@@ -33,8 +35,11 @@ def _gather_rows(t):
 
 
 class TSNEPlot(CallbackBase):
-    def __init__(self, perplexity, n_jobs, plot_percentage, opacity, marker_size, tasks=None):
+    def __init__(self, perplexity, n_jobs, plot_percentage, opacity, marker_size, tasks=None, max_points=None):
+        """max_points: the most plans one map embeds (None: the neighbour path's cap, ops.TSNE_NBR_MAX_N); an epoch with more
+        is subsampled without replacement by self.rng."""
         self.perplexity, self.n_jobs, self.plot_percentage = perplexity, n_jobs, plot_percentage
+        self.max_points = max_points
         self.opacity, self.marker_size = opacity, marker_size
         if tasks is not None and "_target_" in tasks:
             tasks = instantiate(tasks)
@@ -75,9 +80,30 @@ class TSNEPlot(CallbackBase):
 
     # ------------------------------------------------------------------------------ the epoch's map
     def _get_tsne(self, sampled_plans):
-        from ...evaluation.tsne import tsne_embed
+        from ... import ops
+        from ...evaluation.tsne import tsne_embed, tsne_embed_neighbours
 
-        return tsne_embed(sampled_plans, perplexity=self.perplexity, return_kl=True)
+        n = sampled_plans.reshape(-1, sampled_plans.shape[-1]).shape[0]
+        embed = tsne_embed if n <= ops.TSNE_MAX_N else tsne_embed_neighbours
+        return embed(sampled_plans, perplexity=self.perplexity, return_kl=True)
+
+    def _subsample(self, plans, labels):
+        """At most max_points rows of both, the kept rows in their order.  With floor(3 perplexity) > ops.TSNE_NBR_MAX_K
+        (perplexity above 64) the neighbour path does not apply, so the limit is the dense path's ops.TSNE_MAX_N."""
+        from ... import ops
+
+        cap = ops.TSNE_NBR_MAX_N if self.max_points is None else min(int(self.max_points), ops.TSNE_NBR_MAX_N)
+        why = "max_points"
+        if ops.tsne_nbr_k(self.perplexity) > ops.TSNE_NBR_MAX_K and cap > ops.TSNE_MAX_N:
+            # lists longer than the neighbour path keeps: only the dense path takes this perplexity, and it stops at its own cap
+            cap, why = ops.TSNE_MAX_N, f"perplexity {self.perplexity:g} needs the dense path, which takes {ops.TSNE_MAX_N}"
+        n = plans.shape[0]
+        if n <= cap:
+            return plans, labels
+        keep = np.sort(self.rng.choice(n, size=cap, replace=False))
+        log.info("TSNEPlot: %d plans this epoch, the map embeds a random %d of them (%s)", n, cap, why)
+        idx = torch.from_numpy(keep)
+        return plans[idx.to(plans.device)], labels[idx.to(labels.device)]
 
     def _shown(self, labels):
         """The rows the reference's figure shows: a plot_percentage share of each group, the unlabelled capped at 100."""
@@ -98,6 +124,7 @@ class TSNEPlot(CallbackBase):
             plans, labels = _gather_rows(plans), _gather_rows(labels.to(plans.device))
             if dist.get_rank() != 0:
                 return
+        plans, labels = self._subsample(plans, labels)
         need = math.ceil(3 * self.perplexity + 1)
         if plans.shape[0] < need:
             log.info("TSNEPlot: %d plans, perplexity %g needs at least %d: no map this epoch", plans.shape[0], self.perplexity, need)
