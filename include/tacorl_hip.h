@@ -67,7 +67,12 @@ int tacorl_rnn_linear_fwd(const void* x_bf16, const void* w_bf16, const float* b
                           tacorl_stream_t stream);
 /* nprob <= 4 independent y = act(x W^T + b + addend) of one shape (M, K, N) in one launch, one activation per
  * problem: the wavefront schedule of the stacked RNN (launch s = recurrent step s-2l of every layer l plus
- * the input projection of step s-2l+1 of layers l >= 1). */
+ * the input projection of step s-2l+1 of layers l >= 1).
+ * In this entry and its _twin / _ext forms:
+ *   x_bf16[p] == NULL: a zero operand (the RNN's first step, h_{-1} = 0) - its K tiles are neither fetched nor multiplied;
+ *     bit-identical to passing a buffer of zeros for finite weights.  Only for a problem without twin rows (with twin rows:
+ *     TACORL_EINVAL); without a K extension either, the result is act(b + addend).
+ *   y[p] == NULL: the fp32 result is not stored, only the bf16 copy (which must then be given). */
 int tacorl_rnn_linear_fwd_batch(int nprob, const void* const* x_bf16, const void* const* w_bf16,
                                 const float* const* bias, const float* const* addend, int ld_add,
                                 float* const* y, void* const* y_bf16, int M, int K, int N, const int* acts,
@@ -322,6 +327,17 @@ int tacorl_mlp_fwd_fused_gather(int nprob, const int* nseg, const float* const* 
                                 const float* const* params, const void* const* params_bf16, float* const* act,
                                 const int* M, int n_layers, const int* dims, const int* acts, int lean,
                                 tacorl_stream_t stream);
+/* tacorl_mlp_fwd_fused_gather that also writes, for problems with xb_out[p] != NULL, the weight gradients' layer-0 operand:
+ * the input rows as bf16 [Mp][128] (Mp = M rounded up to 64), zeros beyond dims[0] columns and beyond M rows - the copy
+ * tacorl_mlp_bwd_fused_wgrad otherwise converts from x with a launch of its own.  xb_out[p] = the backward site's workspace +
+ * tacorl_mlp_bwd_fused_xb_offset(...) (-1: problem p of that site has no such region); the site's _wgrad call then passes
+ * lean | 2.  Only for problems of a lean site with 2048 <= M < 16384 rows; TACORL_EINVAL otherwise. */
+int tacorl_mlp_fwd_fused_gather_xb(int nprob, const int* nseg, const float* const* seg_ptr, const int* seg_ld,
+                                   const int* seg_c0, const int* seg_mod, float* const* x_out, void* const* xb_out, int ldx,
+                                   const float* const* params, const void* const* params_bf16, float* const* act,
+                                   const int* M, int n_layers, const int* dims, const int* acts, int lean,
+                                   tacorl_stream_t stream);
+long tacorl_mlp_bwd_fused_xb_offset(int nprob, const int* M, int n_layers, const int* dims, int p);
 /* dst[i][:] = bf16(src[i][:]) for n <= 16 buffers in one launch (count[i] % 4 == 0). */
 int tacorl_to_bf16_batch(int n, const float* const* src, void* const* dst, const long* count,
                          tacorl_stream_t stream);
@@ -369,6 +385,10 @@ int tacorl_prep_batch_begin(void);
 int tacorl_reduce_batch_begin(void);
 int tacorl_reduce_batch_end(tacorl_stream_t stream);
 int tacorl_prep_batch_end(tacorl_stream_t stream);
+/* lean: bit 0 = the site runs lean (above); bit 1 = the many-row problems' bf16 input rows in ws are current - the forward
+ * wrote them (tacorl_mlp_fwd_fused_gather_xb) - so x is not converted again.  Bit 1 for a region no such forward was given
+ * (with this M, on this host thread) since the last _wgrad call over it is TACORL_EINVAL: every _wgrad call uses the note up.
+ * This guards against a bit set without the address having been passed; it tracks addresses, not the bytes behind them. */
 int tacorl_mlp_bwd_fused_wgrad(int nprob, const float* const* x, int ldx, const float* const* act,
                                const float* const* d_out, int ldo, float* const* grads, const int* M,
                                int n_layers, const int* dims, const int* acts, int accumulate, int lean,

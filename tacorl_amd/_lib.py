@@ -74,6 +74,8 @@ _SIGS = {
     "tacorl_mlp_fwd_fused": (_i, [_i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p]),
     "tacorl_mlp_fwd_fused_gather_supported": (_i, [_i, _p, _i, _p, _p, _i, _i]),
     "tacorl_mlp_fwd_fused_gather": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p]),
+    "tacorl_mlp_fwd_fused_gather_xb": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p]),
+    "tacorl_mlp_bwd_fused_xb_offset": (_l, [_i, _p, _i, _p, _i]),
     "tacorl_add_rows_bcast": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _p]),
     "tacorl_attention_fwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "tacorl_attention_dropout_fwd": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _p]),

@@ -1120,6 +1120,9 @@ static int mlp_fwd_fused_impl(int nprob, const float* const* x, int ldx, const f
     tacorl_mlp_act_layout(M[p], L, dims, acts, z1, y1);
     const int b = (lean && mlp_big_prob_ok(M[p], L, dims, acts)) ? 1 : 0, q = n[b]++;
     gm[b][q] = p;
+    if (gather && gather->xb[p] && (!b || M[p] >= 16384 || !aligned16(gather->xb[p])))
+      FAIL(TACORL_EINVAL, "mlp_fwd_fused_gather_xb: problem %d: the bf16 input rows are written only for a lean site's problems of "
+                          "2048 .. 16383 rows, 16-byte aligned", p);
     xs[b][q] = x ? x[p] : nullptr; ps[b][q] = params[p]; pb[b][q] = params_bf16[p]; as[b][q] = act[p]; Ms[b][q] = M[p];
     for (int l = 0; l < L; l++) {
       if (b) { ybf[q * MF_MAXL + l] = y1[l]; sbf[q * MF_MAXL + l] = z1[l]; }
@@ -1158,23 +1161,78 @@ extern "C" int tacorl_mlp_fwd_fused_gather_supported(int nprob, const int* M, in
   (void)M; (void)acts; (void)lean;  // (the many-row kernels gather too since round 5)
   return mlp_fused_fwd_ok(nprob, L, dims, ldx) ? 1 : 0;
 }
-extern "C" int tacorl_mlp_fwd_fused_gather(int nprob, const int* nseg, const float* const* seg_ptr, const int* seg_ld,
-                                           const int* seg_c0, const int* seg_mod, float* const* x_out, int ldx,
-                                           const float* const* params, const void* const* params_bf16, float* const* act,
-                                           const int* M, int L, const int* dims, const int* acts, int lean,
-                                           tacorl_stream_t stream) {
+// The bf16 input rows a forward has written (tacorl_mlp_fwd_fused_gather_xb), by address: tacorl_mlp_bwd_fused_wgrad takes
+// "the workspace's xb is current" (lean bit 1) only for an address listed here with the same row count, and every
+// weight-gradient call over an address takes it off the list again (with the bit: the image is used up; without it: the call
+// converts x itself) - so the bit needs a forward of this entry since the site's last weight gradients.  Per host thread, as
+// the preparation and reduce batches are: a site's forward and backward are issued by one thread.
+// THE LIMIT OF THIS: it is a guard against a caller that sets the bit without having passed the address (a stale or never
+// written region), not a proof about the bytes.  It knows addresses, not buffers: a forward of the same site through another
+// entry between the two calls, or a freed workspace whose address a new one reuses before the weight gradients run, is not
+// seen.  Sixteen addresses; an older one that falls out is refused, never accepted.
+namespace {
+struct XbWritten { const void* ptr; int M; };
+thread_local XbWritten g_xb_written[16];
+thread_local int g_xb_next = 0;
+void xb_note(const void* ptr, int M) {
+  for (XbWritten& e : g_xb_written)
+    if (e.ptr == ptr) { e.M = M; return; }
+  g_xb_written[g_xb_next] = XbWritten{ptr, M};
+  g_xb_next = (g_xb_next + 1) % 16;
+}
+bool xb_noted(const void* ptr, int M) {
+  for (const XbWritten& e : g_xb_written)
+    if (e.ptr == ptr && e.M == M) return true;
+  return false;
+}
+void xb_forget(const void* ptr) {
+  for (XbWritten& e : g_xb_written)
+    if (e.ptr == ptr) e = XbWritten{nullptr, 0};
+}
+}  // namespace
+static int mlp_fwd_fused_gather_impl(int nprob, const int* nseg, const float* const* seg_ptr, const int* seg_ld,
+                                     const int* seg_c0, const int* seg_mod, float* const* x_out, void* const* xb_out, int ldx,
+                                     const float* const* params, const void* const* params_bf16, float* const* act,
+                                     const int* M, int L, const int* dims, const int* acts, int lean,
+                                     tacorl_stream_t stream) {
   if (nprob < 1 || nprob > MF_MAXP || !nseg || !seg_ptr || !seg_ld || !seg_c0 || !seg_mod) FAIL(TACORL_EINVAL, "mlp_fwd_fused_gather: arguments");
   MlpXGather g{};
   for (int p = 0; p < nprob; p++) {
     if (nseg[p] < 1 || nseg[p] > MF_MAXSEG) FAIL(TACORL_EINVAL, "mlp_fwd_fused_gather: nseg[%d] = %d", p, nseg[p]);
     g.nseg[p] = nseg[p];
     g.xw[p] = x_out ? x_out[p] : nullptr;
+    g.xb[p] = xb_out ? xb_out[p] : nullptr;
     for (int t = 0; t < nseg[p]; t++) {
       g.ptr[p][t] = seg_ptr[MF_MAXSEG * p + t]; g.ld[p][t] = seg_ld[MF_MAXSEG * p + t];
       g.c0[p][t] = seg_c0[MF_MAXSEG * p + t]; g.mod[p][t] = seg_mod[MF_MAXSEG * p + t];
     }
   }
-  return mlp_fwd_fused_impl(nprob, nullptr, ldx, params, params_bf16, act, M, L, dims, acts, lean, stream, &g);
+  const int rc = mlp_fwd_fused_impl(nprob, nullptr, ldx, params, params_bf16, act, M, L, dims, acts, lean, stream, &g);
+  if (rc == TACORL_OK)
+    for (int p = 0; p < nprob; p++)
+      if (g.xb[p] && M[p] > 0) xb_note(g.xb[p], M[p]);
+  return rc;
+}
+extern "C" int tacorl_mlp_fwd_fused_gather(int nprob, const int* nseg, const float* const* seg_ptr, const int* seg_ld,
+                                           const int* seg_c0, const int* seg_mod, float* const* x_out, int ldx,
+                                           const float* const* params, const void* const* params_bf16, float* const* act,
+                                           const int* M, int L, const int* dims, const int* acts, int lean,
+                                           tacorl_stream_t stream) {
+  return mlp_fwd_fused_gather_impl(nprob, nseg, seg_ptr, seg_ld, seg_c0, seg_mod, x_out, nullptr, ldx, params, params_bf16, act, M,
+                                   L, dims, acts, lean, stream);
+}
+/* tacorl_mlp_fwd_fused_gather that also writes, for problems with xb_out[p] != NULL, the weight gradients' layer-0 operand: the
+ * input rows as bf16 [Mp][128] (Mp = M rounded up to 64), zero beyond dims[0] columns and M rows - what
+ * tacorl_mlp_bwd_fused_wgrad otherwise converts from x with a launch of its own.  xb_out[p] = the backward site's workspace +
+ * tacorl_mlp_bwd_fused_xb_offset(...); the site's weight gradients then pass lean | 2.  Only for problems of a lean site with
+ * 2048 <= M < 16384 rows (the kernels that hold those bf16 chunks in registers); TACORL_EINVAL otherwise. */
+extern "C" int tacorl_mlp_fwd_fused_gather_xb(int nprob, const int* nseg, const float* const* seg_ptr, const int* seg_ld,
+                                              const int* seg_c0, const int* seg_mod, float* const* x_out, void* const* xb_out,
+                                              int ldx, const float* const* params, const void* const* params_bf16,
+                                              float* const* act, const int* M, int L, const int* dims, const int* acts, int lean,
+                                              tacorl_stream_t stream) {
+  return mlp_fwd_fused_gather_impl(nprob, nseg, seg_ptr, seg_ld, seg_c0, seg_mod, x_out, xb_out, ldx, params, params_bf16, act, M,
+                                   L, dims, acts, lean, stream);
 }
 struct ToBf16Tbl { const float* src[16]; __bf16* dst[16]; long n4[16]; };
 __global__ void to_bf16_batch_kernel(ToBf16Tbl t) {
@@ -1247,6 +1305,13 @@ extern "C" int tacorl_mlp_bwd_fused_supported(int nprob, int L, const int* dims,
 extern "C" size_t tacorl_mlp_bwd_fused_ws_bytes(int nprob, const int* M, int L, const int* dims) {
   if (nprob < 1 || nprob > MF_MAXP || L < 1 || L > MF_MAXL) return 0;
   return mlp_bwd_fused_plan(nprob, M, L, dims).total;
+}
+/* Byte offset, inside the workspace of a backward site (nprob, M, L, dims), of problem p's bf16 input rows - the region
+ * tacorl_mlp_bwd_fused_wgrad reads as layer 0's operand (same plan, so the two cannot disagree); -1: problem p has none
+ * (not a many-row problem). */
+extern "C" long tacorl_mlp_bwd_fused_xb_offset(int nprob, const int* M, int L, const int* dims, int p) {
+  if (nprob < 1 || nprob > MF_MAXP || L < 1 || L > MF_MAXL || p < 0 || p >= nprob || !mlp_big_prob_ok(M[p], L, dims, nullptr)) return -1;
+  return (long)mlp_bwd_fused_plan(nprob, M, L, dims).xb_off[p];
 }
 extern "C" int tacorl_mlp_bwd_fused_dgrad(int nprob, const float* const* params, const float* const* act,
                                           const float* const* d_out, int ldo, float* const* d_x, int ldd, const int* M,
@@ -1332,6 +1397,11 @@ extern "C" int tacorl_mlp_bwd_fused_wgrad(int nprob, const float* const* x, int 
                                           tacorl_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
   if (nprob < 1 || nprob > MF_MAXP || L < 1 || L > MF_MAXL) FAIL(TACORL_EINVAL, "mlp_bwd_fused_wgrad: bad L/nprob");
+  // lean bit 1: the many-row problems' bf16 input rows in ws are current (the forward wrote them:
+  // tacorl_mlp_fwd_fused_gather_xb) - no conversion launch; refused unless such a forward was given these addresses since
+  // the last weight gradients over them (xb_note above, with what that does and does not establish)
+  const bool xb_current = (lean & 2) != 0;
+  lean &= ~2;
   const MlpBwdWs w = mlp_bwd_fused_plan(nprob, M, L, dims);
   if (ws_bytes < w.total) FAIL(TACORL_ENOMEM, "mlp_bwd_fused_wgrad: workspace too small");
   long wo[MLP_MAXL], bo[MLP_MAXL];
@@ -1355,13 +1425,16 @@ extern "C" int tacorl_mlp_bwd_fused_wgrad(int nprob, const float* const* x, int 
     const int b = (lean && mlp_big_prob_ok(M[p], L, dims, acts)) ? 1 : 0, q = n[b]++;
     xs[b][q] = x[p]; as[b][q] = act[p]; ds[b][q] = d_out[p]; dzp[b][q] = (const float*)ws; gs[b][q] = grads[p]; Ms[b][q] = M[p];
     if (b) xb[q] = (unsigned char*)ws + w.xb_off[p];
+    if (b && xb_current && grads[p] && M[p] > 0 && !xb_noted(xb[q], M[p]))
+      FAIL(TACORL_EINVAL, "mlp_bwd_fused_wgrad: problem %d: no forward has written the workspace's bf16 input rows", p);
     for (int l = 0; l < L; l++) {
       dzo[b][q * MF_MAXL + l] = w.dzoff[p * MF_MAXL + l];
       yoffs[b][q * MF_MAXL + l] = b ? yo[l] : ((lean && l + 1 < L && zo[l] >= 0) ? -(zo[l] + 1) : yo[l]);
     }
   }
+  for (int q = 0; q < n[1]; q++) xb_forget(xb[q]);  // (every problem has passed the check above)
   if (n[1] && mlp_fused_wgrad_big(n[1], xs[1], ldx, as[1], ds[1], ldo, dzp[1], gs[1], (float*)slab, xb, Ms[1], L, dims, yoffs[1],
-                                  dzo[1], wo, bo, accumulate, st, w.slab_bytes / sizeof(float)))
+                                  dzo[1], wo, bo, accumulate, st, w.slab_bytes / sizeof(float), xb_current))
     FAIL(TACORL_ELAUNCH, "mlp_bwd_fused_wgrad: many-row launch failed (or its records exceed the planned slab)");
   if (!n[0]) return TACORL_OK;
   if (mlp_fused_wgrad_ok(n[0], L, dims)) {  // every layer and network in one launch (+ one reduce)

@@ -15,6 +15,7 @@ struct MlpXGather {
   int ld[MF_MAXP][MF_MAXSEG], c0[MF_MAXP][MF_MAXSEG], mod[MF_MAXP][MF_MAXSEG];
   int nseg[MF_MAXP];
   float* xw[MF_MAXP];
+  void* xb[MF_MAXP];  // many-row problems below 16 384 rows only: also the bf16 [Mp][128] copy (MlpBigFwdArgs.xb), or NULL
 };
 
 // bf16 compute only: hidden widths multiples of 8, every width <= 256 (the input width may be ragged, e.g. 64 + 7).
@@ -75,4 +76,4 @@ size_t mlp_big_xb_bytes(int M);
 int mlp_fused_wgrad_big(int nprob, const float* const* x, int ldx, const float* const* act, const float* const* d_out, int ldo,
                         const float* const* dz, float* const* grads, float* slab, void* const* xb, const int* M, int L,
                         const int* dims, const long* ybf, const long* dzoff, const long* woff, const long* boff, int accumulate,
-                        hipStream_t st, size_t slab_floats);
+                        hipStream_t st, size_t slab_floats, bool xb_current = false);

@@ -692,6 +692,7 @@ int red_flush(hipStream_t st) {
   m.njob = 0; m.first[0] = 0;
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+bool red_batch_open() { return g_red.on; }
 // the reduce of one site: launched, or recorded while a batch is open
 int launch_reduce(const MlpWgReduceArgs& r, int gx, int Ly, int nprob, hipStream_t st) {
   if (!g_red.on) {
@@ -732,6 +733,9 @@ struct MlpBigFwdArgs {
   MlpXSeg seg[MF_MAXP][MF_MAXSEG];  // gathered layer-0 input (see MlpFwdArgs)
   int nseg[MF_MAXP];
   float* xw[MF_MAXP];
+  // optional: the input rows as the weight gradients' layer-0 operand - bf16 [Mp][128], zero beyond dims[0] columns / M rows,
+  // the image mlp_x_to_bf16_kernel makes of the fp32 rows (the per-block kernels only; mlp_big_fwd refuses it elsewhere)
+  __bf16* xb[MF_MAXP];
   const float* x[MF_MAXP];
   const float* params[MF_MAXP];
   const __bf16* pbf[MF_MAXP];
@@ -808,6 +812,14 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
   if (n0 < a.dims[1]) load_layer(0);
   auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
   for (int e = tid; e < 2 * BMF * XP / 8; e += MF_NT) reinterpret_cast<f32x4*>(X)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+  __bf16* xb = a.xb[p];
+  if (xb) {  // the zeros of the [Mp][128] image: the chunks beyond the input width and the pad rows of this block
+    for (int e = tid; e < BMF * 16; e += MF_NT) {
+      const int row = e >> 4, ch = e & 15;
+      if (m0 + row < Mp && (m0 + row >= M || ch >= c8))
+        *reinterpret_cast<f32x4*>(xb + (long)(m0 + row) * 128 + 8 * ch) = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
   lds_barrier();
 #pragma unroll
   for (int u = 0; u < 2; u++) {
@@ -817,6 +829,7 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
 #pragma unroll
       for (int j = 0; j < 4; j++) { v[j] = (__bf16)(k + j < K0 ? xr[u][0][j] : 0.f); v[4 + j] = (__bf16)(k + 4 + j < K0 ? xr[u][1][j] : 0.f); }
       *reinterpret_cast<bf16x8*>(X + row * XP + k) = v;
+      if (xb) *reinterpret_cast<bf16x8*>(xb + (long)(m0 + row) * 128 + k) = v;  // (the very chunk layer 0 multiplies)
       if (ns > 0 && a.xw[p]) {  // the assembled fp32 rows (the gather masked them at the segment ends: pad columns are zeros)
         float* o = a.xw[p] + (long)(m0 + row) * a.ldx + k;
         if (k + 8 <= a.ldx) { *reinterpret_cast<f32x4*>(o) = xr[u][0]; *reinterpret_cast<f32x4*>(o + 4) = xr[u][1]; }
@@ -1602,6 +1615,81 @@ __device__ __forceinline__ bf16x8 bg_tr_frag8(const unsigned char* lo, const uns
   return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// last layer with NL <= 4 outputs: dW[n][k] = sum_r bf16(d_out[r][n]) * y[r][k], db[n] = sum_r bf16(d_out[r][n]) (the operand
+// rounding of the MFMA path); y bf16 [Mp][256].  A bandwidth kernel (51 MB of y per network): OUT_RPW rows per workgroup,
+// thread = (row group of 8, 8 columns), four 16-byte loads in flight per thread; partials [slice][NL][257] to a slab of
+// their own, summed in slice order by mlp_wgrad_reduce_kernel (as a one-layer record).
+constexpr int OUT_RPW = 512;
+struct MlpWgOutArgs {
+  const __bf16* y[MF_MAXP]; const float* dlast[MF_MAXP]; float* slab[MF_MAXP];
+  int M[MF_MAXP];
+  long rec;
+  int NL, ldo, rpw;  // rpw: rows per workgroup (OUT_RPW at tens of thousands of rows, 64 at a few thousand: latency, not bytes)
+};
+// At a few thousand rows (rpw 64: latency, not bytes) it runs as one more blockIdx.y plane of mlp_wgrad_big_kernel's launch - it
+// needs only the forward's saved y and d_out, not the MFMA planes' results, and was a launch of its own behind them: the first
+// 256 threads of the workgroup compute, all of them reach the barrier; red [8][4][257] floats lives at the start of the launch's
+// dynamic LDS.  At tens of thousands of rows it stays a launch of its own (mlp_wgrad_out_kernel below): as a plane it is one
+// 96 KB workgroup per CU with half its threads idle, too few loads in flight for 51 MB per network (C5: +56 us on the step).
+constexpr int OUT_NT = 256;
+__device__ __forceinline__ void mlp_wgrad_out_body(const MlpWgOutArgs& a, int p, float (*red)[4][256 + 1]) {
+  const int M = a.M[p], r0 = blockIdx.x * a.rpw;
+  if (r0 >= M) return;  // (the whole workgroup)
+  const int r1 = min(M, r0 + a.rpw), tid = threadIdx.x, cg = tid & 31, rg = (tid >> 5) & 7, NL = a.NL;
+  const bool on = tid < OUT_NT;
+  float acc[4][8], bsum[4];
+#pragma unroll
+  for (int n = 0; n < 4; n++) {
+    bsum[n] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) acc[n][j] = 0.f;
+  }
+  const __bf16* __restrict__ y = a.y[p];
+  const float* __restrict__ d = a.dlast[p];
+  for (int rb = on ? r0 + rg : r1; rb < r1; rb += 32) {
+    bf16x8 v[4];
+    float dv[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {  // (rows beyond the slice: clamped address, zero weight)
+      const int r = rb + 8 * u, rc = r < r1 ? r : r0;
+      v[u] = *reinterpret_cast<const bf16x8*>(y + (long)rc * 256 + 8 * cg);
+#pragma unroll
+      for (int n = 0; n < 4; n++) dv[u][n] = (n < NL && r < r1) ? (float)(__bf16)d[(long)rc * a.ldo + n] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+      for (int n = 0; n < 4; n++)
+        if (n < NL) {
+          bsum[n] += dv[u][n];
+#pragma unroll
+          for (int j = 0; j < 8; j++) acc[n][j] += dv[u][n] * (float)v[u][j];
+        }
+  }
+  if (on) {
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+#pragma unroll
+      for (int j = 0; j < 8; j++) red[rg][n][8 * cg + j] = acc[n][j];
+      if (cg == 0) red[rg][n][256] = bsum[n];
+    }
+  }
+  __syncthreads();
+  float* rec = a.slab[p] + (long)blockIdx.x * a.rec;  // one-layer record: [NL][256] then [NL]
+  for (int e = on ? tid : NL * 257; e < NL * 257; e += OUT_NT) {
+    const int n = e / 257, k = e - n * 257;
+    float t = 0.f;
+#pragma unroll
+    for (int g8 = 0; g8 < 8; g8++) t += red[g8][n][k];  // fixed order
+    if (k < 256) rec[(long)n * 256 + k] = t; else rec[(long)NL * 256 + n] = t;
+  }
+}
+
+__global__ __launch_bounds__(OUT_NT) void mlp_wgrad_out_kernel(MlpWgOutArgs a) {
+  __shared__ float red[8][4][256 + 1];
+  mlp_wgrad_out_body(a, blockIdx.y, red);
+}
+
 struct MlpWgBigArgs {
   const __bf16* dz[MF_MAXP][MF_MAXL];  // [Mp][256]
   const __bf16* xb[MF_MAXP][MF_MAXL];  // [Mp][ldxb[l]]
@@ -1614,8 +1702,14 @@ struct MlpWgBigArgs {
   int rps;                             // rows per slice (a multiple of BG_R)
 };
 
-__global__ __launch_bounds__(64 * BG_NW) void mlp_wgrad_big_kernel(MlpWgBigArgs a) {
+// grid (max(row slices, output-layer slices), x tiles + 1, problems): blockIdx.y == tile0[nl] is the output layer's plane (where
+// the launch has one)
+__global__ __launch_bounds__(64 * BG_NW) void mlp_wgrad_big_kernel(MlpWgBigArgs a, MlpWgOutArgs oa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  if ((int)blockIdx.y == a.tile0[a.nl]) {
+    mlp_wgrad_out_body(oa, blockIdx.z, reinterpret_cast<float(*)[4][256 + 1]>(lds));
+    return;
+  }
   const int p = blockIdx.z, Mp = a.Mp[p];
   const int r_begin = blockIdx.x * a.rps;
   if (r_begin >= Mp) return;
@@ -1734,68 +1828,6 @@ __global__ __launch_bounds__(256) void mlp_x_to_bf16_kernel(MlpXbArgs a) {
       }
     }
     *reinterpret_cast<bf16x8*>(o + (long)row * 128 + k) = v;
-  }
-}
-
-// last layer with NL <= 4 outputs: dW[n][k] = sum_r bf16(d_out[r][n]) * y[r][k], db[n] = sum_r bf16(d_out[r][n]) (the operand
-// rounding of the MFMA path); y bf16 [Mp][256].  A bandwidth kernel (51 MB of y per network): OUT_RPW rows per workgroup,
-// thread = (row group of 8, 8 columns), four 16-byte loads in flight per thread; partials [slice][NL][257] to a slab of
-// their own, summed in slice order by mlp_wgrad_reduce_kernel (as a one-layer record).
-constexpr int OUT_RPW = 512;
-struct MlpWgOutArgs {
-  const __bf16* y[MF_MAXP]; const float* dlast[MF_MAXP]; float* slab[MF_MAXP];
-  int M[MF_MAXP];
-  long rec;
-  int NL, ldo, rpw;  // rpw: rows per workgroup (OUT_RPW at tens of thousands of rows, 64 at a few thousand: latency, not bytes)
-};
-__global__ __launch_bounds__(256) void mlp_wgrad_out_kernel(MlpWgOutArgs a) {
-  __shared__ float red[8][4][256 + 1];
-  const int p = blockIdx.y, M = a.M[p], r0 = blockIdx.x * a.rpw;
-  if (r0 >= M) return;
-  const int r1 = min(M, r0 + a.rpw), tid = threadIdx.x, cg = tid & 31, rg = tid >> 5, NL = a.NL;
-  float acc[4][8], bsum[4];
-#pragma unroll
-  for (int n = 0; n < 4; n++) {
-    bsum[n] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; j++) acc[n][j] = 0.f;
-  }
-  const __bf16* __restrict__ y = a.y[p];
-  const float* __restrict__ d = a.dlast[p];
-  for (int rb = r0 + rg; rb < r1; rb += 32) {
-    bf16x8 v[4];
-    float dv[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {  // (rows beyond the slice: clamped address, zero weight)
-      const int r = rb + 8 * u, rc = r < r1 ? r : r0;
-      v[u] = *reinterpret_cast<const bf16x8*>(y + (long)rc * 256 + 8 * cg);
-#pragma unroll
-      for (int n = 0; n < 4; n++) dv[u][n] = (n < NL && r < r1) ? (float)(__bf16)d[(long)rc * a.ldo + n] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-      for (int n = 0; n < 4; n++)
-        if (n < NL) {
-          bsum[n] += dv[u][n];
-#pragma unroll
-          for (int j = 0; j < 8; j++) acc[n][j] += dv[u][n] * (float)v[u][j];
-        }
-  }
-#pragma unroll
-  for (int n = 0; n < 4; n++) {
-#pragma unroll
-    for (int j = 0; j < 8; j++) red[rg][n][8 * cg + j] = acc[n][j];
-    if (cg == 0) red[rg][n][256] = bsum[n];
-  }
-  __syncthreads();
-  float* rec = a.slab[p] + (long)blockIdx.x * a.rec;  // one-layer record: [NL][256] then [NL]
-  for (int e = tid; e < NL * 257; e += 256) {
-    const int n = e / 257, k = e - n * 257;
-    float t = 0.f;
-#pragma unroll
-    for (int g8 = 0; g8 < 8; g8++) t += red[g8][n][k];  // fixed order
-    if (k < 256) rec[(long)n * 256 + k] = t; else rec[(long)NL * 256 + n] = t;
   }
 }
 
@@ -1970,12 +2002,16 @@ int mlp_big_fwd(int nprob, const float* const* x, int ldx, const float* const* p
                 const long* yout, const long* woff, const long* boff, hipStream_t st, const MlpXGather* gather, const int* gmap) {
   MlpBigFwdArgs a{};
   int maxM = 0;
+  bool any_xb = false;
   for (int p = 0; p < nprob; p++) {
     if (mlp_set_gather(a, p, gmap ? gmap[p] : p, gather, dims[0]) != TACORL_OK) return TACORL_EINVAL;
     if ((!a.nseg[p] && ((uintptr_t)x[p] & 15)) || ((uintptr_t)params[p] & 15) || ((uintptr_t)params_bf16[p] & 7) || ((uintptr_t)act[p] & 15)) return TACORL_EINVAL;
     a.x[p] = x[p]; a.params[p] = params[p]; a.pbf[p] = (const __bf16*)params_bf16[p]; a.act[p] = act[p]; a.M[p] = M[p];
     for (int l = 0; l < L; l++) { a.ybf[p][l] = ybf[p * MF_MAXL + l]; a.sbf[p][l] = sbf[p * MF_MAXL + l]; }
     a.yout[p] = yout[p];
+    a.xb[p] = gather ? (__bf16*)gather->xb[gmap ? gmap[p] : p] : nullptr;
+    if ((uintptr_t)a.xb[p] & 15) return TACORL_EINVAL;
+    any_xb = any_xb || a.xb[p];
     maxM = M[p] > maxM ? M[p] : maxM;
   }
   for (int l = 0; l < L; l++) {
@@ -1984,6 +2020,7 @@ int mlp_big_fwd(int nprob, const float* const* x, int ldx, const float* const* p
   }
   a.dims[L] = dims[L]; a.L = L; a.ldx = ldx;
   if (maxM == 0) return TACORL_OK;
+  if (any_xb && mlp_rows_huge(maxM)) return TACORL_EINVAL;  // (the persistent kernel does not write the bf16 rows)
   constexpr size_t lds = (size_t)2 * 128 * XP * 2, lds_mid = (size_t)2 * 32 * XP * 2;
   static int once = (hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_big_fwd_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
@@ -2078,11 +2115,15 @@ static int mlp_big_rps(int nprob, const int* M, int L) {
   const int sps = (stages + nslice - 1) / nslice;
   return (sps < 4 ? 4 : sps) * BG_R;
 }
-static int mlp_out_rpw(int nprob, const int* M) {
+// The output layer's column sums (mlp_wgrad_out_body) of a call: a bandwidth pass at tens of thousands of rows - OUT_RPW rows per
+// workgroup, a launch of its own (mlp_wgrad_out_kernel) - and a latency matter at a few thousand - 64 rows per workgroup, as
+// one more plane of mlp_wgrad_big_kernel's launch.  Both choices follow from this one predicate.
+static bool mlp_out_bandwidth_bound(int nprob, const int* M) {
   int maxM = 0;
   for (int p = 0; p < nprob; p++) maxM = M[p] > maxM ? M[p] : maxM;
-  return mlp_rows_huge(maxM) ? OUT_RPW : 64;
+  return mlp_rows_huge(maxM);
 }
+static int mlp_out_rpw(int nprob, const int* M) { return mlp_out_bandwidth_bound(nprob, M) ? OUT_RPW : 64; }
 static long mlp_big_out_rec(int L, const int* dims) { return ((long)dims[L] * 257 + 3) & ~3L; }
 size_t mlp_big_wgrad_slab_floats(int nprob, const int* M, int L, const int* dims) {
   const long rec = mlp_wgrad_record(L, dims, nullptr), orec = mlp_big_out_rec(L, dims);
@@ -2094,11 +2135,11 @@ size_t mlp_big_wgrad_slab_floats(int nprob, const int* M, int L, const int* dims
 }
 size_t mlp_big_xb_bytes(int M) { return (size_t)((M + 63) & ~63) * 128 * 2; }
 // ybf[p*MF_MAXL + l]: float offset in act[p] of layer l's bf16 output copy (l < L-1); dz[p] + dzoff[p*MF_MAXL + l]: bf16 dZ_l;
-// xb[p]: scratch of mlp_big_xb_bytes(M[p]) bytes for layer 0's input
+// xb[p]: scratch of mlp_big_xb_bytes(M[p]) bytes for layer 0's input (xb_current: already written by the forward, x is not read)
 int mlp_fused_wgrad_big(int nprob, const float* const* x, int ldx, const float* const* act, const float* const* d_out, int ldo,
                         const float* const* dz, float* const* grads, float* slab, void* const* xb, const int* M, int L,
                         const int* dims, const long* ybf, const long* dzoff, const long* woff, const long* boff, int accumulate,
-                        hipStream_t st, size_t slab_floats) {
+                        hipStream_t st, size_t slab_floats, bool xb_current) {
   MlpWgBigArgs a{};
   MlpXbArgs xa{};
   MlpWgOutArgs oa{};
@@ -2146,14 +2187,29 @@ int mlp_fused_wgrad_big(int nprob, const float* const* x, int ldx, const float* 
     n2++;
   }
   constexpr int lds = BG_S * BG_STAGE;
+  static_assert(lds >= (int)sizeof(float) * 8 * 4 * (256 + 1) && 64 * BG_NW >= OUT_NT, "the output layer's plane: its LDS and threads");
   static int once = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_wgrad_big_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess ? 0 : -1;
   if (once) return -1;
   const int xblocks = (int)(((long)maxMp * 16 + 255) / 256);
-  hipLaunchKernelGGL(mlp_x_to_bf16_kernel, dim3(xblocks > 4096 ? 4096 : xblocks, n2), dim3(256), 0, st, xa);
-  hipLaunchKernelGGL(mlp_wgrad_big_kernel, dim3(maxs, a.tile0[L - 1], n2), dim3(64 * BG_NW), lds, st, a);
-  hipLaunchKernelGGL(mlp_wgrad_out_kernel, dim3(maxso, n2), dim3(256), 0, st, oa);
-  if (launch_reduce(r, 256, L - 1, n2, st) || launch_reduce(ro, 8, 1, n2, st)) return -1;
+  // (xb_current: the forward has written these very images - MlpBigFwdArgs.xb)
+  if (!xb_current) hipLaunchKernelGGL(mlp_x_to_bf16_kernel, dim3(xblocks > 4096 ? 4096 : xblocks, n2), dim3(256), 0, st, xa);
+  // the MFMA planes and - at a few thousand rows - the output layer's column sums as plane tile0[L - 1] (blocks past their
+  // own slice count return); at tens of thousands of rows the column sums are their own launch (see mlp_wgrad_out_body)
+  const bool out_plane = !mlp_out_bandwidth_bound(nprob, M);
+  hipLaunchKernelGGL(mlp_wgrad_big_kernel, dim3(out_plane && maxso > maxs ? maxso : maxs, a.tile0[L - 1] + (out_plane ? 1 : 0), n2),
+                     dim3(64 * BG_NW), lds, st, a, oa);
+  if (!out_plane) hipLaunchKernelGGL(mlp_wgrad_out_kernel, dim3(maxso, n2), dim3(OUT_NT), 0, st, oa);
+  if (red_batch_open()) {  // the step-wide reduce batch takes both records
+    if (launch_reduce(r, 256, L - 1, n2, st) || launch_reduce(ro, 8, 1, n2, st)) return -1;
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+  }
+  // both records' reduces as ONE launch of two jobs (the same sums in the same slice order as two mlp_wgrad_reduce_kernel launches)
+  MlpWgReduceMulti m{};
+  m.job[0] = r; m.gx[0] = 256; m.L[0] = L - 1; m.first[1] = n2;
+  m.job[1] = ro; m.gx[1] = 8; m.L[1] = 1; m.first[2] = 2 * n2;
+  m.njob = 2;
+  hipLaunchKernelGGL(mlp_wgrad_reduce_multi_kernel, dim3(256, L - 1, 2 * n2), dim3(256), 0, st, m);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

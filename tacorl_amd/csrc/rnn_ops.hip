@@ -26,12 +26,12 @@ constexpr int RB_K = 128;
 constexpr int ROW_BYTES = RB_K * 2;  // 256 B per staged row (16 chunks of 16 B)
 
 struct RnnArgs {
-  const __bf16* x;
+  const __bf16* x;        // NULL: a zero operand - no main K tile is issued or multiplied (see rnn_gemm_kernel)
   const __bf16* w;
   const float* bias;
   const float* addend;
   const float* mask_src;  // optional [M][N]: result kept where mask_src > 0 (ReLU derivative in BPTT)
-  float* y;
+  float* y;               // NULL: no fp32 store (forward batches only: the caller reads the bf16 copy alone)
   __bf16* yb;
   int M, K, N, ld_add, act;
   // optional twin rows: M2 more rows of the same problem (same W, bias, act) whose activations live in other buffers -
@@ -90,7 +90,12 @@ __global__ __launch_bounds__(64 * NW) void rnn_gemm_kernel(RnnBatch ab, int MT, 
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, g = lane >> 4;
   const int m0 = mt * RB_M, n0 = ntile * RB_N;
-  const int nkm = a.K / RB_K, nk = nkm + (a.x_ext ? 1 : 0), mtot = a.M + a.M2;
+  // x == NULL (problems without twin rows, rnn_fwd_batch): the operand is all zeros - a stacked RNN's first step, h_{-1} = 0.
+  // Its K tiles are neither fetched nor multiplied.  Same bits as multiplying a zero buffer: the accumulators start at +0 and
+  // +0 + (+-0) * w = +0 for every finite w, so they are still +0 when the extension tile and the epilogue follow.  With no
+  // extension either (nk == 0) nothing is issued, the K loop with its wait and barrier does not run, and the epilogue is
+  // act(bias + addend).
+  const int nkm = a.x ? a.K / RB_K : 0, nk = nkm + (a.x_ext ? 1 : 0), mtot = a.M + a.M2;
   const long ldx = a.ldx ? a.ldx : a.K, ldy = a.ldy ? a.ldy : a.N;
 
   auto issue = [&](int kt, int slot) {
@@ -174,7 +179,7 @@ __global__ __launch_bounds__(64 * NW) void rnn_gemm_kernel(RnnBatch ab, int MT, 
         for (int r = 0; r < 4; r++) z[r] = ms[r] > 0.f ? z[r] : 0.f;
       }
       const long ldo = twin ? (long)a.N : ldy;
-      *reinterpret_cast<f32x4*>(y + (long)m * ldo + n) = z;
+      if (y) *reinterpret_cast<f32x4*>(y + (long)m * ldo + n) = z;
       if (yb) *reinterpret_cast<bf16x4*>(yb + (long)m * ldo + n) = bf16x4{(__bf16)z[0], (__bf16)z[1], (__bf16)z[2], (__bf16)z[3]};
     }
   }
@@ -605,6 +610,9 @@ static int rnn_fwd_batch(int nprob, const void* const* x_bf16, const void* const
     void* yb = y_bf16 ? y_bf16[p] : nullptr;
     if (((uintptr_t)x_bf16[p] | (uintptr_t)w_bf16[p] | (uintptr_t)y[p] | (uintptr_t)bi | (uintptr_t)ad) & 15) return TACORL_EINVAL;
     if ((uintptr_t)yb & 7) return TACORL_EINVAL;
+    // x[p] == NULL: a zero operand - only for a problem without twin rows (the kernel would read x2 at the skipped tiles' place);
+    // y[p] == NULL: no fp32 copy - then the bf16 one must exist
+    if (!w_bf16[p] || (!x_bf16[p] && M2 > 0 && x2_bf16[p]) || (!y[p] && !yb)) return TACORL_EINVAL;
     ab.p[p] = RnnArgs{(const __bf16*)x_bf16[p], (const __bf16*)w_bf16[p], bi, ad, nullptr, y[p], (__bf16*)yb, M, K, N, ld_add, acts[p]};
     if (x_ext && x_ext[p]) {  // K extension of this problem
       if (!w_ext || !w_ext[p] || (((uintptr_t)x_ext[p] | (uintptr_t)w_ext[p] | (uintptr_t)(bias2 ? bias2[p] : nullptr)) & 15)) return TACORL_EINVAL;

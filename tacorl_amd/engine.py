@@ -702,12 +702,28 @@ class ACEngine:
             seg = lambda k, mod, a_t: self._emb_segs(*self._OBS_SRC[k], mod) + [(a_t, 0, A, E, 0)]  # noqa: E731
             segs = [seg("q1", B, self.acts_main), seg("q2", B, self.acts_main), seg("q1", 0, self.act_pi), seg("q2", 0, self.act_pi),
                     seg("tq1", 0, self.act_next), seg("tq2", 0, self.act_next)]
+            # (the q1 / q2 rows also as the bf16 operand of their weight gradients, where the backward site keeps one -
+            # thousands of rows -: the forward holds those chunks in registers, the conversion was a launch of the critic backward)
+            xb = self._q_xb()
+            self._q_xb_current = all(x is not None for x in xb)
             ops.mlp_fwd_gather(segs, [self.XQ["q1"], self.XQ["q2"], None, None, None, None], self.ldq, ps, pb, ac,
-                               [self.R, self.R, B, B, B, B], qd, qa, lean=self._lean("q"))
+                               [self.R, self.R, B, B, B, B], qd, qa, lean=self._lean("q"),
+                               xb_out=xb + [None] * 4 if self._q_xb_current else None)
         else:
+            self._q_xb_current = False
             self._assemble_q_rows()
             xs = [self.XQ["q1"], self.XQ["q2"], self.XQpi["q1"], self.XQpi["q2"], self.XT["tq1"], self.XT["tq2"]]
             ops.mlp_fwd(xs, self.ldq, ps, ac, [self.R, self.R, B, B, B, B], qd, qa, self.compute, params_bf16=pb, lean=self._lean("q"))
+
+    def _q_xb(self):
+        """Where the q1 / q2 problems' bf16 input rows lie in the Q backward site's workspace ([None] where it keeps none);
+        looked up again only when a buffer has been (re)allocated."""
+        key = (ops.alloc_epoch(), self.R)
+        if getattr(self, "_q_xb_cache", (None,))[0] != key:
+            ok = self._lean("q") and self.R < 16384
+            xb = ops.mlp_bwd_fused_xb([self.R, self.R], self.q1.head_dims, "mlp_bwdf_q", self.dev) if ok else [None]
+            self._q_xb_cache = ((ops.alloc_epoch(), self.R), xb)  # (the lookup itself may allocate the workspace)
+        return self._q_xb_cache[1]
 
     def _assemble_q_rows(self):
         """XQ / XQpi / XT = [S | action] for the forwards that do not gather (one launch)."""
@@ -728,7 +744,7 @@ class ACEngine:
         self._mlp_backward("q", [self.XQ["q1"], self.XQ["q2"]], self.ldq, [self.q1.head(), self.q2.head()],
                            [self.qact["q1"], self.qact["q2"]], [self.dq["q1"], self.dq["q2"]], 1,
                            [self.q1.head(self.q1.grad), self.q2.head(self.q2.grad)], [self.dXQ["q1"], self.dXQ["q2"]],
-                           self.ldq, [self.R, self.R], qd, qa)
+                           self.ldq, [self.R, self.R], qd, qa, xb_current=self._q_xb_current)
         self._state_grads_from_q()
 
     def _state_grads_from_q(self):
@@ -736,6 +752,7 @@ class ACEngine:
         call("tacorl_reduce_rows_mod_batch", 2, ops.ptr_array([self.dXQ["q1"], self.dXQ["q2"]]), self.ldq,
              ops.ptr_array([self.dS["q1"], self.dS["q2"]]), self.lds, B, self.E, 3 * n + 1, ops.stream())
 
+    _q_xb_current = False  # set by _q_forward: it has written the Q weight gradients' bf16 input rows (_q_xb)
     lean_mlp_acts = True  # hidden-layer outputs of the fused MLPs are recomputed by the weight-gradient launch, not saved
 
     def _lean(self, tag):
@@ -752,8 +769,9 @@ class ACEngine:
             cache[tag] = ops.mlp_lean_ok(n, dims, ldx, ldo, ldd, self.compute) and ops.mlp_bwd_fused_ok(n, dims, ldo, ldd, self.compute)
         return cache[tag]
 
-    def _mlp_backward(self, tag, *sites):
-        ops.mlp_backward(("mlp_bwd_" + tag, "mlp_bwdf_" + tag), *sites, self.compute, prepacked=self._prepacked, lean=self._lean(tag))
+    def _mlp_backward(self, tag, *sites, **kw):
+        ops.mlp_backward(("mlp_bwd_" + tag, "mlp_bwdf_" + tag), *sites, self.compute, prepacked=self._prepacked, lean=self._lean(tag),
+                         **kw)
 
     def _actor_backward(self, bc_phase, head_cur, q1p, q2p, gs):
         B, A, Ac, nz = self.B, self.A, self.Ac, self.noise

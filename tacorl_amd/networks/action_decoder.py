@@ -412,14 +412,18 @@ class ActionDecoderLogistic:
             ops.copy_cols(module.f_out[c], 0, 32, module._ad_in, 32 * j, module._ad_in.shape[1], B * T, 32)
         return module._ad_in, module._ad_in.shape[1]
 
-    def forward(self, plan, emb, ld_emb, B, T, Tm, compute, frozen=False, mirrors_current=False, twin=None, rows_current=False):
+    def forward(self, plan, emb, ld_emb, B, T, Tm, compute, frozen=False, mirrors_current=False, twin=None, rows_current=False,
+                bf16_state_only=False):
         """plan (B,P); emb [B*T][ld_emb] batch-major frame embeddings; uses steps t < Tm.  Fills self.heads.
         rows_current=True (frozen ring route only, see ring_rows): xb_seq already holds this plan's and these frames' rows.
         frozen=True: the caller never steps these weights with the library's optimiser kernels, so the bf16
         copies of the weight matrices are refreshed only when the block's torch version counter moved
         (load_state_dict / copy_).
         twin: a twin_state() whose layer-0 projection has been issued (twin_input_proj) - its recurrent steps and heads
-        are computed as extra rows of this pass's launches (twin_ok() must hold); fills twin.heads."""
+        are computed as extra rows of this pass's launches (twin_ok() must hold); fills twin.heads.
+        bf16_state_only=True (frozen ring-GEMM path without a twin; ignored elsewhere): the recurrent steps write only the bf16
+        hidden state - the next step's and the heads' operand - and leave self.h as it was (2 MB per layer and step at the
+        headline shapes).  Only backward() reads self.h: never set this for a pass that a backward follows."""
         self._ensure(B, Tm)
         blk, H, R = self.blk, self.hidden, B * Tm
         x, K = self.x_seq, self.P + self.E
@@ -458,6 +462,7 @@ class ActionDecoderLogistic:
                 self._lin(x, K, blk.p("rnn.weight_ih_l0"), blk.p("rnn.bias_ih_l0"), self.xin[0], R, K, H, ACT_NONE, compute)
             L = self.L
             assert twin is None or (proj_fused and twin.shape == (B, Tm)), "twin pass: twin_ok() / twin_state(B, Tm)"
+            no_h = bf16_state_only and frozen and twin is None
             hbp = lambda l, t, o=self: C.c_void_p(o.hb[l].data_ptr() + 2 * t * B * H)  # noqa: E731
             xbp = lambda t, o=self: C.c_void_p(o.xb_seq.data_ptr() + 2 * t * B * 128)  # noqa: E731
             for s_ in range(Tm + 2 * (L - 1)):
@@ -468,9 +473,12 @@ class ActionDecoderLogistic:
                     t = s_ - 2 * l
                     if 0 <= t < Tm:  # h_l[t] = relu(W_hh h_l[t-1] + b_hh + xin_l[t])
                         ext = ring and l == 0  # ... with xin_0[t] = W_ih x_t + b_ih as one more K tile of this problem
-                        xs.append(ptr(self.h0b) if t == 0 else hbp(l, t - 1)); wt.append(ptr(self.whb[l]))
+                        # (t == 0: h_{-1} = 0 - a NULL operand, whose K tiles the ring GEMM skips; twin launches pass the zero
+                        # buffer: a problem with twin rows takes no NULL)
+                        h_prev = hbp(l, t - 1) if t else (None if twin is None else ptr(self.h0b))
+                        xs.append(h_prev); wt.append(ptr(self.whb[l]))
                         bs.append(blk.p(f"rnn.bias_hh_l{l}")); ad.append(None if ext else at(self.xin[l], t * B * H))
-                        ys.append(at(self.h[l], t * B * H)); yb.append(hbp(l, t)); ac.append(ACT_RELU)
+                        ys.append(None if no_h else at(self.h[l], t * B * H)); yb.append(hbp(l, t)); ac.append(ACT_RELU)
                         xe.append(xbp(t) if ext else None); we.append(ptr(self.wih0_b) if ext else None)
                         b2.append(blk.p("rnn.bias_ih_l0") if ext else None)
                         if twin is not None:
@@ -562,8 +570,9 @@ class ActionDecoderLogistic:
         emb, ld = emb if emb is not None else self.module_emb(module, B, T)
         # (mirrors_current / prepared: the caller has issued refresh_mirrors() / prepare_backward() for the current weights;
         # rows_current: its plan-sampling launch has written xb_seq - ring_rows)
+        # (the logging-only pass: no backward follows, nobody reads the fp32 hidden state)
         self.forward(plan, emb, ld, B, T, T - 1, module.compute, frozen=frozen and not optimize, mirrors_current=mirrors_current,
-                     rows_current=rows_current)
+                     rows_current=rows_current, bf16_state_only=not optimize)
         slot = ops._at(module.engine.logs, LOG_SLOTS.index("action_loss"))
         self.loss(acts, slot, B, T, T - 1, want_grad=optimize, grad_scale=1.0 / module.world_size, lazy=True)
         if optimize:

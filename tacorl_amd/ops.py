@@ -162,18 +162,21 @@ def mlp_fwd_gather_ok(M, dims, acts, ldx, compute, lean):
         len(M), int_array(M), len(dims) - 1, int_array(dims), int_array(acts), ldx, int(lean)))
 
 
-def mlp_fwd_gather(segs, x_out, ldx, params, params_bf16, acts_buf, M, dims, acts, lean=False):
+def mlp_fwd_gather(segs, x_out, ldx, params, params_bf16, acts_buf, M, dims, acts, lean=False, xb_out=None):
     """The fused forward with gathered layer-0 inputs.  segs[p] = [(tensor, float offset, ld, first column, row modulo)],
-    <= 4 per problem, in column order; x_out[p]: tensor that also receives the assembled fp32 rows, or None."""
+    <= 4 per problem, in column order; x_out[p]: tensor that also receives the assembled fp32 rows, or None.
+    xb_out[p]: address (mlp_bwd_fused_xb) that also receives the rows as the weight gradients' bf16 operand, or None."""
     n = len(segs)
     sp, sl, sc, sm = [0] * (4 * n), [0] * (4 * n), [0] * (4 * n), [0] * (4 * n)
     for p, ss in enumerate(segs):
         assert 1 <= len(ss) <= 4
         for t, (ten, off, ld, c0, mod) in enumerate(ss):
             sp[4 * p + t], sl[4 * p + t], sc[4 * p + t], sm[4 * p + t] = ten.data_ptr() + 4 * off, ld, c0, mod
-    call("tacorl_mlp_fwd_fused_gather", n, int_array([len(ss) for ss in segs]), (C.c_void_p * (4 * n))(*[v or None for v in sp]),
-         int_array(sl), int_array(sc), int_array(sm), ptr_array(x_out), ldx, ptr_array(params), ptr_array(params_bf16),
-         ptr_array(acts_buf), int_array(M), len(dims) - 1, int_array(dims), int_array(acts), int(lean), stream())
+    xb = () if xb_out is None else (ptr_array(xb_out),)
+    call("tacorl_mlp_fwd_fused_gather" + ("_xb" if xb else ""), n, int_array([len(ss) for ss in segs]),
+         (C.c_void_p * (4 * n))(*[v or None for v in sp]), int_array(sl), int_array(sc), int_array(sm), ptr_array(x_out), *xb, ldx,
+         ptr_array(params), ptr_array(params_bf16), ptr_array(acts_buf), int_array(M), len(dims) - 1, int_array(dims),
+         int_array(acts), int(lean), stream())
 
 
 def mlp_bwd(xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, compute=F32, accumulate=False,
@@ -198,6 +201,16 @@ def mlp_bwd_fused_pack(params, M, dims, ws_tag, device):
          ws.numel(), stream())
 
 
+def mlp_bwd_fused_xb(M, dims, ws_tag, device):
+    """Per problem of the backward site (M, dims, ws_tag): the address inside its workspace where mlp_bwd_fused_wgrad reads
+    layer 0's bf16 input rows - what mlp_fwd_gather(xb_out=...) may write for it (then: xb_current=True) -, or None for a
+    problem that has no such region."""
+    n, Ma, da = len(M), int_array(M), int_array(dims)
+    ws = workspace(L.lib().tacorl_mlp_bwd_fused_ws_bytes(n, Ma, len(dims) - 1, da), device, ws_tag)
+    offs = [L.lib().tacorl_mlp_bwd_fused_xb_offset(n, Ma, len(dims) - 1, da, p) for p in range(n)]
+    return [None if o < 0 else ws.data_ptr() + o for o in offs]
+
+
 def mlp_bwd_fused_dgrad(params, acts_buf, d_outs, ldo, d_xs, ldd, M, dims, acts, ws_tag, prepacked=False, lean=False):
     """Input-gradient chain of the whole MLP in one launch; leaves every layer's dZ in workspace(ws_tag)
     for mlp_bwd_fused_wgrad (same ws_tag, same shapes, same `lean` as the forward and the weight gradients: at
@@ -209,27 +222,30 @@ def mlp_bwd_fused_dgrad(params, acts_buf, d_outs, ldo, d_xs, ldd, M, dims, acts,
          int_array(dims), int_array(acts), int(bool(prepacked)) | (2 if lean else 0), ptr(ws), ws.numel(), stream())
 
 
-def mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, ws_tag, accumulate=False, lean=False):
+def mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, ws_tag, accumulate=False, lean=False,
+                        xb_current=False):
+    """xb_current: the site's forward has written the many-row problems' bf16 input rows (mlp_bwd_fused_xb)."""
     nb = L.lib().tacorl_mlp_bwd_fused_ws_bytes(len(xs), int_array(M), len(dims) - 1, int_array(dims))
     ws = workspace(nb, acts_buf[0].device, ws_tag)
     call("tacorl_mlp_bwd_fused_wgrad", len(xs), ptr_array(xs), ldx, ptr_array(acts_buf), ptr_array(d_outs), ldo,
-         ptr_array(grads), int_array(M), len(dims) - 1, int_array(dims), int_array(acts), int(accumulate), int(lean), ptr(ws),
-         ws.numel(), stream())
+         ptr_array(grads), int_array(M), len(dims) - 1, int_array(dims), int_array(acts), int(accumulate),
+         int(bool(lean)) | (2 if xb_current else 0), ptr(ws), ws.numel(), stream())
 
 
 def mlp_backward(tags, xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, compute, prepacked=False,
-                 lean=False):
+                 lean=False, xb_current=False):
     """MLP backward.  bf16 mode: the input-gradient chain as ONE launch, the weight gradients as one launch in line
     behind it (on side streams of their own - only Adam needs them - a third set of concurrent launches beside the
     action-decoder branch's chip-wide GEMMs cost the chain more than their kernels' time: 0.8801 -> 0.8682 ms in line,
     round 3).  Otherwise: the per-layer path.  tags = (per-layer, fused) scratch buffer names; prepacked / lean: see
-    mlp_bwd_fused_pack / mlp_lean_ok."""
+    mlp_bwd_fused_pack / mlp_lean_ok; xb_current: see mlp_bwd_fused_wgrad."""
     if not mlp_bwd_fused_ok(len(xs), dims, ldo, ldd, compute):
+        assert not xb_current
         mlp_bwd(xs, ldx, params, acts_buf, d_outs, ldo, grads, d_xs, ldd, M, dims, acts, compute, ws_tag=tags[0])
         return
     mlp_bwd_fused_dgrad(params, acts_buf, d_outs, ldo, d_xs, ldd, M, dims, acts, tags[1], prepacked=prepacked, lean=lean)
     if any(g is not None for g in grads):
-        mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, tags[1], lean=lean)
+        mlp_bwd_fused_wgrad(xs, ldx, acts_buf, d_outs, ldo, grads, M, dims, acts, tags[1], lean=lean, xb_current=xb_current)
 
 
 # --------------------------------------------------------------------- data movement
