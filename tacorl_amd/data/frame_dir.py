@@ -114,14 +114,7 @@ class FrameDirectory:
         names = sorted(names) if names is not None else frame_files(self.root)
         if not names:
             raise FileNotFoundError(f"{self.root}: no .npz frame file")
-        stem = names[0][:-4]  # (the reference takes whichever file scandir names first: every frame file shares the pattern)
-        digits = re.findall(r"\d+", stem)
-        if not digits:
-            raise ValueError(f"{os.path.join(self.root, names[0])}: no step number in the file name")
-        self.prefix = re.split(r"\d+", stem)[0]
-        self.n_digits = int(n_digits) if n_digits is not None else len(digits[0])
-        if self.n_digits < 1:
-            raise ValueError(f"n_digits {self.n_digits} < 1")
+        self.prefix, self.n_digits = name_pattern(self.root, names[0], n_digits)
         self.n_files = len(names)
         ep = self.ep_steps
         if (ep[:, 0] > ep[:, 1]).any() or (ep[1:, 0] <= ep[:-1, 1]).any() or ep.min() < 0:
@@ -256,6 +249,40 @@ class FrameDirectory:
 def frame_files(root):
     """The names of the directory's .npz files, sorted."""
     return sorted(e.name for e in os.scandir(root) if e.name.endswith(".npz"))
+
+
+def name_pattern(root, name, n_digits=None):
+    """(prefix, digits) of the directory's frame-file names, read off one of them - the reference takes whichever file scandir
+    names first: every frame file shares the pattern."""
+    stem = name[:-4]
+    digits = re.findall(r"\d+", stem)
+    if not digits:
+        raise ValueError(f"{os.path.join(root, name)}: no step number in the file name")
+    nd = int(n_digits) if n_digits is not None else len(digits[0])
+    if nd < 1:
+        raise ValueError(f"n_digits {nd} < 1")
+    return re.split(r"\d+", stem)[0], nd
+
+
+def step_files(root, n_digits=None):
+    """The directory's frame files by step number alone - no episode table - for readers that name single steps (the rollout
+    callback's start and goal states): step -> path, by the file-name rule FrameDirectory.file_of applies."""
+    root = os.path.expanduser(str(root))
+    if not os.path.isdir(root):
+        raise FileNotFoundError(f"{root} is not a directory")
+    names = frame_files(root)
+    if not names:
+        raise FileNotFoundError(f"{root}: no .npz frame file")
+    prefix, nd = name_pattern(root, names[0], n_digits)
+    have = set(names)
+
+    def file_of(step):
+        name = f"{prefix}{int(step):0{nd}d}.npz"
+        if name not in have:
+            raise FileNotFoundError(f"{os.path.join(root, name)}: step {int(step)} has no frame file")
+        return os.path.join(root, name)
+
+    return file_of
 
 
 def _copy_chunk(dst, src, non_blocking):

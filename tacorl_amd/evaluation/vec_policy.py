@@ -21,6 +21,13 @@ the yardstick of tests/test_vec_policy_cpu.py (as modules/cem.py's cem_restateme
 `RelayPolicy` / `relay_policy_restatement` below are the same for RelayImitationLearning (rollout_manager.py:434-557): the same
 clock, a latent sub-goal from the high-level policy in place of the plan, the low-level policy in place of the decoder, no
 recurrent state.  `rollout_episodes` drives either policy.
+
+`RLPolicy` / `rl_policy_restatement` are the flat baseline (rollout_manager.py:81-180 RLRollout): one deterministic
+`actor.get_actions` per row per step, refined by CEMOptimizer under use_cem; no clock and no state.
+
+Every `step` takes `embeddings=` in place of images: what evaluation/frame_ingest.py FrameIngest makes of the environments' raw
+uint8 frames - per network the observation embeddings {camera: (R,32)} of this step and the per-row cache of goal embeddings.
+With embeddings=None a step runs exactly as it did without the argument.
 """
 import numpy as np
 import torch
@@ -69,6 +76,35 @@ def _take(x, idx):
     return x.index_select(0, idx)
 
 
+def _cat_rows(d, cams, idx=None):
+    """The {camera: (R,32)} embeddings of `cams` side by side, as state_from_observation concatenates them; rows idx of it."""
+    x = d[cams[0]] if len(cams) == 1 else torch.cat([d[c] for c in cams], dim=-1)
+    return x if idx is None else x.index_select(0, idx)
+
+
+def _obs_goal_rows(owner, net, emb, name, cams, goal_cams, idx=None):
+    """[enc(obs) | goal_encoder(enc(goal))] of network `name` out of a step's embeddings: the second half of
+    ActorSurface / CriticSurface.emb_representation (modules/inference.py), the same launch on the same rows."""
+    from .. import ops
+
+    e_obs = _cat_rows(emb.obs[name], cams, idx)
+    if not goal_cams:
+        return e_obs
+    e_goal = _cat_rows(emb.goal[name], goal_cams, idx).contiguous()
+    n = e_obs.shape[0]
+    lay = ops.mlp_act_layout(n, net.genc_dims, net.genc_acts)
+    gact = torch.zeros(lay[2], device=owner.dev)
+    ops.mlp_fwd([e_goal], e_goal.shape[1], [net.genc()], [gact], [n], net.genc_dims, net.genc_acts, owner.compute)
+    yo = lay[1][-1]
+    return torch.cat([e_obs, gact[yo: yo + n * net.G].view(n, net.G)], dim=-1)
+
+
+def _critic_rows(module, emb, idx=None):
+    """What CEMOptimizer maximises over, out of a step's embeddings: q1's own [enc(obs) | goal_encoder(enc(goal))]."""
+    cs = module.q1.__dict__["critic_surface"]
+    return _obs_goal_rows(module, cs.net, emb, "q1", cs.cams, cs.goal_cams, idx)
+
+
 class LatentPlanPolicy:
     def __init__(self, module, n_envs, plan_duration=16, use_cem=False, cem_kwargs=None):
         self.module, self.R = module, int(n_envs)
@@ -103,7 +139,22 @@ class LatentPlanPolicy:
         return self.state.hidden
 
     # ------------------------------------------------------------------ plan source
-    def _source(self, observation, goal, idx, eps):
+    def _source_embedded(self, emb, idx, eps, cem_eps=None):
+        """_source on a step's embeddings (FrameIngest) in place of images."""
+        m = self.module
+        if self.actor is not None:
+            surf = m.__dict__["_actor_surface"]
+            o = _obs_goal_rows(m, surf.net, emb, "actor", surf.cams, surf.goal_cams, idx)
+            plan, _ = self.actor.get_actions(o, deterministic=True, reparameterize=False)
+            if self.cem is not None:
+                plan = self.cem.get_action(obs=_critic_rows(m, emb, idx), initial_mean=plan,
+                                           noise=None if cem_eps is None else {"eps": cem_eps})
+            return plan
+        state = _cat_rows(emb.obs["lmp"], m.plan_proposal_obs_modalities, idx)
+        pp_goal = m.goal_encoder(_cat_rows(emb.goal["lmp"], m.plan_proposal_goal_modalities, idx))
+        return m.plan_proposal.get_dist(state_emb=state, goal_emb=pp_goal).sample(noise=eps)
+
+    def _source(self, observation, goal, idx, eps, cem_eps=None):
         """The plan of rows idx: (len(idx), P)."""
         m = self.module
         obs, g = _take(observation, idx), _take(goal, idx)
@@ -111,7 +162,7 @@ class LatentPlanPolicy:
             o = {"observation": obs, "goal": g} if self.image else torch.cat([obs, g], dim=-1)
             plan, _ = self.actor.get_actions(o, deterministic=True, reparameterize=False)
             if self.cem is not None:
-                plan = self.cem.get_action(obs=o, initial_mean=plan)
+                plan = self.cem.get_action(obs=o, initial_mean=plan, noise=None if cem_eps is None else {"eps": cem_eps})
             return plan
         if self.image:
             pe = m.perceptual_encoder
@@ -121,14 +172,19 @@ class LatentPlanPolicy:
             state, pp_goal = obs, g
         return m.plan_proposal.get_dist(state_emb=state, goal_emb=pp_goal).sample(noise=eps)
 
-    def step(self, observation, goal, noise=None, plans=None):
+    def step(self, observation, goal, noise=None, plans=None, embeddings=None):
         """observation / goal: {camera: (R,3,H,W)} fp32 dicts (image modules) or (R,S) / (R,G) tensors (D4RL).  noise: any
-        subset of {"plan_eps": (R,P), "rand_a": (R,Da,K), "rand_b": (R,Da)}; the rest is drawn on the device.  plans: (R,P)
-        with NaN rows meaning "not given" - overrides the plan source for the rows that re-plan (an external planner).
+        subset of {"plan_eps": (R,P), "rand_a": (R,Da,K), "rand_b": (R,Da), "cem_eps": (R,iters,N,P)}; the rest is drawn on the
+        device.  plans: (R,P) with NaN rows meaning "not given" - overrides the plan source for the rows that re-plan (an
+        external planner).  embeddings: a FrameIngest step's result, in place of observation / goal (image modules; both may then be None).
         Returns the (R, A) actions: a view that stays valid until the next step."""
         R, dev, noise = self.R, self.dev, noise or {}
-        to = lambda x: ({k: to(v) for k, v in x.items()} if isinstance(x, dict) else torch.as_tensor(x).to(dev, torch.float32))  # noqa: E731
-        observation, goal = to(observation), to(goal)
+        if embeddings is not None:
+            if not self.image:
+                raise ValueError("embeddings= stands in for images: this module takes vector observations")
+        else:
+            to = lambda x: ({k: to(v) for k, v in x.items()} if isinstance(x, dict) else torch.as_tensor(x).to(dev, torch.float32))  # noqa: E731
+            observation, goal = to(observation), to(goal)
         due = self.clock.due()
         if due:
             need = due
@@ -141,7 +197,13 @@ class LatentPlanPolicy:
                 nidx = idx if need == due else torch.tensor(need, dtype=torch.long, device=dev)
                 eps = noise.get("plan_eps")
                 eps = None if eps is None else eps.to(dev, torch.float32).reshape(R, -1).index_select(0, nidx)
-                src = self._source(observation, goal, nidx, eps).to(torch.float32).reshape(len(need), -1)
+                ce = noise.get("cem_eps")
+                ce = None if ce is None else ce.to(dev, torch.float32).index_select(0, nidx)
+                if embeddings is not None:
+                    src = self._source_embedded(embeddings, nidx, eps, ce)
+                else:
+                    src = self._source(observation, goal, nidx, eps, ce)
+                src = src.to(torch.float32).reshape(len(need), -1)
                 new = src if need == due else torch.zeros(R, self.ad.P, device=dev).index_copy_(0, nidx, src).index_select(0, idx)
             if plans is not None:
                 given_rows = plans.to(dev, torch.float32).reshape(R, -1).index_select(0, idx)
@@ -150,7 +212,9 @@ class LatentPlanPolicy:
                 else:
                     new = torch.where(torch.isnan(given_rows).any(dim=1, keepdim=True), new, given_rows)
             self.plan.index_copy_(0, idx, new)
-        if self.image:
+        if embeddings is not None:
+            emb = _cat_rows(embeddings.obs["lmp"], self.module.action_decoder_modalities)
+        elif self.image:
             emb = self.module.perceptual_encoder.get_state_from_observation(
                 observation=observation, modalities=self.module.action_decoder_modalities)
         else:
@@ -176,35 +240,60 @@ def default_batch_obs(raw, envs):
             torch.as_tensor(np.stack([np.asarray(g, dtype=np.float32) for g in goals])))
 
 
-def rollout_episodes(policy, envs, max_steps=None, batch_obs=None, noise=None):
+def rollout_episodes(policy, envs, max_steps=None, batch_obs=None, noise=None, reset_infos=None, ingest=None, actions_out=None):
     """One episode per environment, all at once: envs is a list of policy.R gym-API objects (`reset()`, `step(a)` ->
     (obs, reward, done, info), `_max_episode_steps`).  One `.cpu()` of the (R, A) actions per step; finished rows idle (their
     last observation is fed again, their actions are dropped).  batch_obs(list of raw observations, envs) -> (observation,
-    goal) for policy.step; noise: None or a callable step -> the step's noise dict.  Returns the reference's rollout_info
-    dicts (`episode_length`, `episode_return`, `success`), one per environment."""
+    goal) for policy.step; noise: None or a callable step -> the step's noise dict.
+    reset_infos: None or one dict per environment, passed as `env.reset(**reset_info)` (rollout_manager.py:111, :216).
+    ingest: None or a FrameIngest of R rows, used in place of batch_obs: the raw uint8 frames become the step's
+    `embeddings=`; its goal cache is dropped with the policy's reset.  actions_out: None or a list that receives, per
+    environment, the list of the actions it was stepped with.
+    Returns the reference's rollout_info dicts (`episode_length`, `episode_return`, `success`, and `successful_tasks` where
+    the environment's last info reports it, :177-178), one per environment."""
     R = len(envs)
     if R != policy.R:
         raise ValueError(f"{R} environments for a policy of {policy.R} rows")
+    if reset_infos is not None and len(reset_infos) != R:
+        raise ValueError(f"{len(reset_infos)} reset_infos for {R} environments")
+    if ingest is not None and ingest.R != R:
+        raise ValueError(f"{R} environments for an ingest of {ingest.R} rows")
     batch_obs = batch_obs or default_batch_obs
-    raw = [env.reset() for env in envs]
+    raw = [env.reset(**(reset_infos[r] if reset_infos is not None else {})) for r, env in enumerate(envs)]
     policy.reset()
+    if ingest is not None:
+        ingest.reset()
     limit = [env._max_episode_steps if max_steps is None else min(max_steps, env._max_episode_steps) for env in envs]
     steps, returns, info = [0] * R, [0] * R, [{} for _ in range(R)]
     live = [limit[r] > 0 for r in range(R)]
+    if actions_out is not None:
+        actions_out[:] = [[] for _ in range(R)]
     t = 0
     while any(live):
-        observation, goal = batch_obs(raw, envs)
-        actions = policy.step(observation, goal, noise=noise(t) if noise is not None else None).cpu().numpy()
+        step_noise = noise(t) if noise is not None else None
+        if ingest is not None:
+            actions = policy.step(None, None, noise=step_noise, embeddings=ingest.step(raw))
+        else:
+            observation, goal = batch_obs(raw, envs)
+            actions = policy.step(observation, goal, noise=step_noise)
+        actions = actions.cpu().numpy()
         for r in range(R):
             if not live[r]:
                 continue
+            if actions_out is not None:
+                actions_out[r].append(actions[r].copy())
             raw[r], reward, done, info[r] = envs[r].step(actions[r])
             returns[r] += reward
             steps[r] += 1
             live[r] = not (done or steps[r] >= limit[r])
         t += 1
-    return [{"episode_length": steps[r], "episode_return": returns[r],
-             "success": ("success" in info[r]) and info[r]["success"]} for r in range(R)]
+    out = []
+    for r in range(R):
+        d = {"episode_length": steps[r], "episode_return": returns[r], "success": ("success" in info[r]) and info[r]["success"]}
+        if "successful_tasks" in info[r]:
+            d["successful_tasks"] = info[r]["successful_tasks"]
+        out.append(d)
+    return out
 
 
 def latent_plan_policy_restatement(plan_fn, decoder_fn, observations, goals, n_envs, plan_duration, hidden0, resets=None,
@@ -353,10 +442,12 @@ class RelayPolicy:
         obs_emb, goal_emb = to(obs_emb), to(goal_emb)
         return self._advance(obs_emb, lambda nidx: _take(goal_emb, nidx), subgoals)
 
-    def step(self, observation, goal, noise=None, subgoals=None):
+    def step(self, observation, goal, noise=None, subgoals=None, embeddings=None):
         """observation / goal: {camera: (R,3,H,W)} fp32 dicts.  Every camera of the union is encoded once for all R rows; the
         goal images of the rows that are due only.  noise is accepted for rollout_episodes and unused (the actions are
-        deterministic)."""
+        deterministic).  embeddings: a FrameIngest step's result in place of the two image dicts."""
+        if embeddings is not None:
+            return self._advance(embeddings.obs["ril"], lambda nidx: _take(embeddings.goal["ril"], nidx), subgoals)
         to = lambda d: {c: torch.as_tensor(d[c]).to(self.dev, torch.float32) for c in self.cams}  # noqa: E731
         observation, goal = to(observation), to(goal)
         pe = self.module.perceptual_encoder
@@ -395,4 +486,80 @@ def relay_policy_restatement(high_fn, low_fn, obs_embs, goal_embs, n_envs, plan_
         clock.tick(set(due))
         out["replanned"].append(due)
         out["subgoal"].append(sub.clone())
+    return out
+
+
+# ------------------------------------------------------------------------------------------ the flat baseline
+class RLPolicy:
+    """The RLRollout manager's inner loop (reference evaluation/rollout_manager.py:121-141) for R environments in one step:
+
+        policy = RLPolicy(module, n_envs=R, use_cem=False)
+        policy.reset(rows=None)                                  # nothing to forget: the policy has no state
+        actions = policy.step(observation, goal)                 # (R, A) fp32 on the device
+
+    `actor.get_actions(obs, deterministic=True, reparameterize=False)` on every row, every step - tanh(mean), and with a
+    discrete gripper the arg-max class, as ActorSurface.get_actions states it - and with use_cem
+    `CEMOptimizer.get_action(obs, initial_mean=that action)` over all R rows in its one launch, discrete_gripper taken from the
+    actor as the manager does (:101-106).  Image modules (CQL_Offline) take {camera: (R,3,H,W)} dicts or `embeddings=`, vector
+    modules (the D4RL CQL) (R,S) / (R,G) tensors."""
+
+    def __init__(self, module, n_envs, use_cem=False, cem_kwargs=None):
+        actor = getattr(module, "actor", None)
+        if getattr(actor, "get_actions", None) is None:
+            raise ValueError("the module has no actor.get_actions")
+        if int(n_envs) < 1:
+            raise ValueError(f"n_envs {n_envs}")
+        self.module, self.R, self.dev, self.actor = module, int(n_envs), module.dev, actor
+        self.image = hasattr(getattr(module, "__dict__", {}).get("_actor_surface"), "cams")
+        self.A = int(actor.action_dim)
+        self.cem = None
+        if use_cem:
+            from ..modules.cem import CEMOptimizer
+
+            self.cem = CEMOptimizer(q1=module.q1, q2=module.q2, action_dim=self.A,
+                                    discrete_gripper=bool(actor.discrete_gripper), **(cem_kwargs or {}))
+
+    def reset(self, rows=None):
+        _row_list(rows, self.R)
+
+    def step(self, observation, goal=None, noise=None, embeddings=None):
+        """noise: None or {"cem_eps": (R, iters, N, A)} - the CEM draws; the actor's action is deterministic."""
+        dev, noise = self.dev, noise or {}
+        if embeddings is not None:
+            if not self.image:
+                raise ValueError("embeddings= stands in for images: this module takes vector observations")
+            surf = self.module.__dict__["_actor_surface"]
+            o = _obs_goal_rows(self.module, surf.net, embeddings, "actor", surf.cams, surf.goal_cams)
+            o_cem = _critic_rows(self.module, embeddings) if self.cem is not None else None
+        else:
+            to = lambda x: ({k: to(v) for k, v in x.items()} if isinstance(x, dict) else torch.as_tensor(x).to(dev, torch.float32))  # noqa: E731
+            observation = to(observation)
+            if goal is None:
+                o = observation
+            elif self.image:
+                o = {"observation": observation, "goal": to(goal)}
+            else:
+                o = torch.cat([observation, to(goal)], dim=-1)
+            o_cem = o
+        actions, _ = self.actor.get_actions(o, deterministic=True, reparameterize=False)
+        if self.cem is not None:
+            eps = noise.get("cem_eps")
+            actions = self.cem.get_action(obs=o_cem, initial_mean=actions, noise=None if eps is None else {"eps": eps})
+        return actions
+
+
+def rl_policy_restatement(actor_fn, observations, goals, n_envs, cem_fn=None):
+    """RLPolicy's schedule in plain torch ops, over callables standing in for the networks (any device, any dtype).
+      actor_fn(observation (R,..), goal (R,..) or None, t) -> (R, A): the deterministic action of every row;
+      cem_fn(observation, goal, initial_mean (R,A), t) -> (R, A): the refinement (None: use_cem off);
+      observations[t], goals[t] (or goals None): the step's inputs.
+    Returns dict(actions [T x (R,A)], initial_mean [T x (R,A)])."""
+    out = dict(actions=[], initial_mean=[])
+    for t in range(len(observations)):
+        obs, goal = observations[t], (goals[t] if goals is not None else None)
+        a = actor_fn(obs, goal, t)
+        if a.shape[0] != n_envs:
+            raise ValueError(f"{a.shape[0]} action rows for {n_envs} environments")
+        out["initial_mean"].append(a)
+        out["actions"].append(cem_fn(obs, goal, a, t) if cem_fn is not None else a)
     return out

@@ -256,6 +256,7 @@ class MiniTrainer:
         self.optimizers = []
         self.logged_metrics = {}
         self.model = None
+        self.datamodule = None  # what fit(datamodule=...) was given (PL's trainer.datamodule: callbacks read it)
 
     def _log(self, name, value, **kw):
         self.logged_metrics[name] = value
@@ -291,6 +292,7 @@ class MiniTrainer:
 
     def fit(self, model, train_dataloaders=None, val_dataloaders=None, datamodule=None, ckpt_path=None):
         self._attach(model)
+        self.datamodule = datamodule
         if datamodule is not None:
             train_dataloaders = datamodule.train_dataloader()
             val_dataloaders = datamodule.val_dataloader() if hasattr(datamodule, "val_dataloader") else None
