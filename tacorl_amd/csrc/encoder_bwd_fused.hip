@@ -28,9 +28,6 @@
 
 namespace {
 
-#ifndef EBW_ROLL_IMG
-#define EBW_ROLL_IMG 0  // 1: conv1 weight gradient with its k-steps as a loop - 210 -> 111 registers at 84 x 84 (it then fits beside a ring-GEMM workgroup) but 24.3 -> 27.7 us and the step +9 us (round 5, same-box A/B)
-#endif
 constexpr int NT = 512;  // 8 waves: 2 per SIMD
 constexpr int NW = NT / 64;
 
@@ -280,7 +277,10 @@ __global__ __launch_bounds__(NT) void ebw_wgrad_tr_kernel(WgArgs a) {
     };
     // (fully unrolled the k-steps hoist their pixel -> address arithmetic: at 7 steps - conv2 of a 128 x 128 camera, 196
     // output pixels - beside 48 staging registers that was 256 registers + 54 spilled ones reloaded per image; round 5)
-    if constexpr (G::KS > 4 && (!IMG || EBW_ROLL_IMG || G::KS > 16)) {  // (conv1 of 150 x 200 in 3 bands: 19 k-steps - unrolled they spill 74 registers)
+    // The conv1 weight gradient (IMG) of up to 16 k-steps stays unrolled: as a loop it takes 111 registers instead of 210
+    // at 84 x 84 (it then fits beside a ring-GEMM workgroup) but ran 24.3 -> 27.7 us and the step +9 us (round 5, same-box
+    // A/B of a compile-time switch that commit 071142c was the last to carry).
+    if constexpr (G::KS > 4 && (!IMG || G::KS > 16)) {  // (conv1 of 150 x 200 in 3 bands: 19 k-steps - unrolled they spill 74 registers)
 #pragma unroll 1
       for (int s = 0; s < G::KS; s++) kstep(s);
     } else {
@@ -614,15 +614,6 @@ struct L3Args {
 // every wave doing both (round 3's first version) the 72 fragment + 80 accumulator registers left nothing to read ahead
 // with: dgrad3 ran as 54 x (ds_read, wait, MFMA), 38 us per launch; roles keep the two register sets in different waves
 // and let the two phases of an image overlap on the MFMA pipe.  All waves share the soft-argmax and the staging.
-#ifdef L3_STAMPS  // scratch builds: shader / wall clocks of workgroup 0 per phase, summed over its images
-__device__ unsigned long long l3_st[16];
-extern "C" int tacorl_l3_stamps_read(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(l3_st), sizeof(l3_st)) == hipSuccess ? 0 : -1;
-}
-#define L3_ST(i) do { if (tid == 64 * w && blockIdx.x == 0 && (w == 0 || w == ND3)) { const unsigned long long t_ = clock64(); st[i] += t_ - tl; tl = t_; } } while (0)
-#else
-#define L3_ST(i) do { } while (0)
-#endif
 constexpr int NT3 = 512, NW3 = NT3 / 64, ND3 = 4;
 struct L3Tile { static constexpr int MGRP = 1, NGRP = 4, KGRP = 1; };  // wgrad3's wave tiling here (TrTile: 2 x 4 over 8 waves)
 template <class L>
@@ -754,15 +745,10 @@ __global__ __launch_bounds__(NT3) void ebw_l3_kernel(L3Args a) {
       for (int j = 0; j < 8; j++) ones[j] = (__bf16)1.0f;
     }
     float dt = 0.f;
-#ifdef L3_STAMPS
-    unsigned long long st[6] = {0, 0, 0, 0, 0, 0}, tl = clock64();
-    const unsigned long long w0 = wall_clock64(), c0 = tl;
-#endif
     __syncthreads();  // zero fill done
     if (j0 < n_img) { fetch(j0); fetch3(j0); put(y2s); }
     __syncthreads();
     int kb = 0;
-    L3_ST(0);  // prologue
     for (int img = j0; img < n_img; img += a.wpp, kb ^= 1) {
       const int nxt = img + a.wpp;
       int wl = w;  // opaque copy: the pixel coordinates derived from it are scalar arithmetic per image; hoisted out of the
@@ -816,10 +802,8 @@ __global__ __launch_bounds__(NT3) void ebw_l3_kernel(L3Args a) {
           dzh[((iy + L::HA) * L::C + (i - iy * L::OW) + L::HB) * L::PP + lane] = (__bf16)(v[k] != 0.f ? ds * it : 0.f);  // ReLU mask: y3 > 0 <=> y3 / t != 0
         }
       }
-      L3_ST(1);  // soft-argmax
       if (img != j0) flush(img - a.wpp, z2s + (kb ^ 1) * G::Z2E);
       __syncthreads();  // dZ3 of this image complete
-      L3_ST(2);  // flush + barrier
       if constexpr (ROLE == 0) {
         // ---- dgrad3: dZ2 = (dZ3 (*) W3^T) masked by y2 > 0; TG3 pixel tiles share every fragment step
         __bf16* zw = z2s + kb * G::Z2E;
@@ -901,10 +885,8 @@ __global__ __launch_bounds__(NT3) void ebw_l3_kernel(L3Args a) {
           }
         }
       }
-      L3_ST(3);  // role phase
       if (nxt < n_img) put(y2s + (kb ^ 1) * G::Y2E);
       __syncthreads();  // dZ3 / y2 of this image consumed, the next y2 staged
-      L3_ST(4);  // put + barrier
     }
     if (j0 < n_img) flush(j0 + ((n_img - 1 - j0) / a.wpp) * a.wpp, z2s + (kb ^ 1) * G::Z2E);  // the last image's dZ2 (its buffer: kb flipped once more)
     if constexpr (ROLE == 1) {
@@ -932,14 +914,6 @@ __global__ __launch_bounds__(NT3) void ebw_l3_kernel(L3Args a) {
       for (int ww = 0; ww < NW3; ww++) sum += shd[ww];
       a.dtp[p][j0] = sum;
     }
-#ifdef L3_STAMPS
-    L3_ST(5);  // epilogue
-    if (tid == 64 * w && blockIdx.x == 0 && (w == 0 || w == ND3)) {
-      const int o = w == 0 ? 0 : 8;
-      for (int i = 0; i < 6; i++) l3_st[o + i] = st[i];
-      l3_st[o + 6] = clock64() - c0; l3_st[o + 7] = wall_clock64() - w0;
-    }
-#endif
   };
   if (w < ND3) run(std::integral_constant<int, 0>{});
   else run(std::integral_constant<int, 1>{});

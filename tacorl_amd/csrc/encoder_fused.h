@@ -95,38 +95,22 @@ __device__ __forceinline__ u32x2 pack4_bf16(float a, float b, float c, float d) 
   return __builtin_bit_cast(u32x2, t);
 }
 
-#ifndef EF_VAR
-#define EF_VAR 0   // scratch timing builds only (see encoder_fused.hip)
-#endif
 // MFMA with the weight fragment held in AGPRs (the conv2/conv3 weights fill 136 AGPRs; as plain
 // builtin operands hipcc keeps them in arch VGPRs, runs out, and serialises every LDS read behind one
 // shared destination register).  Inline asm is invisible to hipcc's hazard recogniser, so the chain
 // brackets itself: s_nop before the first MFMA (VALU-written accumulator) and after the last one
 // (MFMA result read by VALU) - cdna_hip_programming.md section 5.7.
-#if EF_VAR & 2
-#define MFMA_AW(acc, wfrag, bfrag) asm volatile("" : "+v"(acc) : "a"(wfrag), "v"(bfrag))
-#else
 #define MFMA_AW(acc, wfrag, bfrag) \
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(wfrag), "v"(bfrag))
-#endif
 #define MFMA_CHAIN_BEGIN(acc) asm volatile("s_nop 1" : "+v"(acc))
 // First MFMA of a chain: the bias registers are its C operand and the accumulator only its destination - no four
 // v_mov per chain to seed the accumulator (22 chains per image), and no VALU-write -> MFMA-read wait either: the
 // bias registers were written once, before the image loop.
-#if EF_VAR & 2
-#define MFMA_FIRST_AW(acc, wfrag, bfrag, bias) asm volatile("" : "=v"(acc) : "a"(wfrag), "v"(bfrag), "v"(bias))
-#else
 #define MFMA_FIRST_AW(acc, wfrag, bfrag, bias) \
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %3" : "=v"(acc) : "a"(wfrag), "v"(bfrag), "v"(bias))
-#endif
 // (12 wait states: what an 8-pass XDL result needs before a non-MFMA reader, cdna_hip_programming.md section 5.7 item 2;
 // v_mfma_f32_16x16x32_bf16 issues every ~17 clk in a dependent chain, i.e. is a 4-pass op - 20 states were used before)
 #define MFMA_CHAIN_END(acc) asm volatile("s_nop 11" : "+v"(acc))
-#if EF_VAR & 2
-#define EF_MFMA_TXT(...) ""
-#else
-#define EF_MFMA_TXT(...) __VA_ARGS__
-#endif
 
 // encoder_ring.hip
 int ef_ring_supported(int H, int W);

@@ -26,18 +26,13 @@
 #include "encoder_fused.h"
 #include "enc_bwd_fused.h"
 
-#ifndef EF_DEFER
-#define EF_DEFER 1      // 0: every pixel in the per-image tiles, as rounds 1-5 (A/B builds)
-#endif
 #define EF_DCHUNK 8     // images per leftover-pixel tile (8 of its 16 MFMA columns; 16 would not fit the LDS)
-#ifndef EF_SETUP_COST
 #define EF_SETUP_COST 128 // launch balance: the prologue of a workgroup's second problem (248 weight registers per lane from L2, first image), in 1/64 image: measured ~2 images (a 27-image workgroup that crosses: 256 k clk against 238 k)
-#endif
-#ifndef EF_ACT_COST
-#define EF_ACT_COST 72  // cost of an image whose activations are also stored, in 1/64 of a plain image: 10.7 k vs 9.5 k clk (per-workgroup clocks, -DEF_BLKCLK)
-                        // (49 KB of stores through a ~14 B/clk per-CU store path; per-workgroup clocks of a -DEF_BLKCLK build,
+#define EF_ACT_COST 72  // cost of an image whose activations are also stored, in 1/64 of a plain image: 10.7 k vs 9.5 k clk (per-workgroup clocks)
+                        // (49 KB of stores through a ~14 B/clk per-CU store path; per-workgroup clocks read by
                         // scratch/run_fused.py: critical workgroup 335 k clk at 64, 313 k at 72, 292 k at 80, 295 k at 84; mean 279 k)
-#endif
+// (The clocks cited in this file - per workgroup from entry to exit, per phase of one wave - and the timing-only variants
+// behind its "scratch builds" figures were compile-time switches of this source; commit 071142c is the last that has them.)
 
 
 // ------------------------------------------------------------------ weight packing
@@ -92,43 +87,43 @@ extern "C" int tacorl_encoder_pack_weights(int nprob, const float* const* params
 // `s_nop 0` between two adjacent asm statements and a counted s_waitcnt in front of each one whose fragment is the
 // youngest LDS read: per 16x16x32 MFMA that was 1.3 scalar instructions, each a 4-5 clk issue slot at one wave per SIMD.
 #define MFMA6_FIRST(acc, bias, w, o, f) \
-  asm volatile(EF_MFMA_TXT("v_mfma_f32_16x16x32_bf16 %0, %1, %7, %13\n\t" \
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %7, %13\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %2, %8, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %3, %9, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %4, %10, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %5, %11, %0\n\t" \
-      "v_mfma_f32_16x16x32_bf16 %0, %6, %12, %0\n\t") \
+      "v_mfma_f32_16x16x32_bf16 %0, %6, %12, %0\n\t" \
       : "=&v"(acc) : "a"((w)[(o) + 0]), "a"((w)[(o) + 1]), "a"((w)[(o) + 2]), "a"((w)[(o) + 3]), "a"((w)[(o) + 4]), "a"((w)[(o) + 5]), "v"((f)[0]), "v"((f)[1]), "v"((f)[2]), "v"((f)[3]), "v"((f)[4]), "v"((f)[5]), "v"(bias))
 #define MFMA6_MORE(acc, w, o, f) \
-  asm volatile(EF_MFMA_TXT("v_mfma_f32_16x16x32_bf16 %0, %1, %7, %0\n\t" \
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %7, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %2, %8, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %3, %9, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %4, %10, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %5, %11, %0\n\t" \
-      "v_mfma_f32_16x16x32_bf16 %0, %6, %12, %0\n\t") \
+      "v_mfma_f32_16x16x32_bf16 %0, %6, %12, %0\n\t" \
       : "+v"(acc) : "a"((w)[(o) + 0]), "a"((w)[(o) + 1]), "a"((w)[(o) + 2]), "a"((w)[(o) + 3]), "a"((w)[(o) + 4]), "a"((w)[(o) + 5]), "v"((f)[0]), "v"((f)[1]), "v"((f)[2]), "v"((f)[3]), "v"((f)[4]), "v"((f)[5]))
 #define MFMA8_FIRST(acc, bias, w, o, f) \
-  asm volatile(EF_MFMA_TXT("v_mfma_f32_16x16x32_bf16 %0, %1, %9, %17\n\t" \
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %9, %17\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %2, %10, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %3, %11, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %4, %12, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %5, %13, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %6, %14, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %7, %15, %0\n\t" \
-      "v_mfma_f32_16x16x32_bf16 %0, %8, %16, %0\n\t") \
+      "v_mfma_f32_16x16x32_bf16 %0, %8, %16, %0\n\t" \
       : "=&v"(acc) : "a"((w)[(o) + 0]), "a"((w)[(o) + 1]), "a"((w)[(o) + 2]), "a"((w)[(o) + 3]), "a"((w)[(o) + 4]), "a"((w)[(o) + 5]), "a"((w)[(o) + 6]), "a"((w)[(o) + 7]), "v"((f)[0]), "v"((f)[1]), "v"((f)[2]), "v"((f)[3]), "v"((f)[4]), "v"((f)[5]), "v"((f)[6]), "v"((f)[7]), "v"(bias))
 #define MFMA8_MORE(acc, w, o, f) \
-  asm volatile(EF_MFMA_TXT("v_mfma_f32_16x16x32_bf16 %0, %1, %9, %0\n\t" \
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %9, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %2, %10, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %3, %11, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %4, %12, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %5, %13, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %6, %14, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %7, %15, %0\n\t" \
-      "v_mfma_f32_16x16x32_bf16 %0, %8, %16, %0\n\t") \
+      "v_mfma_f32_16x16x32_bf16 %0, %8, %16, %0\n\t" \
       : "+v"(acc) : "a"((w)[(o) + 0]), "a"((w)[(o) + 1]), "a"((w)[(o) + 2]), "a"((w)[(o) + 3]), "a"((w)[(o) + 4]), "a"((w)[(o) + 5]), "a"((w)[(o) + 6]), "a"((w)[(o) + 7]), "v"((f)[0]), "v"((f)[1]), "v"((f)[2]), "v"((f)[3]), "v"((f)[4]), "v"((f)[5]), "v"((f)[6]), "v"((f)[7]))
 #define MFMA9_FIRST(acc, bias, w, o, f) \
-  asm volatile(EF_MFMA_TXT("v_mfma_f32_16x16x32_bf16 %0, %1, %10, %19\n\t" \
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %10, %19\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %2, %11, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %3, %12, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %4, %13, %0\n\t" \
@@ -136,10 +131,10 @@ extern "C" int tacorl_encoder_pack_weights(int nprob, const float* const* params
       "v_mfma_f32_16x16x32_bf16 %0, %6, %15, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %7, %16, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %8, %17, %0\n\t" \
-      "v_mfma_f32_16x16x32_bf16 %0, %9, %18, %0\n\t") \
+      "v_mfma_f32_16x16x32_bf16 %0, %9, %18, %0\n\t" \
       : "=&v"(acc) : "a"((w)[(o) + 0]), "a"((w)[(o) + 1]), "a"((w)[(o) + 2]), "a"((w)[(o) + 3]), "a"((w)[(o) + 4]), "a"((w)[(o) + 5]), "a"((w)[(o) + 6]), "a"((w)[(o) + 7]), "a"((w)[(o) + 8]), "v"((f)[0]), "v"((f)[1]), "v"((f)[2]), "v"((f)[3]), "v"((f)[4]), "v"((f)[5]), "v"((f)[6]), "v"((f)[7]), "v"((f)[8]), "v"(bias))
 #define MFMA9_MORE(acc, w, o, f) \
-  asm volatile(EF_MFMA_TXT("v_mfma_f32_16x16x32_bf16 %0, %1, %10, %0\n\t" \
+  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %10, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %2, %11, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %3, %12, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %4, %13, %0\n\t" \
@@ -147,7 +142,7 @@ extern "C" int tacorl_encoder_pack_weights(int nprob, const float* const* params
       "v_mfma_f32_16x16x32_bf16 %0, %6, %15, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %7, %16, %0\n\t" \
       "v_mfma_f32_16x16x32_bf16 %0, %8, %17, %0\n\t" \
-      "v_mfma_f32_16x16x32_bf16 %0, %9, %18, %0\n\t") \
+      "v_mfma_f32_16x16x32_bf16 %0, %9, %18, %0\n\t" \
       : "+v"(acc) : "a"((w)[(o) + 0]), "a"((w)[(o) + 1]), "a"((w)[(o) + 2]), "a"((w)[(o) + 3]), "a"((w)[(o) + 4]), "a"((w)[(o) + 5]), "a"((w)[(o) + 6]), "a"((w)[(o) + 7]), "a"((w)[(o) + 8]), "v"((f)[0]), "v"((f)[1]), "v"((f)[2]), "v"((f)[3]), "v"((f)[4]), "v"((f)[5]), "v"((f)[6]), "v"((f)[7]), "v"((f)[8]))
 
 // ------------------------------------------------------------------------- kernel
@@ -186,7 +181,7 @@ struct EFGeom {
   // over the leftover pixels of those images (image = MFMA column), whose result is merged into the soft-argmax state.
   // PS lives in the FC tail's h1 buffer (dead until the tail, which follows the merge).
   static constexpr int D1S = 16 * 64 + 16, D2S = 9 * 128 + 16;   // per-image pitches: 16-byte slots r16 apart -> conflict-free ds_read_b128
-  static constexpr bool DEFER = EF_DEFER != 0 && NPX2 % 16 == 1 && NPX3 % 16 == 1 && NPX2 > 16 && NPX3 > 16 &&
+  static constexpr bool DEFER = NPX2 % 16 == 1 && NPX3 % 16 == 1 && NPX2 > 16 && NPX3 > 16 &&
                                 2 * ((IMG_BYTES + 15) & ~15) + ACT1_BYTES + ACT2_BYTES + EF_CHUNK * (272 + 528) +
                                         EF_DCHUNK * (D1S + D2S) <= 160 * 1024;
   static constexpr int DEFER_BYTES = DEFER ? EF_DCHUNK * (D1S + D2S) : 0;
@@ -205,50 +200,6 @@ struct EFGeom {
                              LDS_BYTES <= 160 * 1024 && OH3 >= 1 && OW3 >= 1;
 };
 
-// Phase timing for kernel work (scratch builds with -DEF_STAMPS only; the product build has no trace of it):
-// wave 0 of block 0 accumulates shader-clock deltas per phase, read back with tacorl_ef_stamps_read.
-#ifndef EF_VAR
-#define EF_VAR 0
-#endif
-#ifndef EF_X   // scratch experiments (timing only, wrong results): 1 = no image DMA inside the loop, 2 = conv1 does not store its
-#define EF_X 0 // activations, 4 = every fetch re-reads one L2-resident image, 8 = no per-image barriers, 16 = no soft-argmax arithmetic
-#endif
-#if EF_X & 8
-#define EF_IMG_BARRIER() do { } while (0)
-#else
-#define EF_IMG_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
-#if defined(EF_STAMPS) || defined(EF_BLKCLK)  // scratch builds: per-workgroup shader clocks from entry to exit
-__device__ unsigned long long ef_blk[512];    // [0, 256) clocks, [256, 512) images served
-extern "C" int tacorl_ef_blk_read(unsigned long long* out) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(ef_blk), sizeof(ef_blk)) == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
-}
-#endif
-#ifdef EF_STAMPS
-__device__ unsigned long long ef_stamps[64];
-#ifndef EF_STAMP_WAVE
-#define EF_STAMP_WAVE 0
-#endif
-#define STAMP(k)                                                    \
-  do {                                                              \
-    if (blockIdx.x == 0 && threadIdx.x == 64 * EF_STAMP_WAVE) {     \
-      const unsigned long long t_ = clock64();                      \
-      atomicAdd(&ef_stamps[k], t_ - t_prev);                        \
-      t_prev = t_;                                                  \
-    }                                                               \
-  } while (0)
-extern "C" int tacorl_ef_stamps_read(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ef_stamps), sizeof(ef_stamps)) != hipSuccess) return TACORL_ELAUNCH;
-  if (reset) {
-    unsigned long long z[64] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(ef_stamps), z, sizeof(z)) != hipSuccess) return TACORL_ELAUNCH;
-  }
-  return TACORL_OK;
-}
-#else
-#define STAMP(k)
-#endif
-
 template <int H_, int W_>
 __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
   typedef EFGeom<H_, W_> G;
@@ -259,7 +210,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
   // Round 6 - launch balance by WORK UNITS, not by whole workgroups per problem.  The launch lasts as long as its slowest
   // workgroup; with a workgroup bound to one problem (rounds 2-5: ceil(images / workgroups) per problem, bisected budget)
   // the image counts per workgroup came out 24 .. 29 at the bench shapes and the critical workgroup ran 7 % over the mean
-  // (per-workgroup shader clocks, -DEF_BLKCLK: 257 k against 240 k).  Now the problems' images lie on ONE line of work
+  // (per-workgroup shader clocks: 257 k against 240 k).  Now the problems' images lie on ONE line of work
   // units (an image = its problem's cost; EF_SETUP_COST dead units in front of every problem but the first stand for the
   // weight reload of a workgroup that crosses into it), workgroup b owns the units [b U / n, (b + 1) U / n) and serves the
   // images that START inside them - a contiguous run of images of one problem, or the tail of one problem and the head of
@@ -267,13 +218,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
   // in the results (images are independent; FC chunks and leftover-pixel groups are per-column).
   const unsigned long u_lo = (unsigned long)blockIdx.x * (unsigned long)a_.utotal / gridDim.x;
   const unsigned long u_hi = (unsigned long)(blockIdx.x + 1) * (unsigned long)a_.utotal / gridDim.x;
-#if defined(EF_STAMPS) || defined(EF_BLKCLK)
-  const unsigned long long t_entry = clock64();
-  int n_served = 0;
-#endif
-#ifdef EF_STAMPS
-  unsigned long long t_prev = t_entry;
-#endif
 #pragma unroll 1
   for (int pi = 0; pi < a_.nprob; pi++) {
   const long seg_s = a_.p[pi].ustart, seg_e = seg_s + (long)a_.p[pi].n_img * a_.p[pi].cost;
@@ -348,11 +292,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
   // round trip exposed at the top of every image (round 2's kernel had four such waits in its loop).
   asm volatile("" ::"v"(bias1a), "v"(bias1b), "v"(bias2a), "v"(bias2b), "v"(bias3), "v"(temp));
 
-#if EF_VAR & 1
-  u32x4 kconst;  // scratch builds: a benign fragment (bf16 1/128 everywhere) instead of every LDS fragment read
-  asm volatile("v_mov_b32 %0, 0x3c003c00" : "=v"(kconst[0]));
-  kconst[1] = kconst[2] = kconst[3] = kconst[0];
-#endif
   // conv1 k offsets (bytes): lane group g reads image row 4 (s / 3) + g, 8-element group s % 3 of the 24-run
   const int k1g = g * a.W * 6;
 
@@ -559,7 +498,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
   // bias registers above; the weights load straight into AGPRs and would otherwise be waited for inside the loop
   __builtin_amdgcn_s_waitcnt(0x0F70);
   __syncthreads();
-  STAMP(0);  // prologue: weights to registers, first image
 
   while (true) {
     const int slot = it & (EF_CHUNK - 1);
@@ -575,17 +513,10 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       // The next image (band) streams in beside this one's conv1.  Whole-image geometries spread their ~11 pieces per
       // wave over the conv1 tiles (two per tile, below): issued in one burst the pieces queue behind one another in the
       // CU's memory pipeline and the issuing wave stands still for ~100 clk per piece (1 000 clk per image).
-#if !(EF_X & 1)
       if (band + 1 < G::NB) dma_load(cur, band + 1, buf ^ 1);
       else if (has_next && !G::WHOLE) dma_load(nxt, 0, buf ^ 1);
-#endif
-#if EF_X & 4  // scratch: every fetch re-reads the workgroup's FIRST image (L2-resident): the DMA without its HBM traffic
-      if (G::WHOLE) lean_begin(worker, buf ^ 1);
-#else
       if (G::WHOLE) lean_begin(has_next ? nxt : cur, buf ^ 1);  // (the workgroup's last image fetches itself again: no branch per piece)
       if (fp) fp_begin(has_next ? nxt : cur, buf ^ 1);          // (fp32 source: the same rule - the groups never branch on has_next)
-#endif
-      STAMP(1);  // DMA issue
       const unsigned char* ib = lds + buf * a.lds_img;
       constexpr int NT1 = (G::NPXB + 15) >> 4, PER1 = (NT1 + 3) >> 2;
       const int npxb = G::WHOLE ? npx1 : min(G::BR, a.OH1 - band * G::BR) * a.OW1;  // output pixels of this band
@@ -611,24 +542,16 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
 #pragma unroll
         for (int s = 0; s < 6; s++) {
           const int off = (s / 3) * 4 * G::W * 6 + (s % 3) * 16;  // compile-time immediate
-#if EF_VAR & 1
-          bf[s] = kconst; (void)base;
-#else
           const u32x2 lo = *reinterpret_cast<const u32x2*>(base + off);
           const u32x2 hi = *reinterpret_cast<const u32x2*>(base + off + 8);
           bf[s] = u32x4{lo[0], lo[1], hi[0], hi[1]};
-#endif
         }
       };
       auto ld1one = [&](const unsigned char* base, int s) -> u32x4 {
         const int off = (s / 3) * 4 * G::W * 6 + (s % 3) * 16;  // compile-time immediate
-#if EF_VAR & 1
-        (void)base; return kconst;
-#else
         const u32x2 lo = *reinterpret_cast<const u32x2*>(base + off);
         const u32x2 hi = *reinterpret_cast<const u32x2*>(base + off + 8);
         return u32x4{lo[0], lo[1], hi[0], hi[1]};
-#endif
       };
       // Per-wave tiles i = 0 .. PER1 - 1 (tile w + 4 i); tile i lives in fragment set i & 1.  A tile is two chains over
       // the same six fragments; the second chain refills them in place with the fragments of tile i + 2 (two 8-byte
@@ -655,11 +578,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
           const f32x4 r1 = {relu1(acc1[0]), relu1(acc1[1]), relu1(acc1[2]), relu1(acc1[3])};
           const u32x2 lo = pack4_bf16(r0[0], r0[1], r0[2], r0[3]), hi = pack4_bf16(r1[0], r1[1], r1[2], r1[3]);
           const u32x4 pk = {lo[0], lo[1], hi[0], hi[1]};
-#if !(EF_X & 2)
           *reinterpret_cast<u32x4*>(act1 + oyi * G::PITCH1 + ox * ACT1_STRIDE + (8 * g) * 2) = pk;  // channels 8 g .. 8 g + 7
-#else
-          asm volatile("" :: "v"(pk));
-#endif
           // saved for the backward as bf16 - the very value the next layer consumes (ReLU mask of the dgrad, im2col operand
           // of the wgrad) - at the start of y1's fp32-sized slot: one 16-byte store, half the bytes of the fp32 copy
           if (P.act)
@@ -668,12 +587,10 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       };
       u32x4 fa[6], fb[6];
       auto dma_of_tile = [&](int i) {
-#if !(EF_X & 1)
         if (G::WHOLE && !fp) {
 #pragma unroll
           for (int q = 0; q < DPT; q++) lean_piece(i * DPT + q);
         }
-#endif
       };
       // the two chains of tile i; prev >= 0: that tile's epilogue rides in the first chain
       auto chains1 = [&](int i, u32x4 (&bf)[6], int prev) {
@@ -684,7 +601,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
 #pragma unroll                                           // no compiler hazard handling: interleaving two chains returned wrong sums)
         for (int s = 1; s < 6; s++) {
           MFMA_AW(A0[i], wc1a[s], bf[s]);
-#if !(EF_X & 1)
           if (G::WHOLE && (s == 1 || s == 3) && (s >> 1) < DPT) {
             // fp32 source: places 0 .. 3 of the image's nine ride in tiles 0, 1, 3 and 5 (every wave has those), the stores
             // where the first piece went, the loads where the second one did
@@ -692,7 +608,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
             if (fp) { if (s == 1) fp_slot_store(n); else fp_slot_load(n); }
             else lean_piece(i * DPT + (s >> 1));
           }
-#endif
           if (s == 4 && prev >= 0) {
             asm volatile("" : "+v"(A0[prev]), "+v"(A1[prev]));
             epi1(prev);
@@ -741,10 +656,8 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
         buf ^= 1;
       }
     }
-    STAMP(2);  // conv1
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    EF_IMG_BARRIER();
-    STAMP(3);  // barrier after conv1
+    __builtin_amdgcn_s_barrier();
 
     // ------------------------------------------------ conv2: 4x4 stride 2, 32 -> 64 (wave = 32 channels x half the tiles)
     {
@@ -758,11 +671,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
           const int s = 8 * h + i, ky = s >> 2, kx = s & 3;
-#if EF_VAR & 1
-          bf[i] = kconst; (void)base;
-#else
           bf[i] = *reinterpret_cast<const u32x4*>(base + ky * G::PITCH1 + kx * ACT1_STRIDE);
-#endif
         }
       };
       u32x4 fa[8], fb[8];
@@ -771,11 +680,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       // other chain's 8 MFMAs - far beyond the wait states a non-adjacent dependent MFMA needs (hipcc pads
       // nothing for inline asm).
       auto ld2one = [&](const unsigned char* base, int s) -> u32x4 {
-#if EF_VAR & 1
-        (void)base; return kconst;
-#else
         return *reinterpret_cast<const u32x4*>(base + (s >> 2) * G::PITCH1 + (s & 3) * ACT1_STRIDE);
-#endif
       };
       constexpr int PER2 = (NT2 + 1) / 2;  // tiles per wave: ph, ph + 2, ...; with an odd count the last one only for ph == 0
       f32x4 C0[PER2], C1[PER2];
@@ -963,21 +868,15 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
         }
       }
     }
-    STAMP(4);  // conv2
     // Whole-image geometries without saved activations: the next image's DMA pieces (issued during conv1, thousands of
     // clocks ago) are waited for HERE, so that this barrier also publishes "the next image has landed" and the
     // end-of-image barrier can go - the waves then absorb their skew (fc2 runs on two of them) instead of meeting a
     // fourth time per image.  With saved activations the wait would also cover conv2's global stores: old scheme there.
     // (fp32 source: the last groups are stored during conv3 - the end-of-image barrier, as with saved activations)
     const bool early_land = G::WHOLE && P.act == nullptr && !fp;
-#if EF_X & 32  // scratch: nobody waits for the next image's DMA (what would a landing wait that never stalls be worth?)
-    if (early_land) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
     if (early_land) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#endif
     else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    EF_IMG_BARRIER();
-    STAMP(5);  // barrier after conv2
+    __builtin_amdgcn_s_barrier();
 
     // ------------------------------------------------ conv3: 3x3 stride 1, 64 -> 64 + soft-argmax in registers
     {
@@ -1004,11 +903,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
 #pragma unroll
         for (int i = 0; i < 9; i++) {
           const int s = 9 * h + i, tap = s >> 1, ky = tap / 3, kx = tap - 3 * ky;
-#if EF_VAR & 1
-          bf[i] = kconst; (void)base;
-#else
           bf[i] = *reinterpret_cast<const u32x4*>(base + ky * G::PITCH2 + kx * G::PX2 + 64 * (s & 1));
-#endif
         }
       };
       // Fragment reads INSIDE the MFMA chain: a ds_read_b128 issued while an MFMA is executing is free, the same read
@@ -1024,11 +919,7 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       if (d2w) *reinterpret_cast<u32x4*>(d2 + dslot * G::D2S + (lz3 >> 3) * 128 + (lz3 & 7) * 16) = d2v;
       auto ld3one = [&](const unsigned char* base, int s) -> u32x4 {
         const int tap = s >> 1, ky = tap / 3, kx = tap - 3 * ky;
-#if EF_VAR & 1
-        (void)base; return kconst;
-#else
         return *reinterpret_cast<const u32x4*>(base + ky * G::PITCH2 + kx * G::PX2 + 64 * (s & 1));
-#endif
       };
       // a tile's epilogue (ReLU, temperature scale, the saved-activation store) runs inside the NEXT tile's chain, after its
       // fifth MFMA: the finished accumulator is long past its read-after-MFMA hazard there (no s_nop 11), and the VALU
@@ -1070,13 +961,8 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       }
       MFMA_CHAIN_END(accs[NT3 - 1]);
       epi3(NT3 - 1);
-      STAMP(6);  // conv3 MFMA part
       // pass 1: per-channel max over the image (tiles in registers, then the 16 pixel lanes)
       float mx[4], se[4], sx[4], sy[4];
-#if EF_X & 16
-#pragma unroll
-      for (int q = 0; q < 4; q++) { mx[q] = v3[0][q]; se[q] = v3[1][q]; sx[q] = v3[2][q]; sy[q] = v3[NT3 - 1][q]; }
-#else
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         float m = v3[0][q];
@@ -1109,7 +995,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       EF_ROW16_4("v_add_f32_dpp", se);
       EF_ROW16_4("v_add_f32_dpp", sx);
       EF_ROW16_4("v_add_f32_dpp", sy);
-#endif
       if constexpr (G::DEFER) {
         // running (max, sum exp, sum exp x, sum exp y) of this image's first 48 pixels, channel 16 w + 4 g + q: the
         // leftover pixel joins them when its group's tiles have run
@@ -1138,7 +1023,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       }
     }
 
-    STAMP(7);  // soft-argmax
     // ------------------------------------------------ the group's leftover pixels: one conv2 tile, one conv3 tile, the merge
     if constexpr (G::DEFER) {
       if (dslot == EF_DCHUNK - 1 || !has_next) {
@@ -1286,7 +1170,6 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
         }
       }
     }
-    STAMP(8);  // FC tail (every 8th image)
     if (!has_next) {
       // (the last image's conv1 fetched that image once more - lean pieces never branch on has_next: an LDS-DMA write must
       // not still be in flight when the workgroup's LDS is handed to the next one)
@@ -1297,17 +1180,10 @@ __global__ __launch_bounds__(256, 1) void encoder_fused_kernel(EFArgs a_) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the next image has landed
       __syncthreads();                                  // ... and everyone's
     }
-    STAMP(9);  // next image landed + end-of-image barrier
     cur = nxt; it++; buf ^= 1;
   }
-#if defined(EF_STAMPS) || defined(EF_BLKCLK)
-  n_served += it + 1;
-#endif
   __syncthreads();  // (a workgroup that goes on with the next problem: nobody still reads what its prologue overwrites)
   }  // problems of this workgroup
-#if defined(EF_STAMPS) || defined(EF_BLKCLK)
-  if (threadIdx.x == 0 && blockIdx.x < 256) { ef_blk[blockIdx.x] = clock64() - t_entry; ef_blk[256 + blockIdx.x] = n_served; }
-#endif
 }
 
 
@@ -1317,7 +1193,7 @@ extern "C" int tacorl_encoder_fused_supported(int H, int W) {
 #define X(h, w) if (H == h && W == w) return EFGeom<h, w>::OK ? 1 : 0;
   EF_GEOMS(X)
 #undef X
-  return ef_ring_supported(H, W);  // geometries whose conv1 output does not fit the LDS: encoder_ring.hip (no saved activations)
+  return ef_ring_supported(H, W);  // geometries whose conv1 output does not fit the LDS: encoder_ring.hip
 }
 
 template <int H, int W>

@@ -722,12 +722,6 @@ int launch_reduce(const MlpWgReduceArgs& r, int gx, int Ly, int nprob, hipStream
 // [Mp][256] (Mp = M rounded up to 64, zero rows beyond M) - 4 bytes per element instead of 4 (+ 4 for dZ) - and both
 // leave through LDS as 16-byte-per-lane coalesced stores.  Same structure as mlp_fused_{fwd,bwd}_body otherwise.
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-#ifdef MLP_STAMPS  // scratch builds (scratch/mklib2.sh): phase clocks of one workgroup's wave 0, read by tacorl_dbg_mlp_stamps
-__device__ unsigned long long g_mlp_stamps[2][64];
-#define MLP_STAMP(k, j) do { if (stamp_on) g_mlp_stamps[k][j] = clock64(); } while (0)
-#else
-#define MLP_STAMP(k, j) do { } while (0)
-#endif
 
 struct MlpBigFwdArgs {
   MlpXSeg seg[MF_MAXP][MF_MAXSEG];  // gathered layer-0 input (see MlpFwdArgs)
@@ -746,7 +740,6 @@ struct MlpBigFwdArgs {
   long woff[MF_MAXL], boff[MF_MAXL];
   int dims[MF_MAXL + 1], acts[MF_MAXL];
   int L, ldx;
-  int dbg;  // read only by -DMLP_PERS_DBG scratch builds of the persistent kernel (set by hand there); always 0 otherwise
 };
 
 // BMF_ rows per workgroup: 128 for >= 16 384 rows (C5), 32 for the thousands of rows of the other configurations' Q
@@ -762,10 +755,6 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
   if (m0 >= Mp) return;  // (a block of padding rows only still writes their zeros)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, g = lane >> 4;
   const int n0 = MF_CW * w;
-#ifdef MLP_STAMPS
-  const bool stamp_on = blockIdx.x == 300 && p == 0 && tid == 0;
-#endif
-  MLP_STAMP(0, 0);
   // ONE global round trip in front of the first layer: the input rows (8-column chunks, up to two per thread) and the
   // first layer's weights are requested together, LDS is zeroed meanwhile; no barrier of the prologue drains vmcnt
   // (a workgroup starts behind the 393 KB its predecessor on this CU has just stored: every dependent round trip
@@ -843,7 +832,6 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
   lds_barrier();
   int cur = 0;
   for (int l = 0; l < a.L; l++) {
-    MLP_STAMP(0, 8 * l + 1);
     const int K = a.dims[l], N = a.dims[l + 1], KS = (K + 31) / 32, act = a.acts[l];
     const bool hidden = l + 1 < a.L;
     const float* bias = a.params[p] + a.boff[l];
@@ -876,11 +864,9 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
           }
       }
     }
-    MLP_STAMP(0, 8 * l + 2);
     if (hidden && n0 < a.dims[l + 2]) load_layer(l + 1);
     // (the copy-out of the previous layer read both buffers: nobody may write xout before every wave is past it)
     lds_barrier();
-    MLP_STAMP(0, 8 * l + 3);
     if (hidden) {  // SiLU over all 256 columns (mlp_big_prob_ok): y = z sg, act' = sg + y (1 - sg), one exp / rcp for both
 #pragma unroll
       for (int nt = 0; nt < MF_NTW; nt++) {
@@ -918,9 +904,7 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
         }
       }
     }
-    MLP_STAMP(0, 8 * l + 4);
     lds_barrier();  // xout complete, xin dead
-    MLP_STAMP(0, 8 * l + 5);
     if (hidden) {
       // act' through the dead input buffer, then both copies leave as 16-byte coalesced stores
       _Float16* sb = reinterpret_cast<_Float16*>(X + cur * BMF * XP);
@@ -934,7 +918,6 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
         }
       }
       lds_barrier();
-      MLP_STAMP(0, 8 * l + 6);
       __bf16* y16 = reinterpret_cast<__bf16*>(a.act[p] + a.ybf[p][l]);
       __bf16* s16 = reinterpret_cast<__bf16*>(a.act[p] + a.sbf[p][l]);  // (fp16 payload moved as 16-byte vectors)
       const int c8n = N >> 3;
@@ -952,7 +935,6 @@ __device__ __forceinline__ void mlp_big_fwd_body(const MlpBigFwdArgs& a) {
         }
       }
     }
-    MLP_STAMP(0, 8 * l + 7);
     cur ^= 1;
   }
 }
@@ -989,11 +971,6 @@ __global__ __launch_bounds__(PF_NT) void mlp_pers_fwd_kernel(MlpBigFwdArgs a) {
   float* BI = reinterpret_cast<float*>(smem + PF_XB + PF_SB + PF_W0B); // hidden biases [NH + 1][256]
   float* WO = BI + 3 * 256;                                            // output layer [NL <= 4][256], then its bias [4]
   constexpr int L = NH + 2;
-#ifdef MLP_PERS_DBG  // scratch builds only (scratch/mklib_file.sh ... -DMLP_PERS_DBG, scratch/r5_mlp_dissect.sh): phases switched off at run time
-  const int dbg = a.dbg;
-#else
-  constexpr int dbg = 0;
-#endif
   const int p = blockIdx.y, M = a.M[p], Mp = (M + 63) & ~63, nblk = Mp / PF_BM;
   if ((int)blockIdx.x >= nblk) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i = lane & 15, g = lane >> 4;
@@ -1109,8 +1086,7 @@ __global__ __launch_bounds__(PF_NT) void mlp_pers_fwd_kernel(MlpBigFwdArgs a) {
       for (int mt = 0; mt < PF_MT; mt++)
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (dbg & 4) {  // (scratch timing: no MFMA loop)
-      } else if (l == 0) {
+      if (l == 0) {
 #pragma unroll
         for (int ks = 0; ks < PF_K0S; ks++) {
           if (ks >= KS0) break;
@@ -1138,7 +1114,7 @@ __global__ __launch_bounds__(PF_NT) void mlp_pers_fwd_kernel(MlpBigFwdArgs a) {
         }
       }
       lds_barrier();  // the previous layer's copy-out has left S and xout
-      if (!(dbg & 8)) {  // (dbg 8, scratch timing: no epilogue)
+      {
         const int col = n0 + 8 * g;  // this lane's 8 adjacent columns: tile 0 -> col .. col + 3, tile 1 -> col + 4 .. col + 7
         const f32x4 bv0 = *reinterpret_cast<const f32x4*>(BI + 256 * l + col), bv1 = *reinterpret_cast<const f32x4*>(BI + 256 * l + col + 4);
 #pragma unroll
@@ -1156,7 +1132,7 @@ __global__ __launch_bounds__(PF_NT) void mlp_pers_fwd_kernel(MlpBigFwdArgs a) {
             for (int r = 0; r < 4; r += 2) {
               const f32x2 z = {z4[r], z4[r + 1]};
               const f32x2 t = z * f32x2{-1.44269504088896341f, -1.44269504088896341f};
-              const f32x2 d = f32x2{(dbg & 2) ? 1.f : __builtin_amdgcn_exp2f(t[0]), (dbg & 2) ? 1.f : __builtin_amdgcn_exp2f(t[1])} + f32x2{1.f, 1.f};
+              const f32x2 d = f32x2{__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])} + f32x2{1.f, 1.f};
               const f32x2 sg = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
               const f32x2 y = z * sg;
               const f32x2 sd = sg + y * (f32x2{1.f, 1.f} - sg);
@@ -1182,10 +1158,8 @@ __global__ __launch_bounds__(PF_NT) void mlp_pers_fwd_kernel(MlpBigFwdArgs a) {
             yv = *reinterpret_cast<const bf16x8*>(xout + row * XP + k);
             sv = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const __bf16*>(S) + row * XP + k);
           }
-          if (!(dbg & 1)) {
-            *reinterpret_cast<bf16x8*>(y16 + (long)(m0 + row) * 256 + k) = yv;
-            *reinterpret_cast<bf16x8*>(s16 + (long)(m0 + row) * 256 + k) = sv;
-          } else asm volatile("" :: "v"(yv), "v"(sv));
+          *reinterpret_cast<bf16x8*>(y16 + (long)(m0 + row) * 256 + k) = yv;
+          *reinterpret_cast<bf16x8*>(s16 + (long)(m0 + row) * 256 + k) = sv;
         }
       }
       cur ^= 1;
@@ -1974,11 +1948,6 @@ bool mlp_big_prob_ok(int M, int L, const int* dims, const int* acts) {
   }
   return true;
 }
-#ifdef MLP_STAMPS
-extern "C" int tacorl_dbg_mlp_stamps(unsigned long long* dst) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_mlp_stamps), sizeof(g_mlp_stamps)) == hipSuccess ? 0 : -1;
-}
-#endif
 // rows per workgroup of the many-row forward / input-gradient kernels: 128 / 64 at >= 16 384 rows, 32 / 32 below
 static bool mlp_rows_huge(int maxM) { return maxM >= 16384; }
 template <class Args>

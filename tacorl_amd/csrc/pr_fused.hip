@@ -119,27 +119,8 @@ __device__ __forceinline__ void layer_norm32_r(f32x4 (&v)[2], const f32x4 (&ww)[
     for (int r = 0; r < 4; r++) v[nt][r] = (v[nt][r] - mean) * rstd * ww[nt][r] + bb[nt][r];
 }
 
-// Phase clocks of the inference launches (scratch builds with -DPR_STAMPS only): wave 0 of workgroup 0 accumulates shader-clock
-// deltas per phase; read back (and reset) with tacorl_pr_stamps_read.
-#ifdef PR_STAMPS
-__device__ unsigned long long pr_stamps[16];
-#define PR_STAMP(k)                                          \
-  do {                                                       \
-    if (blockIdx.x == 0 && threadIdx.x == 0) {               \
-      const unsigned long long t_ = clock64();               \
-      atomicAdd(&pr_stamps[k], t_ - t_prev);                 \
-      t_prev = t_;                                           \
-    }                                                        \
-  } while (0)
-#else
-#define PR_STAMP(k)
-#endif
-
 template <int RT>
 __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
-#ifdef PR_STAMPS
-  unsigned long long t_prev = clock64();
-#endif
   constexpr int T = 16 * RT;
   __shared__ __attribute__((aligned(16))) __bf16 xb_s[4][T * XB_P];
   __shared__ __attribute__((aligned(16))) unsigned char big_s[4][T * HB_P * 2];  // q|k|v (fp32) or FFN hidden chunk (bf16)
@@ -247,7 +228,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) *reinterpret_cast<f32x4*>(S.xin + rrow[rt] * PR_D + 16 * nt + 4 * g) = x[rt][nt];
     }
-    PR_STAMP(0);
     // ---- q|k|v = x Win^T + b  (this wave's 3 of the 6 N tiles, K = 32)
     put_xb(x);
     lds_sync();
@@ -270,7 +250,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
       }
     }
     lds_sync();
-    PR_STAMP(1);
     // ---- attention: this wave's 2 heads x T queries = 2 T (head, query) pairs, one per lane; result -> xatt (bf16)
     {
       const int p = lane & (2 * T - 1), h = 2 * w + p / T, qi = p % T;
@@ -305,7 +284,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
     }
     __syncthreads();  // the four waves' columns of the attention result (the previous layer's readers of xatt passed the
                       // barrier of its FFN exchange)
-    PR_STAMP(2);
     // ---- out-projection + residual + LayerNorm 1
     {
       bf16x8 af[RT];
@@ -334,7 +312,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
     }
     put_xb(x);  // (the out-projection read xatt, not xb)
     lds_sync();
-    PR_STAMP(3);
     // ---- FFN: relu(x W1^T + b1) W2^T + b2, hidden processed in chunks of 256 kept in LDS as bf16
     if (b1_staged) {
 #pragma unroll
@@ -392,7 +369,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
       lds_sync();  // hidden chunk consumed before the next one overwrites it
     };
     for (int c = w; c < nchunk; c += 4) ffn_chunk(c, c + 4 < nchunk);
-    PR_STAMP(4);
     // the four partial FFN outputs meet in LDS (fixed summation order: every wave ends with the same bits).
     // One barrier for it per layer: the buffer alternates with the layer, and a wave can only reach layer l + 2's write
     // after every wave has passed layer l + 1's barriers, i.e. finished reading layer l's partials.
@@ -416,7 +392,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused_kernel(PrArgs a) {
     }
 #pragma unroll
     for (int rt = 0; rt < RT; rt++) layer_norm32_r(x[rt], n2w, n2b, g, sv0 ? S.st2 + 2 * rrow[rt] : nullptr);
-    PR_STAMP(5);
   }
   if (w != 0) {  // every wave holds the same result: wave 0 writes it
     // ... while waves 1 - 3 write the columns of this sequence's decoder input rows that do not wait for the plan: bf16 of
@@ -543,9 +518,6 @@ __device__ __forceinline__ void layer_norm64(f32x4 (&v)[4], const f32x4 (&ww)[4]
 
 template <int RT>
 __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
-#ifdef PR_STAMPS
-  unsigned long long t_prev = clock64();
-#endif
   constexpr int T = 16 * RT;
   constexpr int BIG = (T * QKV6_P * 4 > T * HB6_P * 2) ? T * QKV6_P * 4 : T * HB6_P * 2;
   __shared__ __attribute__((aligned(16))) __bf16 xb_s[4][T * XB6_P];
@@ -554,7 +526,8 @@ __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
   // The attention is SPLIT over the four waves (round 5; redundant before, as in the d_model-32 kernel): wave w owns heads 2 w and
   // 2 w + 1 - the q / k / v column tiles w, 4 + w, 8 + w of the in-projection, 2 T (head, query) pairs - and writes its 16 columns
   // of the result into this shared operand of the out-projection.  At T = 32 every lane read 2 x 32 B of k and of v per key as
-  // broadcast ds_read_b128 (1 KB of LDS return path for 32 distinct bytes), four waves at once: 35 % of the launch (phase clocks).
+  // broadcast ds_read_b128 (1 KB of LDS return path for 32 distinct bytes), four waves at once: 35 % of the launch (phase clocks of
+  // wave 0 of workgroup 0, a compile-time instrument that this file carried up to commit 071142c).
   __shared__ __attribute__((aligned(16))) __bf16 xatt[T * XB6_P];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
   const int b = blockIdx.x;
@@ -589,7 +562,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
   const int nchunk = a.FF / CH6;
   for (int l = 0; l < a.L; l++) {
     const PrLayerOff& o = a.l[l];
-    PR_STAMP(0);
     // Operands are requested a phase ahead, in front of the LDS waits (which also fence memory for the compiler): fetched where
     // they are consumed, each phase of this latency-bound launch began with an exposed L2 round trip (round 5; the d_model-32
     // kernel above does the same).  Projection weights come from the bf16 mirror - the very values cvt8 of the fp32 block gives.
@@ -632,7 +604,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
       n1b[nt] = *reinterpret_cast<const f32x4*>(a.P + o.n1b + 16 * nt + 4 * g);
     }
     lds_sync();
-    PR_STAMP(1);
     // ---- attention: this wave's 2 heads x T queries, one (head, query) pair per lane (T = 16: the upper half of the wave repeats
     // the lower one and does not store), head_dim 8; result -> xatt (bf16)
     {
@@ -686,7 +657,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
     fetch_w1(c0);
     __syncthreads();  // the four waves' columns of the attention result (the previous layer's readers of xatt passed the two
                       // barriers of its FFN exchange)
-    PR_STAMP(2);
     // ---- out-projection + residual + LayerNorm 1
     {
       bf16x8 af[RT][2];
@@ -714,7 +684,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
     for (int nt = 0; nt < 4; nt++) b2v[nt] = *reinterpret_cast<const f32x4*>(a.P + o.b2 + 16 * nt + 4 * g);
     put_xb(x);  // (the out-projection read xatt, not xb)
     lds_sync();
-    PR_STAMP(3);
     // ---- FFN: relu(x W1^T + b1) W2^T + b2, hidden in chunks of 128 kept in LDS as bf16
     bf16x8 xf[RT][2];
     get_xf(xf);
@@ -750,7 +719,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
       if (c + 4 < nchunk) fetch_w2(c + 4);  // (in flight under the first half of the next chunk)
       lds_sync();  // hidden chunk consumed before the next one overwrites it
     }
-    PR_STAMP(4);
     // (requested in front of the workgroup barriers below: LayerNorm 2)
     f32x4 n2w[4], n2b[4];
 #pragma unroll
@@ -779,7 +747,6 @@ __global__ __launch_bounds__(256) void pr_encoder_fused64_kernel(PrArgs a) {
     }
 #pragma unroll
     for (int rt = 0; rt < RT; rt++) layer_norm64(x[rt], n2w, n2b);
-    PR_STAMP(5);
   }
   if (w != 0) return;  // every wave holds the same result: wave 0 writes it
   // ---- mean over the T time steps
@@ -1315,14 +1282,3 @@ extern "C" int tacorl_pr_encoder_bwd_fused(const float* params, const long* offs
   hipLaunchKernelGGL(pr_ln_reduce_kernel, dim3(2 * L), dim3(256), 0, (hipStream_t)stream, r);
   return hipGetLastError() == hipSuccess ? TACORL_OK : TACORL_ELAUNCH;
 }
-
-#ifdef PR_STAMPS
-extern "C" int tacorl_pr_stamps_read(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pr_stamps), sizeof(pr_stamps)) != hipSuccess) return TACORL_ELAUNCH;
-  if (reset) {
-    unsigned long long z[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(pr_stamps), z, sizeof(z)) != hipSuccess) return TACORL_ELAUNCH;
-  }
-  return TACORL_OK;
-}
-#endif

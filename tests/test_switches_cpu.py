@@ -40,3 +40,28 @@ def test_switches_read_equal_switches_documented():
     assert not outside & read, f"listed as read by bench.py / tests only, but the package reads them: {sorted(outside & read)}"
     assert read - table == set(), f"read under tacorl_amd/ but missing from INTEGRATION.md's table: {sorted(read - table)}"
     assert table - outside - read == set(), f"in INTEGRATION.md's table but read nowhere under tacorl_amd/: {sorted(table - outside - read)}"
+
+
+CONDITIONAL = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b")
+DEFINED = re.compile(r"""extern\s+"C"[^;{(]*?\b(tacorl_[a-z0-9_]+)\s*\(""")
+
+
+def test_kernel_sources_build_one_way():
+    """The compile-time half of the same rule: no preprocessor conditional under csrc/ (a kernel source is the one kernel that
+    ships, not a family of measurement builds), and no extern "C" entry point that include/tacorl_hip.h does not declare
+    (tests/test_abi_cpu.py checks the other direction on the built library)."""
+    from tests.test_abi_cpu import _header_symbols
+
+    sources = [f for f in (ROOT / "tacorl_amd" / "csrc").iterdir() if f.suffix in (".hip", ".h")]
+    lines, conditionals, defined = 0, [], set()
+    for f in sources:
+        text = f.read_text(errors="replace")
+        for no, line in enumerate(text.splitlines(), 1):
+            lines += 1
+            if CONDITIONAL.match(line):
+                conditionals.append(f"{f.name}:{no}: {line.strip()}")
+        defined.update(DEFINED.findall(text))
+    declared = set(_header_symbols())
+    assert lines and defined and declared, "the scan found nothing: csrc/ has moved or the patterns no longer match"
+    assert not conditionals, conditionals
+    assert defined - declared == set(), f'defined extern "C" under csrc/ but not declared in tacorl_hip.h: {sorted(defined - declared)}'
