@@ -1108,6 +1108,33 @@ typedef struct {
 int tacorl_noise_fill(const void* segs, int n_seg, void* base_f32, void* base_u8, unsigned long long seed, unsigned int step,
                       int sample0, tacorl_stream_t stream);
 
+/* ---- a rollout step's draws: the same generator, the sample and step words of the counter taken from a per-row table ----
+ * Row r of a batch of up to TACORL_NOISE_ROWS_MAX environments runs its own episode at its own step, so
+ *     counter = (j >> 2, episode[r], draw_id << 16, number[r])        key = (seed & 0xffffffff, seed >> 32)
+ * with number[r] = step[r] (seg.which == 0) or plan_no[r] (seg.which == 1); the conversions are tacorl_noise_fill's (uniform,
+ * normal).  An element is a function of (seed, draw id, episode, number, j) alone: not of the row, not of n_rows.  A segment
+ * is (n_rows, inner) floats row-major at `offset` of base_f32; rows whose bit of `mask` is clear are NOT WRITTEN (and cost no
+ * thread): the plan and CEM draws are needed for the rows that re-plan only.  One thread per group of four of the rows in the
+ * mask, one launch for up to TACORL_NOISE_ROWS_SEGS segments.
+ * `rows` is a HOST struct: checked on the host, then passed to the kernel BY VALUE in its launch arguments, so the call is
+ * asynchronous, copies nothing and the caller may overwrite the struct as soon as the call returns.  Refused with
+ * TACORL_EINVAL before anything is launched: n_rows outside 1..TACORL_NOISE_ROWS_MAX, n_seg outside
+ * 1..TACORL_NOISE_ROWS_SEGS, a kind other than normal / uniform, which other than 0 / 1, draw_id outside 16 bits, inner < 1,
+ * offset < 0 or a segment that ends past n_f32 (offset + n_rows inner), mask bits at or above n_rows, a non-zero reserved
+ * field, base_f32 NULL or not 16-byte aligned.  A call whose masks are all empty launches nothing. */
+#define TACORL_NOISE_ROWS_MAX 64
+#define TACORL_NOISE_ROWS_SEGS 4
+typedef struct {
+  int offset, kind, draw_id, inner, which, reserved;
+  unsigned long long mask;
+} tacorl_noise_rows_seg;
+typedef struct {
+  int n_rows, n_seg, n_f32, reserved;
+  unsigned int episode[TACORL_NOISE_ROWS_MAX], step[TACORL_NOISE_ROWS_MAX], plan_no[TACORL_NOISE_ROWS_MAX];
+  tacorl_noise_rows_seg seg[TACORL_NOISE_ROWS_SEGS];
+} tacorl_noise_rows;
+int tacorl_noise_fill_rows(const void* rows, void* base_f32, unsigned long long seed, tacorl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,7 @@ _SIGS = {
     "tacorl_rows_mlp_npw": (_i, [_i, _i]),
     "tacorl_rows_mlp_fwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "tacorl_noise_fill": (_i, [_p, _i, _p, _p, C.c_ulonglong, C.c_uint, _i, _p]),
+    "tacorl_noise_fill_rows": (_i, [_p, _p, C.c_ulonglong, _p]),
 }
 
 _lib = None

@@ -97,7 +97,96 @@ __global__ __launch_bounds__(NOISE_WG) void noise_fill_kernel(NoiseTbl t, float*
     if (i < nj) d[i] = v[i];
 }
 
+// ---- a rollout step's draws: sample and step word per row (tacorl_hip.h, tacorl_noise_fill_rows) ----
+// The table travels by value; rowlist[s] lists the rows of segment s's mask in ascending order, so the groups of a launch
+// are numbered densely over the rows that are drawn and a row outside the mask costs no thread.
+struct RowsTbl {
+  int n_seg, n_groups;
+  int group0[TACORL_NOISE_ROWS_SEGS], offset[TACORL_NOISE_ROWS_SEGS], kind[TACORL_NOISE_ROWS_SEGS];
+  int inner[TACORL_NOISE_ROWS_SEGS], which[TACORL_NOISE_ROWS_SEGS];
+  uint32_t ctr2[TACORL_NOISE_ROWS_SEGS];  // draw_id << 16
+  uint32_t episode[TACORL_NOISE_ROWS_MAX];
+  uint32_t number[2][TACORL_NOISE_ROWS_MAX];  // [0]: step, [1]: plan_no
+  unsigned char rowlist[TACORL_NOISE_ROWS_SEGS][TACORL_NOISE_ROWS_MAX];
+};
+
+__global__ __launch_bounds__(NOISE_WG) void noise_fill_rows_kernel(RowsTbl t, float* __restrict__ base_f32, uint32_t key0,
+                                                                   uint32_t key1) {
+  const int g = blockIdx.x * NOISE_WG + threadIdx.x;
+  if (g >= t.n_groups) return;
+  int s = 0;  // last segment whose group0 <= g (an empty segment shares its group0 with the next one: the last one wins)
+#pragma unroll
+  for (int i = 1; i < TACORL_NOISE_ROWS_SEGS; i++)
+    if (i < t.n_seg && t.group0[i] <= g) s = i;
+  const int inner = t.inner[s];
+  const int qn = (inner + 3) >> 2;
+  const int gl = g - t.group0[s];
+  const int q = gl % qn;
+  const int row = t.rowlist[s][gl / qn];
+  uint32_t w[4] = {(uint32_t)q, t.episode[row], t.ctr2[s], t.number[t.which[s]][row]};
+  philox4x32_10(w, key0, key1);
+  float v[4];
+  if (t.kind[s] == TACORL_NOISE_NORMAL) {
+    word_pair_normal(w[0], w[1], v[0], v[1]);
+    word_pair_normal(w[2], w[3], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] = word_uniform(w[i]);
+  }
+  const int j0 = q << 2;
+  const int nj = min(4, inner - j0);
+  const long at = (long)t.offset[s] + (long)row * inner + j0;  // < n_f32: checked by the entry point
+  float* d = base_f32 + at;
+  if (nj == 4 && (at & 3) == 0) {  // (base_f32 is 16-byte aligned: checked by the entry point)
+    *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    if (i < nj) d[i] = v[i];
+}
+
 }  // namespace
+
+extern "C" int tacorl_noise_fill_rows(const void* rows, void* base_f32, unsigned long long seed, tacorl_stream_t stream) {
+  if (rows == nullptr || base_f32 == nullptr || ((uintptr_t)base_f32 & 15) != 0) return TACORL_EINVAL;
+  const tacorl_noise_rows* in = static_cast<const tacorl_noise_rows*>(rows);
+  const int R = in->n_rows;
+  if (R < 1 || R > TACORL_NOISE_ROWS_MAX || in->n_seg < 1 || in->n_seg > TACORL_NOISE_ROWS_SEGS) return TACORL_EINVAL;
+  if (in->n_f32 < 0 || in->reserved != 0) return TACORL_EINVAL;
+  RowsTbl t{};
+  t.n_seg = in->n_seg;
+  long groups = 0;
+  for (int i = 0; i < in->n_seg; i++) {
+    const tacorl_noise_rows_seg& s = in->seg[i];
+    if (s.kind != TACORL_NOISE_NORMAL && s.kind != TACORL_NOISE_UNIFORM) return TACORL_EINVAL;
+    if (s.which != 0 && s.which != 1) return TACORL_EINVAL;
+    if (s.draw_id < 0 || s.draw_id > 65535 || s.inner < 1 || s.offset < 0 || s.reserved != 0) return TACORL_EINVAL;
+    if ((long)s.offset + (long)R * s.inner > (long)in->n_f32) return TACORL_EINVAL;  // (so inner <= INT_MAX - 3 too)
+    if (R < 64 && (s.mask >> R) != 0) return TACORL_EINVAL;
+    t.group0[i] = (int)groups;
+    t.offset[i] = s.offset;
+    t.kind[i] = s.kind;
+    t.inner[i] = s.inner;
+    t.which[i] = s.which;
+    t.ctr2[i] = (uint32_t)s.draw_id << 16;
+    int n = 0;
+    for (int r = 0; r < R; r++)
+      if ((s.mask >> r) & 1ull) t.rowlist[i][n++] = (unsigned char)r;
+    groups += (long)n * (((long)s.inner + 3) / 4);
+    if (groups > (long)INT_MAX - NOISE_WG) return TACORL_EINVAL;
+  }
+  if (groups == 0) return TACORL_OK;  // every mask empty: nothing to draw
+  t.n_groups = (int)groups;
+  for (int r = 0; r < R; r++) {
+    t.episode[r] = in->episode[r];
+    t.number[0][r] = in->step[r];
+    t.number[1][r] = in->plan_no[r];
+  }
+  hipLaunchKernelGGL(noise_fill_rows_kernel, dim3(cdiv(groups, NOISE_WG)), dim3(NOISE_WG), 0, (hipStream_t)stream, t,
+                     (float*)base_f32, (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+  return LAUNCH_OK();
+}
 
 extern "C" int tacorl_noise_fill(const void* segs, int n_seg, void* base_f32, void* base_u8, unsigned long long seed,
                                  unsigned int step, int sample0, tacorl_stream_t stream) {

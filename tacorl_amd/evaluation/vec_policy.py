@@ -20,7 +20,8 @@ the yardstick of tests/test_vec_policy_cpu.py (as modules/cem.py's cem_restateme
 
 `RelayPolicy` / `relay_policy_restatement` below are the same for RelayImitationLearning (rollout_manager.py:434-557): the same
 clock, a latent sub-goal from the high-level policy in place of the plan, the low-level policy in place of the decoder, no
-recurrent state.  `rollout_episodes` drives either policy.
+recurrent state.  `rollout_episodes` drives either policy, one episode per environment; `rollout_episodes_refill` runs a queue
+of episodes over the environments and refills a slot the step after its episode ends (the long-horizon evaluation).
 
 `RLPolicy` / `rl_policy_restatement` are the flat baseline (rollout_manager.py:81-180 RLRollout): one deterministic
 `actor.get_actions` per row per step, refined by CEMOptimizer under use_cem; no clock and no state.
@@ -293,6 +294,99 @@ def rollout_episodes(policy, envs, max_steps=None, batch_obs=None, noise=None, r
         if "successful_tasks" in info[r]:
             d["successful_tasks"] = info[r]["successful_tasks"]
         out.append(d)
+    return out
+
+
+def rollout_episodes_refill(policy, envs, episodes, noise=None, ingest=None, max_steps=None, batch_obs=None, actions_out=None,
+                            refill=True):
+    """A queue of episodes over the R = len(envs) = policy.R slots: episodes is a list of (key, reset_info), possibly longer
+    than R.  The first min(R, n) start in slots 0, 1, 2, ...; when a row's episode ends (`done`, or its step count reaches the
+    limit of rollout_episodes) its rollout_info is stored at the episode's position and - the queue not empty - the slot takes
+    the next episode on the following step: `env.reset(**reset_info)`, `policy.reset(rows=[r])`, `ingest.reset(rows=[r])`, the
+    row's step counter back to 0 (PlanClock re-plans a row on its first step after its reset).  Rows idle only when the queue
+    is empty (their last observation is fed again, their actions are dropped); with fewer episodes than slots the spare rows
+    idle from the start, on slot 0's first observation.
+    refill=False: a slot waits until every row is done, then all slots take the next R episodes at once - the same episodes in
+    fixed batches, for comparison.
+    noise: None or a callable (keys, steps, due_rows) -> the step's noise dict for policy.step - keys[r] / steps[r]: the key
+    and the step counter of the episode in row r (an idle row keeps its last ones; None / 0 for a row that never ran);
+    due_rows: the running rows that re-plan on this step (every running row for a policy without a clock).
+    Returns the rollout_info dicts of rollout_episodes in episode order; actions_out receives each episode's action list."""
+    R, n = len(envs), len(episodes)
+    if n == 0:
+        raise ValueError("no episodes to run")
+    if R != policy.R:
+        raise ValueError(f"{R} environments for a policy of {policy.R} rows")
+    if ingest is not None and ingest.R != R:
+        raise ValueError(f"{R} environments for an ingest of {ingest.R} rows")
+    batch_obs = batch_obs or default_batch_obs
+    clock = getattr(policy, "clock", None)
+    out = [None] * n
+    if actions_out is not None:
+        actions_out[:] = [[] for _ in range(n)]
+    raw, keys, ep = [None] * R, [None] * R, [None] * R  # ep[r]: the position of the row's running episode, None: idle
+    steps, returns, limit, info = [0] * R, [0] * R, [0] * R, [{} for _ in range(R)]
+    queue = 0
+
+    def finish(r):
+        d = {"episode_length": steps[r], "episode_return": returns[r], "success": ("success" in info[r]) and info[r]["success"]}
+        if "successful_tasks" in info[r]:
+            d["successful_tasks"] = info[r]["successful_tasks"]
+        out[ep[r]] = d
+        ep[r] = None
+
+    def start(r):
+        nonlocal queue
+        keys[r], reset_info = episodes[queue]
+        ep[r], queue = queue, queue + 1
+        raw[r] = envs[r].reset(**(reset_info or {}))
+        steps[r], returns[r], info[r] = 0, 0, {}
+        limit[r] = envs[r]._max_episode_steps if max_steps is None else min(max_steps, envs[r]._max_episode_steps)
+        if limit[r] <= 0:
+            finish(r)
+
+    def fill_slots():
+        new = []
+        for r in range(R):
+            while ep[r] is None and queue < n:
+                start(r)
+                new.append(r)
+        return sorted(set(new))
+
+    fill_slots()
+    for r in range(R):
+        if raw[r] is None:  # more slots than episodes: a spare row is fed slot 0's first observation, its environment untouched
+            raw[r] = raw[0]
+    policy.reset()
+    if ingest is not None:
+        ingest.reset()
+    while any(e is not None for e in ep):
+        running = [r for r in range(R) if ep[r] is not None]
+        if noise is not None:
+            due = running if clock is None else [r for r in clock.due() if ep[r] is not None]
+            step_noise = noise(list(keys), list(steps), due)
+        else:
+            step_noise = None
+        if ingest is not None:
+            actions = policy.step(None, None, noise=step_noise, embeddings=ingest.step(raw))
+        else:
+            observation, goal = batch_obs(raw, envs)
+            actions = policy.step(observation, goal, noise=step_noise)
+        actions = actions.cpu().numpy()
+        for r in running:
+            if actions_out is not None:
+                actions_out[ep[r]].append(actions[r].copy())
+            raw[r], reward, done, info[r] = envs[r].step(actions[r])
+            returns[r] += reward
+            steps[r] += 1
+            if done or steps[r] >= limit[r]:
+                finish(r)
+        if refill or all(e is None for e in ep):
+            new = fill_slots()
+            if new:
+                policy.reset(rows=new)
+                if ingest is not None:
+                    ingest.reset(rows=new)
     return out
 
 

@@ -22,9 +22,11 @@ DRAW_IDS = {
     "g_pi": 5, "g_next": 6, "g_cur": 7, "g_nxt": 8,                                # ... discrete-gripper Gumbel uniforms
     "eps_pr": 9,                                                                   # TACORL: the plan-recognition sample
     "eps_plan": 10, "u_plan": 11,                                                  # PlayLMP: posterior sample, random plan
+    # rollouts (RowNoise; 96 = DROPOUT_BASE + DROPOUT_MAX): the decoder's mixture uniforms, the sampled plan, CEM's population
+    "ro_rand_a": 96, "ro_rand_b": 97, "ro_plan": 98, "ro_cem": 99,
 }
 # The plan recognition's keep masks in the reference's order: [embedding] + per layer [attention, dropout1, ffn, dropout2]
-# -> ids DROPOUT_BASE + i (i < DROPOUT_MAX; a 15-layer transformer fits).  The next free id is DROPOUT_BASE + DROPOUT_MAX.
+# -> ids DROPOUT_BASE + i (i < DROPOUT_MAX; a 15-layer transformer fits).  The rollout ids follow them; the next free id is 100.
 # (PlayLMP's training step samples nothing from the action decoder - its logging pass is a loss - so no ids for that.)
 DROPOUT_BASE, DROPOUT_MAX = 32, 64
 
@@ -138,6 +140,69 @@ class DeviceNoise:
         return {"seed": self.seed, "step": self.step}
 
 
+# ------------------------------------------------------------------------------------------ a rollout step's draws
+ROWS_MAX, ROWS_SEGS = 64, 4   # TACORL_NOISE_ROWS_MAX, TACORL_NOISE_ROWS_SEGS
+BY_STEP, BY_PLAN = 0, 1       # which of a row's two numbers is a segment's step word
+
+
+class RowSegment:
+    """One (R, inner) row-major buffer at `offset` of the f32 base.  which: BY_STEP or BY_PLAN; rows: the rows that are drawn
+    (None: all of them) - the others are not written."""
+
+    def __init__(self, offset, kind, draw_id, inner, which=BY_STEP, rows=None):
+        self.offset, self.kind = int(offset), _KINDS.get(kind, kind)
+        self.draw_id = DRAW_IDS[draw_id] if isinstance(draw_id, str) else int(draw_id)
+        self.inner, self.which, self.rows = int(inner), int(which), rows
+
+
+class _RowsSeg(C.Structure):  # tacorl_noise_rows_seg
+    _fields_ = [("offset", C.c_int), ("kind", C.c_int), ("draw_id", C.c_int), ("inner", C.c_int), ("which", C.c_int),
+                ("reserved", C.c_int), ("mask", C.c_ulonglong)]
+
+
+class _Rows(C.Structure):  # tacorl_noise_rows
+    _fields_ = [("n_rows", C.c_int), ("n_seg", C.c_int), ("n_f32", C.c_int), ("reserved", C.c_int),
+                ("episode", C.c_uint * ROWS_MAX), ("step", C.c_uint * ROWS_MAX), ("plan_no", C.c_uint * ROWS_MAX),
+                ("seg", _RowsSeg * ROWS_SEGS)]
+
+
+def rows_table(rows, segments, n_f32):
+    """The host struct `tacorl_noise_fill_rows` takes.  rows: (episodes, steps, plan numbers), one entry per row each."""
+    episodes, steps, plan_nos = ([int(v) for v in x] for x in rows)
+    R = len(episodes)
+    if not (1 <= R <= ROWS_MAX and len(steps) == R and len(plan_nos) == R):
+        raise ValueError(f"{R} episodes, {len(steps)} steps, {len(plan_nos)} plan numbers: 1..{ROWS_MAX} rows, one of each per row")
+    if len(segments) > ROWS_SEGS:
+        raise ValueError(f"{len(segments)} segments: a rollout fill takes up to {ROWS_SEGS}")
+    if any(not 0 <= v < 1 << 32 for x in (episodes, steps, plan_nos) for v in x):
+        raise ValueError("episode / step / plan number: the counter holds 32 bits of each")
+    t = _Rows()
+    t.n_rows, t.n_seg, t.n_f32 = R, len(segments), int(n_f32)
+    for r in range(R):
+        t.episode[r], t.step[r], t.plan_no[r] = episodes[r], steps[r], plan_nos[r]
+    for c, s in zip(t.seg, segments):
+        mask = (1 << R) - 1 if s.rows is None else sum({1 << int(r) for r in s.rows})
+        c.offset, c.kind, c.draw_id, c.inner, c.which, c.mask = s.offset, s.kind, s.draw_id, s.inner, s.which, mask
+    return t
+
+
+class RowNoise:
+    """The rollouts' generator: its whole state is the seed, every draw is keyed by the row's own (episode, step or plan
+    number).  fill() is one asynchronous launch on the current stream; the table travels in the launch arguments."""
+
+    def __init__(self, seed):
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"device noise seed {seed}: 64 bits")
+        self.seed = seed
+
+    def fill(self, rows, segments, base):
+        from . import _lib
+
+        t = rows_table(rows, segments, base.numel())
+        _lib.call("tacorl_noise_fill_rows", C.byref(t), _lib.ptr(base), self.seed, _lib.stream())
+
+
 def rank_sample0(B_local, world_size):
     """First global sample of this rank's shard: rank x B_local, the rank taken from the process group when one exists."""
     if world_size <= 1:
@@ -208,3 +273,23 @@ def philox_restatement(seed, step, draw_id, kind, B_local, inner, n_outer=1, sam
             v = (v.astype(np.float32) < np.float32(keep_p)).astype(np.uint8)
     v = v.reshape(B_local, n_outer, -1)[..., :inner]
     return np.ascontiguousarray(v.transpose(1, 0, 2)) if outer_major else v
+
+
+def philox_rows_restatement(seed, draw_id, kind, episodes, numbers, inner):
+    """What `tacorl_noise_fill_rows` writes for one segment whose mask holds every row: (R, 1, inner), row r from the counter
+    (q, episodes[r], draw_id << 16, numbers[r]).  normal: fp64; uniform: fp64 values that are exact fp32 numbers."""
+    kind = _KINDS.get(kind, kind)
+    if kind not in (NORMAL, UNIFORM):
+        raise ValueError("a rollout segment is normal or uniform")
+    ep, nr = np.asarray(episodes, dtype=np.uint64).ravel(), np.asarray(numbers, dtype=np.uint64).ravel()
+    if not (0 <= draw_id <= 65535 and ep.shape == nr.shape and inner >= 1 and (ep < 1 << 32).all() and (nr < 1 << 32).all()):
+        raise ValueError("draw id: 16 bits; episodes / numbers: 32 bits, one of each per row")
+    qn = (inner + 3) // 4
+    ctr = np.zeros((ep.size, 1, qn, 4), dtype=np.uint64)
+    ctr[..., 0] = np.arange(qn, dtype=np.uint64)[None, None, :]
+    ctr[..., 1] = ep[:, None, None]
+    ctr[..., 2] = np.uint64(draw_id << 16)
+    ctr[..., 3] = nr[:, None, None]
+    w = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint64))
+    v = normal_from_words(w) if kind == NORMAL else uniform_from_words(w)
+    return v.reshape(ep.size, 1, -1)[..., :inner]

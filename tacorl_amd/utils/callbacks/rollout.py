@@ -20,7 +20,9 @@ it runs in or on the rank split, and the evaluation leaves torch's generators - 
 Metrics logged with sync_dist=True in the reference are averaged over ranks here (dist.reduce_logs_), and the monitored
 `val_*` keys are computed from the averaged values, so every rank's checkpoint callback sees the same number.
 
-Not built: video logging, `render` and wandb - `log_video` is accepted and ignored; RolloutLongHorizon."""
+The `rollout_lh:` entry of the same callback groups is rollout_long_horizon.py RolloutLongHorizon, a subclass of Rollout
+whose episodes run through a refilled queue with device-drawn noise.
+Not built: video logging, `render` and wandb - `log_video` is accepted and ignored."""
 import hashlib
 import json
 import logging
