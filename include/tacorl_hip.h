@@ -808,7 +808,9 @@ enum {
   TACORL_LG_ALPHA_LOSS = 0, TACORL_LG_ALPHA, TACORL_LG_ACTOR_LOSS, TACORL_LG_BELL1, TACORL_LG_BELL2,
   TACORL_LG_CONS1, TACORL_LG_CONS2, TACORL_LG_Q1LOSS, TACORL_LG_Q2LOSS, TACORL_LG_ALPHA_P,
   TACORL_LG_ALPHA_P_LOSS, TACORL_LG_Q1_DATA, TACORL_LG_Q1_RAND, TACORL_LG_Q1_POL, TACORL_LG_Q2_DATA,
-  TACORL_LG_Q2_RAND, TACORL_LG_Q2_POL, TACORL_LG_ACTION_LOSS, TACORL_LG_COUNT
+  TACORL_LG_Q2_RAND, TACORL_LG_Q2_POL, TACORL_LG_ACTION_LOSS,
+  TACORL_LG_ACTION_ACC /* second float of the action decoder's loss output, not logged */, TACORL_LG_Q1_DR3, TACORL_LG_Q2_DR3,
+  TACORL_LG_COUNT
 };
 /* alpha_loss and d/dlog_alpha (cql_offline_lightning.py:447-449); grad scaled by grad_scale. */
 int tacorl_alpha_loss(const float* logp, int B, const float* log_alpha, float target_entropy,
@@ -833,6 +835,19 @@ int tacorl_actor_head_bwd(const float* head, int ld_head, const float* eps, cons
  * gripper +-1].  The per-element arithmetic is tacorl_actor_head_bwd's `value` term; the mean is a fixed-order sum. */
 int tacorl_tanh_normal_nll(const float* head, int ld_head, const float* target, int ld_target, int M, int Ac,
                            int has_grip, float grad_scale, float* d_head, float* loss_out, tacorl_stream_t stream);
+
+/* ---- DR3 regulariser of the critics (reference cql_offline_lightning.py:424-437, 496-499) ---------- */
+/* For each of n <= 2 critics k, one workgroup each, in ONE launch: emb_obs[k], emb_next[k] are (B, Eo) fp32 rows with
+ * leading dimensions ld_obs, ld_next (the critic's own encoder over the observation cameras; emb_next is a constant).
+ *   v_k = coef / B * sum_b sum_j emb_obs[k][b][j] * emb_next[k][b][j]
+ *   logs[dr3_slots[k]] = v_k;  logs[loss_slots[k]] += v_k
+ *   d_obs[k][b][j] += coef * grad_scale / B * emb_next[k][b][j]   (rows of leading dimension ld_d; columns >= Eo untouched)
+ * Fixed summation order, no atomics (bit-reproducible); fp32 arithmetic whatever the compute mode; no allocation.
+ * TACORL_EINVAL before any launch for n outside 1..2, B < 1, Eo < 1, Eo % 32 != 0, a null pointer, a leading dimension
+ * < Eo, a slot outside the record or two outputs that share a word. */
+int tacorl_dr3_fwd_bwd(int n, const float* const* emb_obs, int ld_obs, const float* const* emb_next, int ld_next,
+                       float* const* d_obs, int ld_d, int B, int Eo, float coef, float grad_scale, float* logs,
+                       const int* dr3_slots, const int* loss_slots, tacorl_stream_t stream);
 
 /* ---- Bellman + CQL logsumexp (+ Lagrange), forward and backward fused (:284-406) -------------- */
 size_t tacorl_cql_ws_bytes(int B);

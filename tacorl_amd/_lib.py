@@ -18,7 +18,10 @@ LOG_SLOTS = [  # enum TACORL_LG_* -> reference self.log key
     "alpha_loss", "alpha", "actor_loss", "bellman_q1_loss", "bellman_q2_loss", "conservative_q1_loss",
     "conservative_q2_loss", "q1_loss", "q2_loss", "alpha_prime", "alpha_prime_loss", "q1_data", "q1_random",
     "q1_policy", "q2_data", "q2_random", "q2_policy", "action_loss",
+    None,  # (the action decoder's loss writes two floats at action_loss: this one is its gripper accuracy, which TACORL does not log)
+    "q1_dr3_loss", "q2_dr3_loss",
 ]
+DR3_SLOTS = ("q1_dr3_loss", "q2_dr3_loss")  # written (and logged) only by an engine built with a dr3_coefficient
 
 _p, _i, _l, _f, _sz = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 _SIGS = {
@@ -175,6 +178,7 @@ _SIGS = {
     "tacorl_tanh_normal_nll": (_i, [_p, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p]),
     "tacorl_cql_ws_bytes": (_sz, [_i]),
     "tacorl_cql_loss": (_i, [_p] * 13 + [_i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _p, _p, _p, _sz, _p]),
+    "tacorl_dr3_fwd_bwd": (_i, [_i, _p, _i, _p, _i, _p, _i, _i, _i, _f, _f, _p, _p, _p, _p]),
     "tacorl_adam_ws_bytes": (_sz, [_l]),
     "tacorl_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _f, _p, _p, _f, _p, _sz, _p]),
     "tacorl_adam_batch_ws_bytes": (_sz, [_i]),

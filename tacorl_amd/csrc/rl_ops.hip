@@ -753,7 +753,7 @@ extern "C" int tacorl_tanh_normal_sample_batch(int njobs, const float* const* he
 enum {
   LG_ALPHA_LOSS = 0, LG_ALPHA, LG_ACTOR_LOSS, LG_BELL1, LG_BELL2, LG_CONS1, LG_CONS2, LG_Q1LOSS, LG_Q2LOSS,
   LG_ALPHA_P, LG_ALPHA_P_LOSS, LG_Q1_DATA, LG_Q1_RAND, LG_Q1_POL, LG_Q2_DATA, LG_Q2_RAND, LG_Q2_POL, LG_ACTION_LOSS,
-  LG_COUNT
+  LG_ACTION_ACC /* the action decoder's loss writes two floats: its second output */, LG_Q1_DR3, LG_Q2_DR3, LG_COUNT
 };
 
 // alpha_loss = -mean(log_alpha * (logpi + target_entropy));  d/dlog_alpha = -mean(logpi + H)
@@ -1137,6 +1137,68 @@ extern "C" int tacorl_cql_loss(const float* q1, const float* q2, float* dq1, flo
   hipLaunchKernelGGL(cql_loss_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(cql_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, blocks * 4, g_log_alpha_prime,
                      logs);
+  return LAUNCH_OK();
+}
+
+// ================================================================ DR3 regulariser
+// dr3_k = coef * mean_b( sum_j emb_obs_k[b][j] * emb_next_k[b][j] ) for each critic k, emb_next detached
+// (cql_offline_lightning.py:424-437, 496-499): the value goes to the critic's dr3 slot and is added to its q_loss slot,
+// and d(dr3_k)/d(emb_obs_k) = coef / B * emb_next_k is ADDED into the critic's state-gradient rows (scaled by 1 / world).
+// One workgroup per critic (blockIdx.x), no atomics: every thread sums its elements i = t, t + 256, ... in that order, the
+// 256 partial sums go through the fixed butterfly of block_sum_256 - the same bits on every run.  A latency-bound launch
+// over a few KiB (B * Eo floats per operand), fp32 in both compute modes.
+struct Dr3Args {
+  const float* obs[2];
+  const float* next[2];
+  float* d_obs[2];
+  int dr3_slot[2], loss_slot[2];
+};
+__global__ __launch_bounds__(256) void dr3_fwd_bwd_kernel(Dr3Args a, int ld_obs, int ld_next, int ld_d, int B, int Eo,
+                                                          float loss_scale, float grad_scale, float* logs) {
+  __shared__ float sh[4];
+  const int k = blockIdx.x;
+  const float* __restrict__ obs = a.obs[k];
+  const float* __restrict__ next = a.next[k];
+  float* __restrict__ d = a.d_obs[k];
+  const long total = (long)B * Eo;
+  float s = 0.f;
+  for (long i = threadIdx.x; i < total; i += 256) {
+    const long b = i / Eo;
+    const int j = (int)(i - b * Eo);
+    const float nx = next[b * ld_next + j];
+    s += obs[b * ld_obs + j] * nx;
+    d[b * ld_d + j] += grad_scale * nx;
+  }
+  s = block_sum_256(s, sh);
+  if (threadIdx.x == 0) {
+    const float v = s * loss_scale;
+    logs[a.dr3_slot[k]] = v;
+    logs[a.loss_slot[k]] += v;
+  }
+}
+extern "C" int tacorl_dr3_fwd_bwd(int n, const float* const* emb_obs, int ld_obs, const float* const* emb_next, int ld_next,
+                                  float* const* d_obs, int ld_d, int B, int Eo, float coef, float grad_scale, float* logs,
+                                  const int* dr3_slots, const int* loss_slots, tacorl_stream_t stream) {
+  if (n < 1 || n > 2 || B < 1 || Eo < 1 || Eo % 32 || !emb_obs || !emb_next || !d_obs || !logs || !dr3_slots || !loss_slots)
+    return TACORL_EINVAL;
+  if (ld_obs < Eo || ld_next < Eo || ld_d < Eo) return TACORL_EINVAL;
+  Dr3Args a{};
+  for (int k = 0; k < n; k++) {
+    if (!emb_obs[k] || !emb_next[k] || !d_obs[k]) return TACORL_EINVAL;
+    if (dr3_slots[k] < 0 || dr3_slots[k] >= TACORL_LG_COUNT || loss_slots[k] < 0 || loss_slots[k] >= TACORL_LG_COUNT ||
+        loss_slots[k] == dr3_slots[k])
+      return TACORL_EINVAL;
+    a.obs[k] = emb_obs[k]; a.next[k] = emb_next[k]; a.d_obs[k] = d_obs[k];
+    a.dr3_slot[k] = dr3_slots[k]; a.loss_slot[k] = loss_slots[k];
+  }
+  if (n == 2 && (a.dr3_slot[0] == a.dr3_slot[1] || a.dr3_slot[0] == a.loss_slot[1] || a.dr3_slot[1] == a.loss_slot[0] ||
+                 a.loss_slot[0] == a.loss_slot[1] || a.d_obs[0] == a.d_obs[1]))
+    return TACORL_EINVAL;  // the two workgroups must not share a word they write
+  // one rounding each for the two factors (the restatement forms them in fp64 from the same fp32 coefficient)
+  const float loss_scale = (float)((double)coef / (double)B);
+  const float g_scale = (float)((double)coef * (double)grad_scale / (double)B);
+  hipLaunchKernelGGL(dr3_fwd_bwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, a, ld_obs, ld_next, ld_d, B, Eo,
+                     loss_scale, g_scale, logs);
   return LAUNCH_OK();
 }
 

@@ -20,7 +20,7 @@ from . import encoder_stage as stage
 from . import image_ingest as ingest
 from . import dist as D
 from . import noise as noise_mod
-from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, BF16, F32, LOG_SLOTS, call, ptr
+from ._lib import ACT_NONE, ACT_RELU, ACT_SILU, BF16, DR3_SLOTS, F32, LOG_SLOTS, call, ptr
 
 
 def _al4(x):
@@ -116,7 +116,10 @@ class ACEngine:
                  critic_lr=3e-4, deterministic_backup=False, reward_scale=1.0, clip_grad_val=1.0,
                  conservative_weight=1.0, lagrange_thresh=5.0, temp=1.0, with_lagrange=False,
                  discrete_gripper=False, target_entropy=-7.0, policy_layers=3, q_layers=3, hidden=256,
-                 compute=F32, img_dtype=torch.float32, world_size=1):
+                 compute=F32, img_dtype=torch.float32, world_size=1, dr3_coefficient=None):
+        if dr3_coefficient is not None and not dr3_coefficient > 0:
+            raise ValueError(f"dr3_coefficient must be positive (or None: no DR3 term), got {dr3_coefficient!r}")
+        self.dr3 = None if dr3_coefficient is None else float(dr3_coefficient)
         if not cams or not goal_cams:
             raise NotImplementedError("observation and goal modalities must both be non-empty (the reference's no-goal "
                                       "branch is not built)")
@@ -176,6 +179,10 @@ class ACEngine:
 
     # reference names of the policy / Q tensors inside a network's block (the visual wrappers' sub-module names)
     name_prefix = ("actor.", "critic.")
+    # DR3 coefficient (reference cql_offline_lightning.py:424-437), None: no such term.  With one, each critic's encoder also
+    # encodes the next observations (forward only: problems q1_nx / q2_nx) and phase_b (_dr3) adds the term's value to the
+    # logged critic losses and its gradient to the critics' state gradients.
+    dr3 = None
 
     def _net_block(self, head_dims, head_acts, head_names, head_parts):
         return NetBlock(self.cams, self.goal_cams, head_dims, head_acts, head_names, self.dev, head_parts=head_parts,
@@ -236,6 +243,11 @@ class ACEngine:
             # actor(obs), actor(next), q1 / q2 (obs), targets (next) = 6*B; goal only: five networks (goal) = 5*B.
             want = [("a_og", self.actor, ("obs", "goal")), ("a_nx", self.actor, ("next",)), ("q1", self.q1, ("obs", "goal")),
                     ("q2", self.q2, ("obs", "goal")), ("tq1", self.tq1, ("goal", "next")), ("tq2", self.tq2, ("goal", "next"))]
+            if self.dr3 is not None:
+                # DR3: the critics' own encoders over the next observations, forward only like a_nx (2*B more images per
+                # observation camera; a goal-only camera has no `next` slot and gets no problem).  Problems of their own: the
+                # q1 / q2 problems' activation buffers are laid out for the nbwd images their backward walks.
+                want += [("q1_nx", self.q1, ("next",)), ("q2_nx", self.q2, ("next",))]
             pr = []
             for k, net, roles in want:
                 have = [s_ for s_ in roles if s_ in sl]
@@ -251,7 +263,7 @@ class ACEngine:
         # (the first camera's table - every camera's when the two lists name the same cameras)
         self.enc_probs = self.cam_probs[self.enc_cams[0]]
         nimg = {(k, c): n_ for c in self.enc_cams for k, _, _, n_ in self.cam_probs[c]}
-        keys = [kc for k in ("a_og", "a_nx", "q1", "q2", "tq1", "tq2") for c in self.enc_cams if (kc := (k, c)) in nimg]
+        keys = [kc for k in ("a_og", "a_nx", "q1", "q2", "tq1", "tq2", "q1_nx", "q2_nx") for c in self.enc_cams if (kc := (k, c)) in nimg]
         self.enc_out = {kc: f(nimg[kc], 32) for kc in keys}
         self.enc_act = {kc: f(ops.encoder_act_layout(nimg[kc], *self.hw[kc[1]])[1]) for kc in keys}
         self.enc_dout = {(k, c): f(self.nbwd[c], 32) for k in ("a_og", "q1", "q2") for c in self.enc_cams}
@@ -268,6 +280,9 @@ class ACEngine:
         self.XQpi = {k: f(B, self.ldq) for k in ("q1", "q2")}
         self.XT = {k: f(B, self.ldq) for k in ("tq1", "tq2")}
         self.dXQ = {k: f(R, self.ldq) for k in ("q1", "q2")}
+        if self.dr3 is not None:
+            # the DR3 launch's operands per critic: [enc(obs) | enc(next)] over the observation cameras, (B, Eo) each
+            self.dr3_in = {k: (f(B, self.Eo), f(B, self.Eo)) for k in ("q1", "q2")}
 
     def _alloc_chains(self):
         """Buffers of the policy and Q chains, the sampled actions, the losses and the step's noise: what the step needs
@@ -678,6 +693,8 @@ class ACEngine:
                 self._actor_backward(bc_phase, head_cur, q1p, q2p, gs)
                 ops.mark("b:actor_bwd")
             self._critic_backward()
+            if self.dr3 is not None:
+                self._dr3(gs)  # behind _state_grads_from_q (it ADDS into dS), in front of _encoders_backward (which reads dS)
             ops.mark("b:critic_bwd")
             main_stream.wait_stream(self._bwd_stream)
             self._encoders_backward()
@@ -751,6 +768,26 @@ class ACEngine:
         B, n = self.B, self.n
         call("tacorl_reduce_rows_mod_batch", 2, ops.ptr_array([self.dXQ["q1"], self.dXQ["q2"]]), self.ldq,
              ops.ptr_array([self.dS["q1"], self.dS["q2"]]), self.lds, B, self.E, 3 * n + 1, ops.stream())
+
+    def _dr3(self, gs):
+        """q{1,2}_dr3_loss = dr3 * mean_b <enc_qk(obs)[b], enc_qk(next)[b]> over the observation cameras, enc(next) a constant
+        (reference cql_offline_lightning.py:424-437): two launches on the main stream, nodes of the captured step like their
+        neighbours.  The encoders' fp32 outputs of both image sets are gathered camera by camera, in the order of `cams`,
+        into (B, Eo) rows (one copy launch: the fused forwards may read the embeddings in place, so S is not always
+        assembled); then ONE launch for both critics logs the term, adds it to q{1,2}_loss (tacorl_cql_loss has written
+        them on this stream) and adds dr3 * gs / B * enc(next) into the observation columns of dS - the only gradient of
+        the term, which the encoder backward then carries into the critics' encoders."""
+        B, ks = self.B, ("q1", "q2")
+        with ops.copy_batch():
+            for k in ks:
+                for j, c in enumerate(self.cams):
+                    ops.copy_cols(self.enc_out[(k, c)], self.erow[(k, c)]["obs"] * 32, 32, self.dr3_in[k][0], 32 * j, self.Eo, B, 32)
+                    ops.copy_cols(self.enc_out[(k + "_nx", c)], self.erow[(k + "_nx", c)]["next"] * 32, 32, self.dr3_in[k][1],
+                                  32 * j, self.Eo, B, 32)
+        call("tacorl_dr3_fwd_bwd", 2, ops.ptr_array([self.dr3_in[k][0] for k in ks]), self.Eo,
+             ops.ptr_array([self.dr3_in[k][1] for k in ks]), self.Eo, ops.ptr_array([self.dS[k] for k in ks]), self.lds, B, self.Eo,
+             self.dr3, gs, ptr(self.logs), ops.int_array([LOG_SLOTS.index(k + "_dr3_loss") for k in ks]),
+             ops.int_array([LOG_SLOTS.index(k + "_loss") for k in ks]), ops.stream())
 
     _q_xb_current = False  # set by _q_forward: it has written the Q weight gradients' bf16 input rows (_q_xb)
     lean_mlp_acts = True  # hidden-layer outputs of the fused MLPs are recomputed by the weight-gradient launch, not saved
@@ -879,4 +916,5 @@ class ACEngine:
             fn()
         logs, div = D.reduce_logs_(self.logs, self.world)
         v = logs.cpu().tolist()
-        return dict(zip(LOG_SLOTS, [x / div for x in v]))
+        # (the DR3 slots belong to an engine built with the term: without it nothing writes them and nothing logs them)
+        return {k: x / div for k, x in zip(LOG_SLOTS, v) if k is not None and (self.dr3 is not None or k not in DR3_SLOTS)}

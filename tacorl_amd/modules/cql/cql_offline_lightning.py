@@ -24,13 +24,23 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
                  bc_epochs: int = 0, clip_grad: bool = True, clip_grad_val: int = 1,
                  conservative_weight: float = 1.0, lagrange_thresh: float = 5.0, n_action_samples: int = 10,
                  temp: float = 1.0, with_lagrange: bool = False, with_dr3: bool = False,
-                 dr3_coefficient: float = 0.03, with_vib: bool = False, vib_coefficient: float = 0.01,
+                 dr3_coefficient: float = None, with_vib: bool = False, vib_coefficient: float = 0.01,
                  real_world: bool = False, obs_modalities: List[str] = [], goal_modalities: List[str] = [],
                  action_dim: int = 7, *args, device=None, compute_dtype="f32", image_dtype="f32", world_size=1,
                  device_noise_seed=None, **kwargs):
         super().__init__()
-        if with_dr3 or with_vib:
-            raise NotImplementedError("DR3 / VIB regularisers are off in every in-scope config (SURVEY 8a A9)")
+        if with_vib:
+            raise NotImplementedError("the VIB regulariser is not built: it changes the encoder head (with_vib=True; SURVEY 8a A9)")
+        if dr3_coefficient is None:
+            # Not stated.  The bare switch keeps the refusal it had before the term was built; without the switch the
+            # coefficient is unused and the hyper-parameters record the reference's default.
+            if with_dr3:
+                raise NotImplementedError("with_dr3=True needs dr3_coefficient stated with it, as config/module/*.yaml do "
+                                          "(the reference's value is 0.03)")
+            dr3_coefficient = 0.03
+        if with_dr3 and not dr3_coefficient > 0:
+            raise ValueError(f"with_dr3=True needs dr3_coefficient > 0, got {dr3_coefficient!r}")
+        self.with_dr3, self.dr3_coefficient = bool(with_dr3), dr3_coefficient  # reference :424-437, 496-499
         self._init_runtime(device, compute_dtype, image_dtype, world_size)
         self.automatic_optimization = False  # reference :115
         self.save_hyperparameters(ignore=["play_lmp"])  # reference :116
@@ -110,7 +120,8 @@ class CQL_Offline(GraphMixin, ModuleMixin, LightningModuleBase):
             conservative_weight=hp["conservative_weight"], lagrange_thresh=hp["lagrange_thresh"], temp=hp["temp"],
             with_lagrange=hp["with_lagrange"], discrete_gripper=a["discrete_gripper"],
             target_entropy=self.target_entropy, policy_layers=a["policy_layers"], q_layers=a["q_layers"],
-            hidden=a["hidden"], compute=self.compute, img_dtype=self.img_dtype, world_size=self.world_size)
+            hidden=a["hidden"], compute=self.compute, img_dtype=self.img_dtype, world_size=self.world_size,
+            dr3_coefficient=float(self.dr3_coefficient) if self.with_dr3 else None)
 
     def _register(self):
         e = self.engine

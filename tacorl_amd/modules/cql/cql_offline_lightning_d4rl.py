@@ -27,8 +27,14 @@ class CQL_Offline(_ImageCQL):
                  state_dim=None, action_dim=None, device=None, compute_dtype="f32", world_size=1, device_noise_seed=None,
                  **kwargs):
         LightningModuleBase.__init__(self)
-        if with_dr3 or with_vib:
-            raise NotImplementedError("DR3 / VIB regularisers are off in every in-scope config (SURVEY 8a A9)")
+        if with_dr3:
+            # (the reference's D4RL critics are plain `Critic`s without get_emb_obs_representation, which its DR3 term
+            # calls: the reference itself fails with with_dr3=True on vector observations, so there is nothing to match)
+            raise NotImplementedError("with_dr3=True: the reference's D4RL critics are plain Critics without "
+                                      "get_emb_obs_representation, so the reference itself fails there; DR3 is built for "
+                                      "the image modules only")
+        if with_vib:
+            raise NotImplementedError("the VIB regulariser is not built (with_vib=True; SURVEY 8a A9)")
         self._init_runtime(device, compute_dtype, "f32", world_size)
         self.automatic_optimization = False  # reference :95
         self.save_hyperparameters(ignore=["play_lmp"])  # reference :96
